@@ -1,6 +1,6 @@
 """bench.py -- molecules/s of the TensorNet energy+force path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 With N > 1 and no torch.distributed environment the script launches its own N ranks (one per GPU) through
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`; launched by the driver under
@@ -13,16 +13,20 @@ embedding, L interaction layers, readout, per-molecule energies AND the hand-wri
                     zero-padded per-molecule energy vector per step;
   strong (BASELINE configs[2]): the SAME 256-molecule batch is sharded over the ranks by contiguous molecule ranges
                     (torchmdnet_amd.parallel.ShardedEvaluator: forces stay local, energies all-reduced over RCCL).
-With N > 1 the other mode is timed as well and reported in a sub-object.
 
-Prints ONE JSON line (rank 0).  `roofline` = the dominant KERNEL (one kernel on one shape) of the dominant kernel class,
-measured live with HIP events recorded by the library on the launch stream around every launch during the timed
-region, with the class average beside it; `roofline_scatter` = the CSR message sweeps against the HBM peak;
-`cpu_baseline` = the oracle (a restatement of the reference's PyTorch CPU path) timed on this host; `et_c4` and
-`water10k` = BASELINE configs[3] / configs[4] with their own dominant-kernel rooflines; `tensornet2` = the AceFF-2.0
-architecture at the same batch; `md_single_system` = ns/day of
-a HIP-graph-replayed 64-atom system; `one_system_8_slabs` = one rank's step of a 98 304-atom periodic box cut into 8 slabs
-(per-layer halo exchange beside the deep halo, one rank at a time on this GPU).
+A plain run sets up, runs W warm-up steps, times K steps (`ms_per_step`, `value`), writes the last timed step's outputs when
+--dump-outputs is given (DIR/energies.npy [molecules], DIR/forces.npy [atoms, 3], float32, rank 0's) and prints ONE JSON line
+(rank 0).  The inputs and weights are seeded, so two runs with the same arguments see the same batch.
+
+--full measures everything else after that, the headline timing unchanged:
+`roofline` = the dominant KERNEL (one kernel on one shape) of the dominant kernel class, measured with HIP events recorded by the
+library on the launch stream around every launch during a second timed region of K steps, with the class average beside it;
+`roofline_scatter` = the CSR message sweeps against the HBM peak; `cpu_baseline` = the oracle (a restatement of the reference's
+PyTorch CPU path) timed on this host; `et_c4` and `water10k` = BASELINE configs[3] / configs[4] with their own dominant-kernel
+rooflines; `tensornet2` = the AceFF-2.0 architecture at the same batch; `md_single_system` = ns/day of a HIP-graph-replayed
+64-atom system; `one_system_8_slabs` = one rank's step of a 98 304-atom periodic box cut into 8 slabs (per-layer halo exchange
+beside the deep halo, one rank at a time on this GPU).  With N > 1 the other scaling mode is timed as well and reported in a
+sub-object.
 """
 import argparse
 import ctypes as C
@@ -39,7 +43,7 @@ for p in (ROOT, os.path.join(ROOT, "torchmd-net_amd")):
         sys.path.insert(0, p)
 
 N_MOL, N_ATOMS = 256, 64
-# /opt/skills/guides/MI355X_MICROARCH.md: fp32 MFMA 157.3 TF, dense bf16 MFMA 2.5 PF, HBM 8 TB/s.  The split-bf16 GEMMs
+# MI355X peaks: fp32 MFMA 157.3 TF, dense bf16 MFMA 2.5 PF, HBM 8 TB/s.  The split-bf16 GEMMs
 # compute every fp32 product as 6 bf16 MFMA products (exact 3-way split, fp32 accumulation, tn_gemm_sb.hip), so their
 # fp32-equivalent ceiling is 2500 / 6 TF.
 PEAK = {"mfma_f32_tflops": 157.3, "mfma_bf16_tflops": 2500.0, "hbm_gbs": 8000.0}
@@ -641,6 +645,19 @@ def gpu_eager_baseline(args_dict, state_dict, dev, chunk=32, reps=3):
             "torch": torch.__version__, "hip": getattr(torch.version, "hip", None), "device": torch.cuda.get_device_name(dev)}
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: what a caller of the timed path received from its last step, one DIR/<name>.npy per array (float32 unless
+    the array is float64).  The energies and forces of the bench batch are ~0.2 MB, far below the 64 MB the option allows."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 # ----------------------------------------------------------------------------------------------- launch
 def self_launch(a):
     """`python bench.py --gpus N` outside torch.distributed: start N ranks of this script, one per GPU."""
@@ -668,15 +685,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--rank-step", choices=["auto", "eager", "graph"], default="auto",
-                    help="auto: eager two-phase call on one GPU (per-kernel events in the timed region), HIP-graph replay + RCCL "
+                    help="auto: eager two-phase call on one GPU (with --full, per-kernel events in timed steps), HIP-graph replay + RCCL "
                          "all-reduce per rank for N > 1; graph: force the N > 1 path (testable on one GPU under torch.distributed.run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-md", action="store_true", help="skip the HIP-graph latency leg (rocprofv3 --pmc cannot trace graph replays)")
-    ap.add_argument("--no-aux", action="store_true", help="skip the configs[3] / configs[4] legs (profiling runs)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write the energies and forces of the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline timing, measure everything else: rooflines, auxiliary legs, baselines, the other "
+                         "scaling mode (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU and eager-GPU baselines")
+    ap.add_argument("--no-md", action="store_true",
+                    help="with --full: skip the HIP-graph latency leg (rocprofv3 --pmc cannot trace graph replays)")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip the configs[3] / configs[4] legs (profiling runs)")
     ap.add_argument("--aux-only", action="store_true",
-                    help="run ONLY the auxiliary legs (ET, water box, TensorNet2) and print their line: the target of the rocprofv3 passes of tools/profile_round.sh that give these legs their kernel stats and PMC traffic")
-    ap.add_argument("--breakdown", type=str, default="", help="write the per-class / per-kernel timing table to this file")
+                    help="with --full: run ONLY the auxiliary legs (ET, water box, TensorNet2) and print their line: the target of the rocprofv3 passes of tools/profile_round.sh that give these legs their kernel stats and PMC traffic")
+    ap.add_argument("--breakdown", type=str, default="", help="with --full: write the per-class / per-kernel timing table to this file")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if (a.aux_only or a.breakdown) and not a.full:
+        ap.error("--aux-only and --breakdown are part of the --full measurement: add --full")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a))
@@ -730,8 +757,8 @@ def main():
     zs, ps, bs = (t.to(dev) for t in W.synthetic_batch(n_mol=N_MOL, n_atoms=N_ATOMS, first_seed=0))
 
     if not use_graph_step:
-        # one GPU: the eager two-phase call (graph build with its 3-integer read-back, then the enqueue-only E+F call), every
-        # launch bracketed by the library's HIP events -> the per-kernel rooflines come from the timed region itself
+        # one GPU: the eager two-phase call (graph build with its 3-integer read-back, then the enqueue-only E+F call); with --full
+        # a second timed region brackets launches with the library's HIP events -> the per-kernel rooflines come from timed steps
         def step_weak():
             return model.energy_and_forces(zw, pw, bw, None, None, N_MOL, want_forces=True)
 
@@ -766,11 +793,14 @@ def main():
         rank_step = ("eager two-phase call on the rank's pre-cut shard + one RCCL all-reduce of the zero-padded energy vector" if a.scaling == "weak"
                      else "HIP-graph replay of the static-shape step (parallel.ShardSession) + one RCCL all-reduce of the energies")
 
-    def timed(step, steps, mask):
+    def timed(step, steps, mask=None):
+        """`steps` steps between barrier + synchronize (max over ranks).  With `mask`, the library records HIP events around every
+        launch of those kernel classes and the per-kernel groups of the region come back beside the time."""
         if use_dist:
             dist.barrier()
         torch.cuda.synchronize(dev)
-        profile_begin(model, L, mask)
+        if mask is not None:
+            profile_begin(model, L, mask)
         t0 = time.perf_counter()
         for _ in range(steps):
             out = step()
@@ -778,7 +808,7 @@ def main():
         if use_dist:
             dist.barrier()
         el = time.perf_counter() - t0
-        _, groups = profile_records(model, L, stream_ptr)
+        groups = profile_records(model, L, stream_ptr)[1] if mask is not None else None
         if use_dist:
             t = torch.tensor([el], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -787,69 +817,16 @@ def main():
 
     step = step_weak if a.scaling == "weak" else step_strong
 
-    def eager_profile_step():  # per-launch HIP events need eager launches (a replayed graph has no per-kernel events)
-        if not use_graph_step:
-            return step()
-        if a.scaling == "weak":
-            return model.energy_and_forces(zw, pw, bw, None, None, N_MOL, want_forces=True)
-        m_lo, m_hi, a_lo, a_hi = ranges[rank]
-        return model.energy_and_forces(zs[a_lo:a_hi], ps[a_lo:a_hi], bs[a_lo:a_hi] - m_lo, None, None, m_hi - m_lo, want_forces=True)
-
-    for _ in range(max(a.warmup - 1, 0)):
+    for _ in range(a.warmup):
         step()
-    # one fully profiled warm-up step picks the dominant kernel class / kernel and records the breakdown
-    eager_profile_step()
-    torch.cuda.synchronize(dev)
-    profile_begin(model, L)
-    eager_profile_step()
-    classes, groups = profile_records(model, L, stream_ptr)
-    # the dominant KERNEL: the (kernel, shape) group with the largest share of the step, whatever its class's total is (two
-    # classes within 1 % of each other - per-atom GEMMs and message sweeps - used to flip the choice from run to run)
-    (dom_cls, dom_label), _ = dominant(groups, None)
-    names = list(classes)
-    (_, gemm_label), _ = dominant(groups, "gemm_node")
-
-    el, tgroups, (e, f) = timed(step, a.steps, (1 << names.index(dom_cls)) | (1 << names.index("gemm_node")))
+    el, _, (e, f) = timed(step, a.steps)
     assert torch.isfinite(e).all() and torch.isfinite(f).all()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"energies": e, "forces": f})
     mols_per_step = world * N_MOL if a.scaling == "weak" else N_MOL
 
-    other = None
-    if world > 1:  # the other scaling mode, same step count, for the record
-        ostep = step_strong if a.scaling == "weak" else step_weak
-        for _ in range(3):
-            ostep()
-        oel, _, _ = timed(ostep, a.steps, 0)
-        omols = N_MOL if a.scaling == "weak" else world * N_MOL
-        other = {"scaling": "strong" if a.scaling == "weak" else "weak", "value": omols * a.steps / oel, "unit": "molecules/s",
-                 "ms_per_step": oel / a.steps * 1e3, "molecules_per_step": omols}
-
     if rank == 0:
-        n_pairs, n_edges, _ = model._engine.counts
-        pmc = load_pmc()
-        # N = 1: records of the timed region.  N > 1: the timed region replays HIP graphs (no per-kernel events), so the
-        # records of the eager profiled step of this rank's shard stand in and the line says so.
-        live = (dom_cls, dom_label) in tgroups
-        rgroups, rsteps = (tgroups, a.steps) if live else (groups, 1)
-        kern_rec = rgroups[(dom_cls, dom_label)]
-        cls_rec = dict(ms=0.0, flops=0.0, bytes=0.0, launches=0)
-        for (c, _), v in rgroups.items():
-            if c == dom_cls:
-                for k in cls_rec:
-                    cls_rec[k] += v[k]
-        roof = roofline_of(kern_rec, dom_cls, dom_label, pmc=pmc_kernel_bytes(pmc, dom_cls, dom_label) + (pmc,))
-        roof["measured"] = ("HIP events around every launch of this kernel inside the timed region" if live else
-                            "HIP events of one eager profiled step of this rank's shard (the timed region replays HIP graphs)")
-        roof["launches_per_step"] = kern_rec["launches"] // max(rsteps, 1)
-        roof["share_of_step"] = kern_rec["ms"] / rsteps / (el / a.steps * 1e3)
-        cavg = roofline_of(cls_rec, dom_cls, "class average", pmc=pmc.get(dom_cls))
-        roof["class"] = {"name": dom_cls, "achieved": cavg["achieved"], "frac": cavg["frac"], "launches_per_step":
-                         cls_rec["launches"] // max(rsteps, 1), "share_of_step": cls_rec["ms"] / rsteps / (el / a.steps * 1e3),
-                         "traffic": cavg.get("traffic"), "traffic_ratio": cavg.get("traffic_ratio")}
-        gemm_rec = rgroups.get(("gemm_node", gemm_label))
-        if dom_cls == "message":
-            rq = request_ceiling("k_message_adjoint_rows8" if "adjoint" in dom_label else "k_message_rows8", roof["avg_launch_us"])
-            if rq:
-                roof["request_ceiling"] = rq
+        n_pairs, n_edges, _ = model._engine.counts or (None, None, None)
         out = {
             "metric": "molecules/sec (64-atom molecules) TensorNet E+F",
             "value": mols_per_step * a.steps / el,
@@ -869,10 +846,75 @@ def main():
                                     "the GPUs by molecule ranges, energies + forces, random-init weights (seed 0)"),
                        "atoms_per_gpu": N_MOL * N_ATOMS if a.scaling == "weak" else ranges[0][3] - ranges[0][2],
                        "pairs_per_gpu": n_pairs, "directed_edges_per_gpu": n_edges,
-                       "parallelism": f"molecule-sharded x{world}, RCCL all-reduce of energies"},
-            "roofline": roof,
+                       "parallelism": f"molecule-sharded x{world}, RCCL all-reduce of energies",
+                       "rank_step": rank_step},
         }
-        out["config"]["rank_step"] = rank_step
+        if use_dist:
+            out["ranks_seen_by_rccl"] = dist.get_world_size()
+            out["rccl"] = {"backend": dist.get_backend(), "version": ".".join(str(v) for v in torch.cuda.nccl.version()),
+                           "collective_per_step": f"all_reduce(sum) of a zero-padded fp32[{mols_per_step}] energy vector"}
+    if a.full:
+        def eager_profile_step():  # per-launch HIP events need eager launches (a replayed graph has no per-kernel events)
+            if not use_graph_step:
+                return step()
+            if a.scaling == "weak":
+                return model.energy_and_forces(zw, pw, bw, None, None, N_MOL, want_forces=True)
+            m_lo, m_hi, a_lo, a_hi = ranges[rank]
+            return model.energy_and_forces(zs[a_lo:a_hi], ps[a_lo:a_hi], bs[a_lo:a_hi] - m_lo, None, None, m_hi - m_lo, want_forces=True)
+
+        # one fully profiled step picks the dominant kernel class / kernel and records the breakdown
+        eager_profile_step()
+        torch.cuda.synchronize(dev)
+        profile_begin(model, L)
+        eager_profile_step()
+        classes, groups = profile_records(model, L, stream_ptr)
+        # the dominant KERNEL: the (kernel, shape) group with the largest share of the step, whatever its class's total is (two
+        # classes within 1 % of each other - per-atom GEMMs and message sweeps - used to flip the choice from run to run)
+        (dom_cls, dom_label), _ = dominant(groups, None)
+        names = list(classes)
+        (_, gemm_label), _ = dominant(groups, "gemm_node")
+        # a second timed region of the same steps with the library's HIP events around the launches of those two classes
+        pel, tgroups, _ = timed(step, a.steps, (1 << names.index(dom_cls)) | (1 << names.index("gemm_node")))
+
+        other = None
+        if world > 1:  # the other scaling mode, same step count, for the record
+            ostep = step_strong if a.scaling == "weak" else step_weak
+            for _ in range(3):
+                ostep()
+            oel, _, _ = timed(ostep, a.steps)
+            omols = N_MOL if a.scaling == "weak" else world * N_MOL
+            other = {"scaling": "strong" if a.scaling == "weak" else "weak", "value": omols * a.steps / oel, "unit": "molecules/s",
+                     "ms_per_step": oel / a.steps * 1e3, "molecules_per_step": omols}
+
+    if a.full and rank == 0:
+        if out["config"]["pairs_per_gpu"] is None:  # the strong graph path never ran the eager model before the profiled steps
+            out["config"]["pairs_per_gpu"], out["config"]["directed_edges_per_gpu"] = model._engine.counts[:2]
+        pmc = load_pmc()
+        # N = 1: records of the profiled timed region.  N > 1: that region replays HIP graphs (no per-kernel events), so the
+        # records of the eager profiled step of this rank's shard stand in and the line says so.
+        live = (dom_cls, dom_label) in tgroups
+        rgroups, rsteps = (tgroups, a.steps) if live else (groups, 1)
+        kern_rec = rgroups[(dom_cls, dom_label)]
+        cls_rec = dict(ms=0.0, flops=0.0, bytes=0.0, launches=0)
+        for (c, _), v in rgroups.items():
+            if c == dom_cls:
+                for k in cls_rec:
+                    cls_rec[k] += v[k]
+        roof = roofline_of(kern_rec, dom_cls, dom_label, pmc=pmc_kernel_bytes(pmc, dom_cls, dom_label) + (pmc,))
+        roof["measured"] = ("HIP events around every launch of this kernel inside a timed region of the same steps" if live else
+                            "HIP events of one eager profiled step of this rank's shard (the timed region replays HIP graphs)")
+        roof["launches_per_step"] = kern_rec["launches"] // max(rsteps, 1)
+        roof["share_of_step"] = kern_rec["ms"] / rsteps / (pel / a.steps * 1e3)
+        cavg = roofline_of(cls_rec, dom_cls, "class average", pmc=pmc.get(dom_cls))
+        roof["class"] = {"name": dom_cls, "achieved": cavg["achieved"], "frac": cavg["frac"], "launches_per_step":
+                         cls_rec["launches"] // max(rsteps, 1), "share_of_step": cls_rec["ms"] / rsteps / (pel / a.steps * 1e3),
+                         "traffic": cavg.get("traffic"), "traffic_ratio": cavg.get("traffic_ratio")}
+        gemm_rec = rgroups.get(("gemm_node", gemm_label))
+        if dom_cls == "message":
+            rq = request_ceiling("k_message_adjoint_rows8" if "adjoint" in dom_label else "k_message_rows8", roof["avg_launch_us"])
+            if rq:
+                roof["request_ceiling"] = rq
+        out["roofline"] = roof
         if gemm_rec:
             if gemm_label.startswith("tlin9"):
                 gb, gk = pmc_kernel_bytes(pmc, "gemm_node", gemm_label)
@@ -881,10 +923,6 @@ def main():
                 gpmc = ((pmc.get("_per_kernel_total", {}).get("k_gemm_sb1<0>"), "k_gemm_sb1<0>", pmc)
                         if gemm_label.startswith("tensor_linear") else None)
             out["roofline_mfma"] = roofline_mfma_of(gemm_rec, gemm_label, pmc=gpmc)
-        if use_dist:
-            out["ranks_seen_by_rccl"] = dist.get_world_size()
-            out["rccl"] = {"backend": dist.get_backend(), "version": ".".join(str(v) for v in torch.cuda.nccl.version()),
-                           "collective_per_step": f"all_reduce(sum) of a zero-padded fp32[{mols_per_step}] energy vector"}
         if other:
             out["other_scaling_mode"] = other
         # north_star: "achieved HBM GB/s on the scatter": the CSR message sweeps, per kernel, from the fully profiled step
@@ -930,6 +968,7 @@ def main():
             with open(a.breakdown, "w") as fh:
                 json.dump({"one_step_profiled_ms": classes, "kernels": {f"{c}: {lab}": v for (c, lab), v in groups.items()},
                            "step_ms": el / a.steps * 1e3, "aux_legs": AUX_GROUPS}, fh, indent=1)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()

@@ -66,19 +66,27 @@ def test_seeded_init_matches_reference_checksums(golden_dir):
     assert abs(chk4 - g4["sd_checksum"]) < 1e-6 * g4["sd_checksum"]
 
 
-@pytest.mark.skipif(not R.reference_available(), reason="/root/reference not present")
-def test_state_dict_identical_to_live_reference():
-    mm = R.reference_model_module()
-    for args, seed in [(W.TINY_ARGS, 3), (dict(W.TINY_ARGS, prior_model="Atomref", prior_args={"max_z": 20}), 4),
-                       (W.ET_TINY_ARGS, 5), (dict(W.ET_TINY_ARGS, neighbor_embedding=False, distance_influence="values"), 6)]:
+def test_state_dict_identical_to_live_reference(golden_dir):
+    """Same seed -> the same initial weights as the reference: against its weights stored in tests/golden/live_reference_ref.pt
+    (oracle/make_golden_live.py) and, when the reference is importable, against the live reference too."""
+    stored = torch.load(os.path.join(golden_dir, "live_reference_ref.pt"))["state_dicts"]
+    mm = R.reference_model_module() if R.reference_available() else None
+    configs = [(W.TINY_ARGS, 3), (dict(W.TINY_ARGS, prior_model="Atomref", prior_args={"max_z": 20}), 4),
+               (W.ET_TINY_ARGS, 5), (dict(W.ET_TINY_ARGS, neighbor_embedding=False, distance_influence="values"), 6)]
+    assert len(stored) == len(configs)
+    for (args, seed), g in zip(configs, stored):
+        assert g["args"] == dict(args) and g["seed"] == seed
         torch.manual_seed(seed)
         a = create_model(dict(args))
-        torch.manual_seed(seed)
-        b = mm.create_model(dict(args))
-        sa, sb = a.state_dict(), b.state_dict()
-        assert set(sa) == set(sb)
-        for k in sa:
-            assert torch.equal(sa[k], sb[k]), k
+        refs = [g["sd"]]
+        if mm is not None:
+            torch.manual_seed(seed)
+            refs.append(mm.create_model(dict(args)).state_dict())
+        sa = a.state_dict()
+        for sb in refs:
+            assert set(sa) == set(sb)
+            for k in sa:
+                assert torch.equal(sa[k], sb[k]), k
 
 
 def _write_ckpt(path, model, args, old_layout=False):
@@ -149,7 +157,9 @@ def test_load_ensemble_and_atomref_toggle(tmp_path):
     assert one.prior_model[-1].enable is True and one._atomref_table().shape == (20,)
 
 
-def test_no_cpu_fallback_and_argument_checks():
+def test_no_cpu_fallback_and_argument_checks(monkeypatch):
+    # as on a machine without a GPU: where one is present, host tensors are staged through it (TorchMD_Net._forward_host_tensors)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     model = create_model(dict(W.TINY_ARGS))
     z, pos, batch = W.synthetic_batch(n_mol=1, n_atoms=5)
     with pytest.raises(RuntimeError, match="no CPU"):

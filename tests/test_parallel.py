@@ -226,6 +226,7 @@ def _ddp_worker(rank, world, port, tmpdir):
     params = [p for p in model.parameters() if p.requires_grad]
     w = float(rank + 1)
     M._require_cuda = lambda *a, **k: None
+    torch.cuda.is_available = lambda: False  # the stand-ins return host tensors: no staging through a GPU that may be present
     M._direct_radial_functions = lambda m: contextlib.nullcontext()
     model.energy_and_forces = lambda *a, **k: (E0.clone(), F0.clone())
     model.parameter_gradients_of = lambda z_, p_, b_, box, q, nm, ge: (E0, {p: torch.full_like(p, w * float(ge.sum())) for p in params})

@@ -2,12 +2,13 @@
 # Same-box A/B of developer switches: runs the headline bench leg once per environment setting and prints step time and the
 # per-class breakdown.  usage (through gpurun):  tools/ab_env.sh "" "TMDNET_X=1" "TMDNET_Y=1 TMDNET_Z=2" ...
 R=${GRAFT_REPO_ROOT:-$PWD}
-mkdir -p $R/gpurun_out/ab
+OUT=${OUT:-$R/bench_out}
+mkdir -p $OUT/ab
 k=0
 for envs in "$@"; do
   for rep in 1 2; do
-    out=$R/gpurun_out/ab/run${k}_${rep}
-    env $envs python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-md --no-aux --breakdown $out.bd.json > $out.json 2> $out.err
+    out=$OUT/ab/run${k}_${rep}
+    env $envs python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-md --no-aux --breakdown $out.bd.json > $out.json 2> $out.err
     python - "$out" "$envs" <<'PY'
 import json, sys
 out, envs = sys.argv[1], sys.argv[2]
