@@ -99,8 +99,28 @@ const char* tmdnet_version(void);
 /* ABI revision of this header: bumped whenever an exported signature or struct layout changes (3: `z` in
  * tmdnet_build_graph[_static], `strategy` in tmdnet_neighbor_pairs).  A binding compares its compile-time
  * TMDNET_ABI_VERSION with the loaded library's tmdnet_abi_version() before its first call. */
-#define TMDNET_ABI_VERSION 9
+#define TMDNET_ABI_VERSION 10
 int tmdnet_abi_version(void);
+
+/* Output head of the handle (ABI 10): TMDNET_HEAD_SCALAR (the default; energies), TMDNET_HEAD_DIPOLE_MOMENT (|| sum (q_i (r_i - c) +
+ * std v_i) + mean ||, reference output_modules.py:166-245), TMDNET_HEAD_SPATIAL_EXTENT (sum q_i ||r_i - c||^2 + mean,
+ * output_modules.py:248-297), TMDNET_HEAD_VECTOR (sum std v_i + mean, Equivariant Transformer only, output_modules.py:300-323).
+ * q_i is the head's scalar output times std, v_i the vector output of the Equivariant Transformer's second gated block (0 on
+ * TensorNet), c the molecule's centre of mass with the masses of the parameter "output_model.atomic_mass" ([TMDNET_MASS_TABLE_SIZE],
+ * indexed by z), r_i the positions given to tmdnet_build_graph* (not wrapped into the box; the pointer must still be valid at
+ * tmdnet_energy_forces, as for TensorNet2).  Call after tmdnet_create* and before the first tmdnet_num_params / tmdnet_set_param: the
+ * parameter list changes (the dipole and spatial-extent heads add "output_model.atomic_mass"; on the Equivariant Transformer the
+ * spatial-extent head is the MLP "output_model.output_network.layers.{0,2}.*" instead of the gated blocks).  The energy output of
+ * tmdnet_energy_forces then holds the property: n_mol floats, 3 n_mol for TMDNET_HEAD_VECTOR; the forces are minus the position
+ * gradient of the sum of its components.  TMDNET_ERR_INVALID for TensorNet2, the vector head on TensorNet, or an unknown kind.  The
+ * property heads take neither atom weights nor the halo exchange, and have no parameter-gradient or second-order pass
+ * (TMDNET_ERR_INVALID from those entries). */
+#define TMDNET_HEAD_SCALAR 0
+#define TMDNET_HEAD_DIPOLE_MOMENT 1
+#define TMDNET_HEAD_SPATIAL_EXTENT 2
+#define TMDNET_HEAD_VECTOR 3
+#define TMDNET_MASS_TABLE_SIZE 119
+int tmdnet_set_output_head(tmdnet_model* m, int32_t kind);
 
 /* Parameters are addressed by the reference's state-dict keys without the "model." prefix
  * (SURVEY.md Appendix A), e.g. "representation_model.layers.0.linears_scalar.2.weight", plus

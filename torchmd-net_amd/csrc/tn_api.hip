@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "tn_heads.h"
 #include "tn_model.h"
 #include "tn_tlin9.h"
 #include "tn_small.h"
@@ -643,6 +644,33 @@ const char* tmdnet_last_error(const tmdnet_model* m) { return m ? m->err.c_str()
 
 int tmdnet_num_params(const tmdnet_model* m) { return m ? (int)m->specs.size() : 0; }
 
+int tmdnet_set_output_head(tmdnet_model* m, int32_t kind) {
+  if (!m) return TMDNET_ERR_INVALID;
+  if (kind < TMDNET_HEAD_SCALAR || kind > TMDNET_HEAD_VECTOR)
+    return fail(m, TMDNET_ERR_INVALID, "unknown output head kind " + std::to_string(kind));
+  if (kind != TMDNET_HEAD_SCALAR && m->tn2)
+    return fail(m, TMDNET_ERR_INVALID, "TensorNet2 has the ScalarPlusWeightedCoulomb head only (no property heads)");
+  if (kind == TMDNET_HEAD_VECTOR && !m->et)
+    return fail(m, TMDNET_ERR_INVALID, "the vector output head needs the Equivariant Transformer's vector features");
+  m->host.clear();  // the parameter list changes: nothing uploaded before stays
+  m->finalized = false;
+  m->upd_ready = false;  // the packed layout changes with the head
+  m->head_kind = kind;
+  if (m->et) {  // EquivariantElectronicSpatialExtent swaps the gated blocks for an MLP: the whole list is rebuilt
+    et_head_specs(m);
+    return TMDNET_OK;
+  }
+  const std::string key = "output_model.atomic_mass";
+  auto& sp = m->specs;
+  for (size_t i = 0; i < sp.size(); ++i)
+    if (sp[i].name == key) {
+      sp.erase(sp.begin() + (long)i);
+      break;
+    }
+  if (kind != TMDNET_HEAD_SCALAR) sp.push_back({key, TMDNET_MASS_TABLE_SIZE, 1});
+  return TMDNET_OK;
+}
+
 const char* tmdnet_param_name(const tmdnet_model* m, int idx, int64_t* numel) {
   if (!m || idx < 0 || idx >= (int)m->specs.size()) return nullptr;
   if (numel) *numel = m->specs[idx].rows * m->specs[idx].cols;
@@ -778,6 +806,7 @@ static void pack_tensornet_params(tmdnet_model* m, std::map<std::string, std::ve
   put("O2", h[O + "2.weight"]);
   put("bO2", h[O + "2.bias"]);
   if (m->hp.has_atomref) put("atomref", h["atomref"]);
+  if (m->head_kind) put("mass", h["output_model.atomic_mass"]);
   // per-type tables U[z], V[z] of the pair embedding (weights only): filled once below by k_ztables
   put("Utab", std::vector<float>((size_t)m->hp.max_z * F, 0.f));
   put("Vtab", std::vector<float>((size_t)m->hp.max_z * F, 0.f));
@@ -858,6 +887,7 @@ int tmdnet_finalize_params(tmdnet_model* m) {
   P.O2 = D("O2");
   P.bO2 = D("bO2");
   P.atomref = m->hp.has_atomref ? D("atomref") : nullptr;
+  P.mass = m->head_kind ? D("mass") : nullptr;
   P.mean = h["mean"][0];
   P.std = h["std"][0];
   {  // split-bf16 tile images (tn_gemm_sb.hip / tn_gemm_sb1.hip) of every GEMM weight, keyed by its fp32 device copy
@@ -1319,6 +1349,11 @@ int tmdnet_forward_workspace_bytes(const tmdnet_model* m, int64_t n_atoms, int64
   // species count is known by now: tmdnet_build_graph precedes this query); otherwise they stay in the plan
   carve_fwd(nullptr, m->hp, n_atoms, n_mol, n_pairs, want_forces != 0, bytes, rb_possible ? 8 : 0,
             m->recompute_rows ? (rb_possible && rb_ntp(m, n_atoms, n_pairs) > 0 ? 7 : 5) : 0);
+  if (m->head_kind) {  // the property heads' molecule state, slice partials and direct position term after the forward buffers
+    size_t hb = 0;
+    carve_heads(nullptr, n_atoms, n_mol, &hb);
+    *bytes = ((*bytes + 255) & ~size_t(255)) + hb;
+  }
   return TMDNET_OK;
 }
 
@@ -1379,6 +1414,17 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
   const int ntp = rb_ntp(m, n_atoms, n_pairs);  // > 0: embedding in the radial basis (no Q / dQ per pair)
   const bool recompute = m->recompute_rows;
   FwdBuffers b = carve_fwd(ws, hp, n_atoms, n_mol, P, want_forces != 0, &need, ntp, recompute ? (ntp ? 7 : 5) : 0);
+  HeadBuffers hbuf{};
+  if (m->head_kind) {
+    if (m->train) return fail(m, TMDNET_ERR_INVALID, "the property heads (tmdnet_set_output_head) have no parameter-gradient pass");
+    if (m->atom_w || m->halo_fn)
+      return fail(m, TMDNET_ERR_INVALID, "the property heads (tmdnet_set_output_head) take neither atom weights nor the halo exchange");
+    if (!m->g_pos) return fail(m, TMDNET_ERR_STATE, "the property heads read the positions of tmdnet_build_graph: build the graph first");
+    need = (need + 255) & ~size_t(255);
+    size_t hb = 0;
+    hbuf = carve_heads(static_cast<char*>(ws) + need, n_atoms, n_mol, &hb);
+    need += hb;
+  }
   if (need > ws_bytes) return fail(m, TMDNET_ERR_WORKSPACE, "forward workspace too small: need " + std::to_string(need));
   const DevParams& W = m->P;
   const int o3 = hp.group_o3;
@@ -1395,6 +1441,11 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
   }
   if (m->graph_has_z) z = g.z_c;  // validated (clamped) and renumbered by the graph phase
   if (!z) return fail(m, TMDNET_ERR_INVALID, "z is required (here or in tmdnet_build_graph)");
+  HeadArgs heads{};
+  if (m->head_kind) {
+    heads.kind = m->head_kind; heads.N = N; heads.B = B; heads.pos = m->g_pos; heads.perm = perm; heads.z = z; heads.batch = batch;
+    heads.mass = W.mass; heads.n_mass = TMDNET_MASS_TABLE_SIZE; heads.q = b.ea; heads.mean = W.mean; heads.y = energy;
+  }
   const int64_t* batch_k = batch;
   if (q) {  // per-atom charge factor once; the kernels then read kap[n] (no dependent batch -> q gather, no range hazard)
     launch_kappa(q, batch, N, B, b.kap, s);
@@ -1459,7 +1510,7 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
   const int64_t o1_ = a0, oF = (int64_t)a0 * F, o2F = 2 * oF, o3F = 3 * oF, o9F = 9 * oF, oH = (int64_t)a0 * H;
   const float* const q_a = q ? q + o1_ : nullptr;                    // per-atom charge factor (kappa) of the active rows
   const int64_t* const batch_a = batch_k ? batch_k + o1_ : nullptr;  // their molecule index
-  const bool fused_small = !tc && !ntp && !recompute && !m->halo_fn && (small_fused_ok(N, F, H, L) || mid_fused_ok(N, F, H, L)) &&
+  const bool fused_small = !tc && !ntp && !recompute && !m->halo_fn && !m->head_kind && (small_fused_ok(N, F, H, L) || mid_fused_ok(N, F, H, L)) &&
                            (!want_forces || (message_adjoint_gd_ok(N, F) && !getenv("TMDNET_SEPARATE_PAIR_GD")));
   if (run_fwd) {
     if (use_tab) {
@@ -1621,7 +1672,13 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
     NODE();
     gemm(s, b.lnr + o3F, 3 * F, W.Lin, 3 * F, W.bLin, b.x + oF, F, Na, F, 3 * F, GEMM_ACT_SILU, b.al + oF, F);
     gemm(s, b.x + oF, F, W.O1, F, W.bO1, b.ao + oH, H, Na, H, F);
-    if ((int64_t)N <= 256 * (int64_t)B) {  // small molecules: head + per-molecule sum in one launch (a block walks its molecule)
+    if (m->head_kind) {
+      // property heads (tn_heads.hip): q_i = head MLP * std per atom with d q_i / d ao, then the two-pass molecule moments
+      KR(CAT_ELEMENTWISE, Nd * H * 4,
+         launch_head_energy(b.ao, W.O2, W.bO2, N, H, W.std, nullptr, z, b.ea, s, want_forces ? b.g_ao : nullptr));
+      heads.state = want_forces ? hbuf.state : nullptr;
+      KR(CAT_ELEMENTWISE, Nd * 32, launch_heads_reduce(g, heads, hbuf, s));
+    } else if ((int64_t)N <= 256 * (int64_t)B) {  // small molecules: head + per-molecule sum in one launch (a block walks its molecule)
       KR(CAT_ELEMENTWISE, Nd * H * 4, launch_head_mol_sum(g, b.ao, W.O2, W.bO2, N, B, H, W.std, W.atomref, z, batch, W.mean, energy, s,
                                                           want_forces ? b.g_ao : nullptr, m->atom_w, perm));
     } else {
@@ -1633,6 +1690,8 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
     }
     }  // !fused_small
   }
+  if (m->head_kind && want_forces && run_bwd)  // reverse seeds into g_ao, and the centre-of-mass term of the forces
+    KR(CAT_ELEMENTWISE, Nd * (8 * H + 40), launch_heads_seed(heads, H, b.g_ao, hbuf.direct, s));
 
   if (want_forces && run_bwd && fused_small) {
     const int gd_nw = message_adjoint_gd_waves(g, N, F, recompute);
@@ -1816,7 +1875,7 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
          launch_embed_pair_gd(g, P, F, z, W.Utab, W.Vtab, b.Q, b.dQ, b.C, b.dC, b.gA, b.gd, b.g_rhat, s, merged_gd ? b.g_delta : nullptr,
                               b.gd_slots, L * gd_nw, gd_stride));
     if (!merged_gd && !tc) KR(CAT_ELEMENTWISE, Pd * 40, launch_geom_gd(g, P, b.gd, b.g_rhat, b.g_delta, s, nullptr, 0, gd_stride));
-    if (!tc) KR(CAT_ELEMENTWISE, E_ * 8 + Nd * 12, launch_force_gather(g, N, b.g_delta, perm, forces, s));
+    if (!tc) KR(CAT_ELEMENTWISE, E_ * 8 + Nd * 12, launch_force_gather(g, N, b.g_delta, perm, forces, s, m->head_kind ? hbuf.direct : nullptr));
   }
   NODE();
   HIP_TRY(m, hipGetLastError());
@@ -1944,6 +2003,7 @@ int tmdnet_energy_param_grads(tmdnet_model* m, void* stream, void* graph_ws, voi
   // grad_energy == NULL: forward half only (energies out, every activation kept in ws / train_ws); energy == NULL: reverse half
   // only, on the workspaces a forward-half call with the same arguments left behind; both given: one pass
   if (!m || !graph_ws || !ws || !train_ws || (!grad_energy && !energy) || (grad_energy && !grads)) return TMDNET_ERR_INVALID;
+  if (m->head_kind) return fail(m, TMDNET_ERR_INVALID, "the property heads (tmdnet_set_output_head) have no parameter-gradient pass");
   recall_graph(m, graph_ws);
   if ((m->et || m->tn2) && (!grad_energy || !energy)) return fail(m, TMDNET_ERR_INVALID, "the two-call form is built for TensorNet only");
   if (n_pairs < 0) return fail(m, TMDNET_ERR_INVALID, "parameter gradients need the exact pair count (dynamic shapes)");

@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include "tn_et.h"
+#include "tn_heads.h"
 #include "tn_model.h"
 
 namespace {
@@ -37,7 +38,10 @@ struct EtParams {
   const float *Wm2, *bm2, *Wm2T;      // [F][F]
   const float *W21, *W21T;            // [F/2][F/2]
   const float *Wn1, *bn1, *Wn1T;      // [F/2][F]
-  const float *Wn2, *bn2;             // row 0 of [2][F/2], bias[0]
+  const float *Wn2, *bn2;             // [2][F/2] (row 0: scalar output, row 1: gate of the vector output), bias [2]
+  const float* W22;                   // [F/2] vec2_proj of block 2
+  const float *Ho1, *Ho1T, *hb1, *Ho2, *hb2;  // EquivariantElectronicSpatialExtent: MLP F -> F/2 -> 1 (else null)
+  const float* mass;                  // property heads with a centre of mass: atomic masses (else null)
   const float* atomref;
   float mean, std;
 };
@@ -115,6 +119,13 @@ void et_build_specs(tmdnet_model* m) {
   }
   s.push_back({R + "out_norm.weight", F, 1});
   s.push_back({R + "out_norm.bias", F, 1});
+  if (m->head_kind == TMDNET_HEAD_SPATIAL_EXTENT) {  // EquivariantElectronicSpatialExtent: the Scalar MLP F -> F/2 -> 1, no gated blocks
+    const std::string O = "output_model.output_network.layers.";
+    s.push_back({O + "0.weight", F2, F});
+    s.push_back({O + "0.bias", F2, 1});
+    s.push_back({O + "2.weight", 1, F2});
+    s.push_back({O + "2.bias", 1, 1});
+  } else {
   const std::string O0 = "output_model.output_network.0.", O1 = "output_model.output_network.1.";
   s.push_back({O0 + "vec1_proj.weight", F, F});
   s.push_back({O0 + "vec2_proj.weight", F2, F});
@@ -128,6 +139,9 @@ void et_build_specs(tmdnet_model* m) {
   s.push_back({O1 + "update_net.layers.0.bias", F2, 1});
   s.push_back({O1 + "update_net.layers.2.weight", 2, F2});
   s.push_back({O1 + "update_net.layers.2.bias", 2, 1});
+  }
+  if (m->head_kind == TMDNET_HEAD_DIPOLE_MOMENT || m->head_kind == TMDNET_HEAD_SPATIAL_EXTENT)
+    s.push_back({"output_model.atomic_mass", TMDNET_MASS_TABLE_SIZE, 1});
   s.push_back({"mean", 1, 1});
   s.push_back({"std", 1, 1});
   if (hp.has_atomref) s.push_back({"atomref", Z, 1});
@@ -231,6 +245,11 @@ EtBuffers et_carve(void* ws, const tmdnet_et_hparams& hp, int64_t N, int64_t B, 
 
 }  // namespace
 
+void et_head_specs(tmdnet_model* m) {  // tmdnet_set_output_head: the parameter list of the new head
+  m->specs.clear();
+  et_build_specs(m);
+}
+
 int et_create(tmdnet_model* m, const tmdnet_et_hparams* hp) {
   const int F = hp->hidden_channels, H = hp->num_heads;
   if (F % H) return TMDNET_ERR_INVALID;
@@ -305,6 +324,14 @@ int et_finalize(tmdnet_model* m) {
   put("lno_w", h[R + "out_norm.weight"]);
   put("lno_b", h[R + "out_norm.bias"]);
   const std::string O0 = "output_model.output_network.0.", O1 = "output_model.output_network.1.";
+  const bool mlp_head = m->head_kind == TMDNET_HEAD_SPATIAL_EXTENT;
+  if (mlp_head) {
+    const std::string O = "output_model.output_network.layers.";
+    putW("Ho1", h[O + "0.weight"], F2, F);
+    put("hb1", h[O + "0.bias"]);
+    put("Ho2", h[O + "2.weight"]);
+    put("hb2", h[O + "2.bias"]);
+  } else {
   putW("W1u", cat({&h[O0 + "vec1_proj.weight"], &h[O0 + "vec2_proj.weight"]}), F + F2, F);
   putW("Wm1", h[O0 + "update_net.layers.0.weight"], F, 2 * F);
   put("bm1", h[O0 + "update_net.layers.0.bias"]);
@@ -315,6 +342,9 @@ int et_finalize(tmdnet_model* m) {
   put("bn1", h[O1 + "update_net.layers.0.bias"]);
   put("Wn2", h[O1 + "update_net.layers.2.weight"]);  // row 0 = the scalar output (row 1 gates a vector that is dropped)
   put("bn2", h[O1 + "update_net.layers.2.bias"]);
+  put("W22", h[O1 + "vec2_proj.weight"]);  // [1][F/2]: the vector output of block 2 (dipole / vector heads)
+  }
+  if (m->head_kind == TMDNET_HEAD_DIPOLE_MOMENT || mlp_head) put("mass", h["output_model.atomic_mass"]);
   if (hp.has_atomref) put("atomref", h["atomref"]);
 
   if (m->dev && m->dev_cap < pk.buf.size()) {
@@ -383,6 +413,13 @@ int et_finalize(tmdnet_model* m) {
   }
   P.lno_w = D("lno_w");
   P.lno_b = D("lno_b");
+  if (mlp_head) {
+    P.Ho1 = D("Ho1");
+    P.Ho1T = D("Ho1T");
+    P.hb1 = D("hb1");
+    P.Ho2 = D("Ho2");
+    P.hb2 = D("hb2");
+  } else {
   P.W1u = D("W1u");
   P.W1uT = D("W1uT");
   P.Wm1 = D("Wm1");
@@ -398,6 +435,9 @@ int et_finalize(tmdnet_model* m) {
   P.Wn1T = D("Wn1T");
   P.Wn2 = D("Wn2");
   P.bn2 = D("bn2");
+  P.W22 = D("W22");
+  }
+  P.mass = m->head_kind == TMDNET_HEAD_DIPOLE_MOMENT || mlp_head ? D("mass") : nullptr;
   P.atomref = hp.has_atomref ? D("atomref") : nullptr;
   P.mean = h["mean"][0];
   P.std = h["std"][0];
@@ -480,6 +520,11 @@ void et_carve_train(void* ws, const tmdnet_model* m, int64_t N, int64_t P, Train
 int et_forward_workspace_bytes(const tmdnet_model* m, int64_t n_atoms, int64_t n_mol, int64_t n_pairs, int32_t want_forces,
                                size_t* bytes) {
   et_carve(nullptr, m->et->hp, n_atoms, n_mol, n_pairs, want_forces != 0, bytes);
+  if (m->head_kind) {  // the property heads' buffers after the forward buffers (tn_heads.hip)
+    size_t hb = 0;
+    carve_heads(nullptr, n_atoms, n_mol, &hb);
+    *bytes = ((*bytes + 255) & ~size_t(255)) + hb;
+  }
   return TMDNET_OK;
 }
 
@@ -491,9 +536,29 @@ int et_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, s
   const int P = n_pairs >= 0 ? (int)n_pairs : (int)g.pcap, P1 = P + 1;
   size_t need = 0;
   EtBuffers b = et_carve(ws, hp, n_atoms, n_mol, P, want_forces != 0, &need);
+  const int kind = m->head_kind;
+  HeadBuffers hbuf{};
+  if (kind) {
+    if (m->train) return fail(m, TMDNET_ERR_INVALID, "the property heads (tmdnet_set_output_head) have no parameter-gradient pass");
+    if (!m->g_pos) return fail(m, TMDNET_ERR_STATE, "the property heads read the positions of tmdnet_build_graph: build the graph first");
+    need = (need + 255) & ~size_t(255);
+    size_t hb = 0;
+    hbuf = carve_heads(static_cast<char*>(ws) + need, n_atoms, n_mol, &hb);
+    need += hb;
+  }
   if (need > ws_bytes) return fail(m, TMDNET_ERR_WORKSPACE, "forward workspace too small: need " + std::to_string(need));
   const EtParams& W = m->et->P;
   const int* perm = m->graph_is_cell ? g.perm : nullptr;
+  HeadArgs heads{};
+  if (kind) {
+    heads.kind = kind; heads.N = N; heads.B = B; heads.pos = m->g_pos; heads.perm = perm; heads.z = z; heads.batch = batch;
+    heads.mass = W.mass; heads.n_mass = TMDNET_MASS_TABLE_SIZE; heads.q = kind == TMDNET_HEAD_VECTOR ? nullptr : b.ea;
+    heads.mean = W.mean; heads.std = W.std; heads.y = energy; heads.state = want_forces ? hbuf.state : nullptr;
+    if (kind != TMDNET_HEAD_SPATIAL_EXTENT) {
+      heads.gate = hbuf.gate;
+      heads.vq2s = hbuf.vq2s;
+    }
+  }
   auto EDGE = [&](int add) { g_gemm_cat = CAT_GEMM_EDGE; g_mdev = n_pairs < 0 ? g.counts : nullptr; g_madd = add; };
   auto NODE = [&]() { g_gemm_cat = CAT_GEMM_NODE; g_mdev = nullptr; g_madd = 0; };
   const double Nd = N, Pd = P, Fd = F, Ed = (double)m->lastE;
@@ -577,6 +642,12 @@ int et_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, s
   NODE();
   KR(CAT_ELEMENTWISE, Nd * Fd * 12, launch_layernorm_fwd(b.x[L], W.lno_w, W.lno_b, N, F, b.xf, b.xfh, b.rstdf, s));
   const int U = F + F2;  // u12 row width: vec1_proj | vec2_proj of head block 0
+  const bool mlp_head = kind == TMDNET_HEAD_SPATIAL_EXTENT;
+  if (mlp_head) {  // EquivariantElectronicSpatialExtent: the Scalar MLP on out_norm's features (pre-activation in pre2)
+    gemm(s, b.xf, F, W.Ho1, F, W.hb1, b.pre2, F2, N, F2, F);
+    KR(CAT_ELEMENTWISE, Nd * F2 * 4, launch_head_energy(b.pre2, W.Ho2, W.hb2, N, F2, W.std, nullptr, z, b.ea, s, want_forces ? b.g_pre2 : nullptr));
+    KR(CAT_ELEMENTWISE, Nd * 32, launch_heads_reduce(g, heads, hbuf, s));
+  } else {
   gemm(s, b.vec[L], F, W.W1u, F, nullptr, b.u12, U, 3 * N, U, F);
   KR(CAT_ELEMENTWISE, Nd * Fd * 24, launch_et_cat_norm(b.xf, F, b.u12, U, F, N, b.hcat, s));
   gemm(s, b.hcat, 2 * F, W.Wm1, 2 * F, W.bm1, b.m1, F, N, F, 2 * F, GEMM_ACT_SILU, b.pre1, F);
@@ -585,7 +656,12 @@ int et_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, s
   gemm(s, b.vq, F2, W.W21, F2, nullptr, b.w1, F2, 3 * N, F2, F2);
   KR(CAT_ELEMENTWISE, Nd * Fd * 8, launch_et_cat_norm(nullptr, F2, b.w1, F2, F2, N, b.hcat2, s));
   gemm(s, b.hcat2, F, W.Wn1, F, W.bn1, b.m2, F2, N, F2, F, GEMM_ACT_SILU, b.pre2, F2);
-  if ((int64_t)N <= 256 * (int64_t)B) {
+  if (kind) {  // dipole / vector: block 2's vector output is kept (gate channel, vec2_proj), then the molecule moments
+    KR(CAT_ELEMENTWISE, Nd * Fd * 8, launch_et_vout(N, F2, b.pre2, W.Wn2, W.bn2, b.vq, W.W22, W.std, hbuf.gate, hbuf.vq2s, s));
+    if (kind == TMDNET_HEAD_DIPOLE_MOMENT)
+      KR(CAT_ELEMENTWISE, Nd * F2 * 4, launch_head_energy(b.pre2, W.Wn2, W.bn2, N, F2, W.std, nullptr, z, b.ea, s, want_forces ? b.g_pre2 : nullptr));
+    KR(CAT_ELEMENTWISE, Nd * 32, launch_heads_reduce(g, heads, hbuf, s));
+  } else if ((int64_t)N <= 256 * (int64_t)B) {
     KR(CAT_ELEMENTWISE, Nd * F2 * 4,
        launch_head_mol_sum(g, b.pre2, W.Wn2, W.bn2, N, B, F2, W.std, W.atomref, z, batch, W.mean, energy, s,
                            want_forces ? b.g_pre2 : nullptr));
@@ -593,6 +669,7 @@ int et_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, s
     KR(CAT_ELEMENTWISE, Nd * F2 * 4, launch_head_energy(b.pre2, W.Wn2, W.bn2, N, F2, W.std, W.atomref, z, b.ea, s, want_forces ? b.g_pre2 : nullptr));
     KR(CAT_ELEMENTWISE, Nd * 12, launch_mol_sum(g, b.ea, batch, N, B, W.mean, energy, s));
   }
+  }  // !mlp_head
 
   // ---------------- reverse (oracle/et_adjoint.py)
   if (want_forces) {
@@ -614,10 +691,18 @@ int et_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, s
       dW("Wn1", b.g_pre2, F2, b.hcat2, F, N, F2, F);
       dB("bn1", b.g_pre2, F2, N, F2);
     }
+    if (mlp_head) {  // seeds into g_ao (= g_pre2), then back through the MLP; the vector features get no gradient from this head
+      KR(CAT_ELEMENTWISE, Nd * (8 * F2 + 40), launch_heads_seed(heads, F2, b.g_pre2, hbuf.direct, s));
+      gemm(s, b.g_pre2, F2, W.Ho1T, F2, nullptr, b.g_xf, F, N, F, F2);
+      KR(CAT_ELEMENTWISE, Nd * Fd * 12, launch_fill(b.g_vec, 0.f, (int64_t)N * 3 * F, s));
+    } else {
+    if (kind)  // dipole / vector: seeds of the scalar and gate channels into g_pre2, of the vector output into gv
+      KR(CAT_ELEMENTWISE, Nd * (12 * F2 + 64), launch_et_heads_seed(heads, F2, b.pre2, W.Wn2, b.g_pre2, hbuf.gv, hbuf.direct, s));
     gemm(s, b.g_pre2, F2, W.Wn1T, F2, nullptr, b.g_h2, F, N, F, F2);                       // (g_xs | g_n2)
     KR(CAT_ELEMENTWISE, Nd * Fd * 12, launch_et_norm_bwd(b.g_h2 + F2, F, b.w1, F2, F2, N, b.g_w1, F2, s));
     if (tc) dW("W21", b.g_w1, F2, b.vq, F2, 3 * N, F2, F2);
     gemm(s, b.g_w1, F2, W.W21T, F2, nullptr, b.g_vq, F2, 3 * N, F2, F2);
+    if (kind) KR(CAT_ELEMENTWISE, Nd * Fd * 20, launch_et_gvq_add(N, F2, hbuf.gv, W.W22, b.g_vq, s));
     KR(CAT_ELEMENTWISE, Nd * Fd * 20,
        launch_et_head_mid_bwd(b.y, b.u12 + F, U, b.g_h2, b.g_vq, F2, N, b.g_y, b.g_u12 + F, U, s));
     if (tc) {
@@ -635,6 +720,7 @@ int et_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, s
     gemm(s, b.g_u12, U, W.W1uT, U, nullptr, b.g_vec, F, 3 * N, F, U);
     // LayerNorm adjoint of out_norm: its input gradient is the first F columns of g_h1 (row stride 2F) -> compact copy
     KR(CAT_ELEMENTWISE, Nd * Fd * 8, launch_et_copy2d(b.g_h1, 2 * F, b.g_xf, F, N, F, s));
+    }  // !mlp_head
     if (tc) {
       dB("lno_w", b.g_xf, F, N, F, b.xfh, F);
       dB("lno_b", b.g_xf, F, N, F);
@@ -707,7 +793,7 @@ int et_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, s
     } else {
       KR(CAT_PAIR, Pd * 48, launch_et_pair_combine(g, P, b.gd2, b.gr2, nwv * L, sstride, gd_emb, b.gd, b.g_rhat, s));
       KR(CAT_PAIR, Pd * 40, launch_geom_gd(g, P, b.gd, b.g_rhat, b.g_delta, s));
-      KR(CAT_PAIR, Ed * 12, launch_force_gather(g, N, b.g_delta, perm, forces, s));
+      KR(CAT_PAIR, Ed * 12, launch_force_gather(g, N, b.g_delta, perm, forces, s, kind ? hbuf.direct : nullptr));
     }
   }
   m->et->last = b;

@@ -241,6 +241,7 @@ int tmdnet_loss_param_grads(tmdnet_model* m, void* stream, void* graph_ws, void*
                             int64_t n_pairs, const int64_t* z, const int64_t* batch, const float* q, const float* v, const float* ge,
                             float* grads, float* hv) {
   if (!m || !graph_ws || !ws || !v || !grads) return TMDNET_ERR_INVALID;
+  if (m->head_kind) return fail(m, TMDNET_ERR_INVALID, "the property heads (tmdnet_set_output_head) have no second-order pass");
   if (ge && n_mol > 1 && !batch) return fail(m, TMDNET_ERR_INVALID, "an energy seed for several molecules needs batch");
   if (!m->finalized) return fail(m, TMDNET_ERR_STATE, "parameters not finalised");
   if (n_pairs < 0) return fail(m, TMDNET_ERR_INVALID, "the second-order pass needs the exact pair count (dynamic shapes)");

@@ -134,7 +134,9 @@ void launch_embed_gate_bwd(const float* G, const float* UX, const float* gates, 
 // contiguous range of the engine's order?)
 void launch_owned_range(const float* aw, const int* perm, int N, int* out, hipStream_t s);
 void launch_embed_bwd_atom(const float* g_u0_lin, const float* u0, const float* g_s0n, int N, int F, float* gA, hipStream_t s);
-void launch_force_gather(const Graph& g, int N, const float* g_delta, const int* perm, float* forces, hipStream_t s);
+// direct [N,3] (engine order, optional): a position gradient that does not go through the pairs (property heads), subtracted too
+void launch_force_gather(const Graph& g, int N, const float* g_delta, const int* perm, float* forces, hipStream_t s,
+                         const float* direct = nullptr);
 void launch_fill(float* p, float v, int64_t n, hipStream_t s);
 void launch_kappa(const float* q, const int64_t* batch, int N, int B, float* kap, hipStream_t s);
 

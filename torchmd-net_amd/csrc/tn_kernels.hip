@@ -1553,7 +1553,7 @@ void launch_embed_bwd_atom(const float* g_u0_lin, const float* u0, const float* 
 // F_i = - sum_{e in row(i)} sign(e) * g_delta[pair(e)]     (no atomics: CSR gather)
 // 16 lanes per atom stride over the row's edges; fixed-order shuffle tree (deterministic)
 __global__ __launch_bounds__(256) void k_force_gather(Graph g, int N, const float* __restrict__ g_delta, const int* __restrict__ perm,
-                                                      float* __restrict__ forces) {
+                                                      float* __restrict__ forces, const float* __restrict__ direct) {
   const int i = blockIdx.x * 16 + (threadIdx.x >> 4), sub = threadIdx.x & 15;
   const bool live = i < N && !g.counts[2];
   float fx = 0.f, fy = 0.f, fz = 0.f;
@@ -1575,15 +1575,21 @@ __global__ __launch_bounds__(256) void k_force_gather(Graph g, int N, const floa
     fz += __shfl_down(fz, off, 16);
   }
   if (live && sub == 0) {
+    if (direct) {  // engine order, like the row
+      fx -= direct[(int64_t)i * 3];
+      fy -= direct[(int64_t)i * 3 + 1];
+      fz -= direct[(int64_t)i * 3 + 2];
+    }
     const int o = perm ? perm[i] : i;  // cell-list path: back to the caller's atom order
     forces[o * 3] = fx;
     forces[o * 3 + 1] = fy;
     forces[o * 3 + 2] = fz;
   }
 }
-void launch_force_gather(const Graph& g, int N, const float* g_delta, const int* perm, float* forces, hipStream_t s) {
+void launch_force_gather(const Graph& g, int N, const float* g_delta, const int* perm, float* forces, hipStream_t s,
+                         const float* direct) {
   if (N <= 0) return;
-  hipLaunchKernelGGL(k_force_gather, dim3(cdiv(N, 16)), dim3(256), 0, s, g, N, g_delta, perm, forces);
+  hipLaunchKernelGGL(k_force_gather, dim3(cdiv(N, 16)), dim3(256), 0, s, g, N, g_delta, perm, forces, direct);
 }
 
 // per-atom charge factor kappa_n = 1 + 0.1 q[batch_n] (reference tensornet.py:789, 812); an out-of-range molecule index

@@ -40,6 +40,7 @@ struct DevParams {
   const float* atomref;
   const uint16_t* Wdp_sb;
   const float *Utab, *Vtab;  // per-type pair-embedding tables (k_ztables at finalize)
+  const float* mass;  // [TMDNET_MASS_TABLE_SIZE] atomic masses of the property heads (tmdnet_set_output_head), else null
   float mean, std;
 };
 
@@ -161,6 +162,7 @@ struct tmdnet_model {
   bool graph_no_ghost_pairs = false;  // the last graph was built with the exchange set: no pairs of two ghosts in it
   int halo_active[2] = {0, 0};      // [first row, rows] the per-atom kernels of the last step ran on ("halo_active_rows")
   tmdnet_hparams hp;
+  int head_kind = 0;  // tmdnet_set_output_head: 0 scalar, 1 dipole moment, 2 electronic spatial extent (tn_heads.hip)
   TrainCtx* train = nullptr;  // non-null while tmdnet_energy_param_grads drives tmdnet_energy_forces
   std::vector<std::pair<std::string, int64_t>> train_entries;  // gradient buffer layout (name, numel), built on first use
   // optional (TMDNET_SIDE_STREAM=1) second stream + events: the edge MLPs of the interaction layers depend on the pair geometry only, so they are
@@ -320,6 +322,7 @@ int tn2_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, 
 
 // Equivariant Transformer (tn_et_api.hip)
 int et_create(tmdnet_model* m, const tmdnet_et_hparams* hp);
+void et_head_specs(tmdnet_model* m);  // the parameter list for m->head_kind (tmdnet_set_output_head)
 void et_destroy(tmdnet_model* m);
 int et_finalize(tmdnet_model* m);
 int et_forward_workspace_bytes(const tmdnet_model* m, int64_t n_atoms, int64_t n_mol, int64_t n_pairs, int32_t want_forces, size_t* bytes);

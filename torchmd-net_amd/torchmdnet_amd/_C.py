@@ -13,6 +13,8 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libtmdnet_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "tmdnet_amd.h")
 
 OK, ERR_INVALID, ERR_HIP, ERR_OVERFLOW, ERR_WORKSPACE, ERR_STATE = 0, 1, 2, 3, 4, 5
+# output heads of tmdnet_set_output_head
+HEAD_SCALAR, HEAD_DIPOLE_MOMENT, HEAD_SPATIAL_EXTENT, HEAD_VECTOR = 0, 1, 2, 3
 
 
 class HParams(C.Structure):
@@ -57,6 +59,10 @@ def lib():
             "torchmdnet_amd has no CPU or eager-PyTorch fallback."
         )
     L = C.CDLL(LIB_PATH)
+    # the ABI revision first: binding the argtypes of a symbol that a stale library lacks would end in a bare AttributeError
+    abi = int(re.search(r"#define\s+TMDNET_ABI_VERSION\s+(\d+)", open(HEADER_PATH).read()).group(1))
+    if L.tmdnet_abi_version() != abi:
+        raise ImportError(f"{LIB_PATH} has ABI revision {L.tmdnet_abi_version()}, include/tmdnet_amd.h declares {abi}: rebuild")
     vp, i64, i32, f32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
     L.tmdnet_create.argtypes = [C.POINTER(HParams), C.POINTER(vp)]
     L.tmdnet_create_et.argtypes = [C.POINTER(EtHParams), C.POINTER(vp)]
@@ -109,9 +115,7 @@ def lib():
     L.tmdnet_force_param_grads.argtypes = [vp, vp, vp, vp, sz, i64, i64, i64, vp, vp, vp, vp, vp, vp]
     L.tmdnet_loss_param_grads.argtypes = [vp, vp, vp, vp, sz, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
     L.tmdnet_hvp_debug_tensor.argtypes = [vp, vp, C.c_char_p, vp, i64]
-    abi = int(re.search(r"#define\s+TMDNET_ABI_VERSION\s+(\d+)", open(HEADER_PATH).read()).group(1))
-    if L.tmdnet_abi_version() != abi:
-        raise ImportError(f"{LIB_PATH} has ABI revision {L.tmdnet_abi_version()}, include/tmdnet_amd.h declares {abi}: rebuild")
+    L.tmdnet_set_output_head.argtypes = [vp, i32]
     for name in declared_symbols():
         fn = getattr(L, name)
         if fn.restype is C.c_int:

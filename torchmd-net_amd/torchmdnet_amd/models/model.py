@@ -47,6 +47,13 @@ def create_model(args, prior_model=None, mean=None, std=None):
     return model
 
 
+# property heads (csrc/tn_heads.hip): head class -> engine head kind (tmdnet_set_output_head)
+_PROPERTY_HEADS = {"DipoleMoment": _C.HEAD_DIPOLE_MOMENT, "ElectronicSpatialExtent": _C.HEAD_SPATIAL_EXTENT,
+                   "EquivariantDipoleMoment": _C.HEAD_DIPOLE_MOMENT, "EquivariantElectronicSpatialExtent": _C.HEAD_SPATIAL_EXTENT,
+                   "EquivariantVectorOutput": _C.HEAD_VECTOR}
+_PROPERTY_ARGS = ("DipoleMoment", "ElectronicSpatialExtent", "VectorOutput")  # the `output_model` values that name them
+
+
 def _create_model(args, prior_model=None, mean=None, std=None):
     """Supported on the HIP path: model in {"tensornet", "tensornet2", "equivariant-transformer"}, precision 32,
     prior_model in {None, Atomref}."""
@@ -132,6 +139,16 @@ def _create_model(args, prior_model=None, mean=None, std=None):
                            derivative=args["derivative"], dtype=dtype)
     if args["model"] == "tensornet2":
         raise NotImplementedError("TensorNet2 has a HIP path with output_model: ScalarPlusWeightedCoulomb only")
+    if args["output_model"] in _PROPERTY_ARGS:
+        # reference model.py:134: the Equivariant Transformer takes the "Equivariant" variant of every head
+        name = ("Equivariant" if is_equivariant else "") + args["output_model"]
+        if name not in _PROPERTY_HEADS:
+            raise NotImplementedError(f"output_model {name} has no HIP path (property heads: {', '.join(_PROPERTY_HEADS)})")
+        output_model = getattr(output_modules, name)(
+            args["embedding_dimension"], activation=args["activation"], reduce_op=args["reduce_op"], dtype=dtype,
+            static_shapes=args.get("static_shapes", False), num_hidden_layers=args.get("output_mlp_num_layers", 0), num_layers=0)
+        return TorchMD_Net(representation_model, output_model, prior_model=prior_model, mean=mean, std=std,
+                           derivative=args["derivative"], dtype=dtype)
     if args["output_model"] not in ("Scalar", "EquivariantScalar"):
         raise NotImplementedError(f'output_model {args["output_model"]} has no HIP path (Scalar, ScalarPlusWeightedCoulomb)')
     if is_equivariant:  # reference model.py:134-135: "Scalar" on an equivariant model is EquivariantScalar
@@ -524,6 +541,10 @@ class TorchMD_Net(nn.Module):
         hp.cutoff_upper = float(rm.cutoff_upper)
         return hp
 
+    def _head_kind(self) -> int:
+        """Engine output head: scalar energies, or one of the property heads (tmdnet_set_output_head)."""
+        return _PROPERTY_HEADS.get(type(self.output_model).__name__, _C.HEAD_SCALAR)
+
     def _is_et(self) -> bool:
         return type(self.representation_model).__name__ == "TorchMD_ET"
 
@@ -633,7 +654,7 @@ class TorchMD_Net(nn.Module):
                 return self._sync_engine()
         L = _C.lib()
         hp = self._et_hparams() if self._is_et() else (self._tn2_hparams() if self._is_tn2() else self._hparams())
-        hp_key = (type(hp).__name__, bytes(hp))
+        hp_key = (type(hp).__name__, bytes(hp), self._head_kind())
         st.generation += 1  # captured replays of the previous weights are stale either way
         if st.handle is None or getattr(st, "hp_key", None) != hp_key:
             st.release()
@@ -642,6 +663,10 @@ class TorchMD_Net(nn.Module):
             rc = create(C.byref(hp), C.byref(handle))
             if rc != _C.OK:
                 raise RuntimeError(f"tmdnet_create failed with code {rc}")
+            if self._head_kind() != _C.HEAD_SCALAR and L.tmdnet_set_output_head(handle, self._head_kind()) != _C.OK:
+                msg = L.tmdnet_last_error(handle).decode()
+                L.tmdnet_destroy(handle)
+                raise NotImplementedError(msg)
             st.handle, st.hp_key = handle, hp_key
         # else: same architecture, new weights (training loop): the handle and its device buffers are kept, the parameters
         # are re-uploaded below (hipFree / hipMalloc per step would each be a device-wide synchronisation)
@@ -1011,6 +1036,20 @@ class TorchMD_Net(nn.Module):
         if t.dtype not in dtypes:
             raise TypeError(f"torchmdnet_amd: `{name}` must have dtype {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
 
+    def _check_mass_index(self, z):
+        """The reference's atomic_mass[z] raises IndexError for z >= len(atomic_mass); the graph phase checks z < max_z only.  Read
+        back once per `z` tensor and version (an MD loop keeps its `z`: no synchronisation per step), never during a capture."""
+        mass = getattr(self.output_model, "atomic_mass", None)
+        if mass is None or mass.numel() >= self.representation_model.max_z or not z.numel():
+            return
+        key = (z.data_ptr(), z._version, tuple(z.shape))
+        if getattr(self._engine, "mass_checked", None) == key or torch.cuda.is_current_stream_capturing():
+            return
+        zmax = int(z.max())
+        if zmax >= mass.numel():
+            raise IndexError(f"index {zmax} is out of bounds for the atomic mass table of size {mass.numel()}")
+        self._engine.mass_checked = key
+
     def energy_and_forces(self, z, pos, batch, box, q, n_mol, want_forces=True, atom_weights=None,
                           halo_exchange=None, cell_grid=None) -> Tuple[Tensor, Optional[Tensor]]:
         """Raw engine call: returns (E [n_mol], F [N,3] or None), both fp32 on ``pos.device``.  ``atom_weights`` ([N] fp32, this
@@ -1030,6 +1069,11 @@ class TorchMD_Net(nn.Module):
         self._check_input(batch, "batch", dev, (torch.long, torch.int32))
         if z.shape[0] != pos.shape[0] or batch.shape[0] != pos.shape[0]:
             raise ValueError(f"z [{z.shape[0]}], pos [{pos.shape[0]}] and batch [{batch.shape[0]}] must have one entry per atom")
+        if self._head_kind() != _C.HEAD_SCALAR:
+            if atom_weights is not None or halo_exchange is not None:
+                raise NotImplementedError(f"{type(self.output_model).__name__}: atom weights and the halo exchange have no HIP path "
+                                          "with a property head")
+            self._check_mass_index(z)
         with torch.cuda.device(dev):
             st = self._sync_engine()
             stream = _stream_ptr(dev)
@@ -1117,7 +1161,9 @@ class TorchMD_Net(nn.Module):
                     raise RuntimeError(f"tmdnet_build_graph: {L.tmdnet_last_error(st.handle).decode()} (code {rc})")
                 L.tmdnet_forward_workspace_bytes(st.handle, n, n_mol, n_pairs, n_edges, int(want_forces), C.byref(nbytes))
                 st.fwd_ws = self._grow(st.fwd_ws, nbytes.value, dev)
-                energy = torch.empty(n_mol, dtype=torch.float32, device=dev)
+                # the vector output (EquivariantVectorOutput) has three components per molecule
+                shape = (n_mol, 3) if self._head_kind() == _C.HEAD_VECTOR else (n_mol,)
+                energy = torch.empty(shape, dtype=torch.float32, device=dev)
                 forces = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_forces else None
                 st.ws_epoch = getattr(st, "ws_epoch", 0) + 1  # the workspaces of a pending parameter-gradient pass are gone
                 rc = L.tmdnet_energy_forces(st.handle, stream, _ptr(st.graph_ws), _ptr(st.fwd_ws), st.fwd_ws.numel(), n, n_mol,
@@ -1183,7 +1229,7 @@ class TorchMD_Net(nn.Module):
     def capture(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
                 q: Optional[Tensor] = None, num_systems: Optional[int] = None, warmup: int = 3):
         """Capture one energy+force evaluation into a HIP graph (needs ``static_shapes=True``).
-        Returns ``replay(pos) -> (energy [B,1], forces [N,3])`` writing into static buffers - the reference gets
+        Returns ``replay(pos) -> (energy [B,1] ([B,3]: vector output), forces [N,3])`` writing into static buffers - the reference gets
         the same effect with torch.cuda.graphs around its model (calculators.py:117-128)."""
         if not getattr(self.representation_model, "static_shapes", False):
             raise RuntimeError("capture() needs a model created with static_shapes=True")
@@ -1224,7 +1270,7 @@ class TorchMD_Net(nn.Module):
                 # costs ~3x a small kernel between two graph launches.  Integrators that can write in place use replay.pos.
                 torch.mul(new_pos.detach(), 1.0, out=s_pos)
             graph.replay()
-            return s_e.view(-1, 1), s_f
+            return (s_e.view(-1, 3) if s_e.dim() == 2 else s_e.view(-1, 1)), s_f
 
         replay.graph = graph
         replay.inputs = (z, batch, box, q)  # what the graph reads, kept alive for as long as it can be replayed
@@ -1287,6 +1333,9 @@ class TorchMD_Net(nn.Module):
         want_forces = bool(self.derivative or (pos.requires_grad and torch.is_grad_enabled()))
         _require_cuda(pos, "TorchMD_Net.forward")
         if self.parameter_gradients and torch.is_grad_enabled():
+            if self._head_kind() != _C.HEAD_SCALAR:
+                raise NotImplementedError(f"parameter_gradients with output_model {type(self.output_model).__name__} has no HIP path "
+                                          "(the property heads evaluate values and forces only)")
             params = [p for p in self.parameters() if p.requires_grad]
             if want_forces:  # force matching: forces carry a (finite-difference) graph to the parameters as well
                 energy, forces = _EnergyForceParamGrad.apply(self, z, pos, batch, box, q, n_mol, *params)
@@ -1298,7 +1347,7 @@ class TorchMD_Net(nn.Module):
         # through it, and `energy.backward()` (ASE calculator, OpenMM wrapper: reference calculators.py:311-316) gets
         # d(sum_m g_m E_m)/d pos_i = -g_{batch_i} F_i from its registered backward
         energy, forces = torch.ops.tmdnet.energy_forces(z, pos, batch, box, q, self._engine.op_key, n_mol, want_forces)
-        y = energy.view(-1, 1)
+        y = energy.view(-1, 3) if energy.dim() == 2 else energy.view(-1, 1)  # [B,1], or [B,3] for the vector output
         if self.derivative:
             return y, forces.detach()
         # an empty tensor keeps the reference's "always two tensors" contract (model.py:629-631)

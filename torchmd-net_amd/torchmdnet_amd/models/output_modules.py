@@ -1,15 +1,14 @@
-"""Output heads (reference torchmdnet/models/output_modules.py).  Only ``Scalar`` is on the energy+force
-path; it is a parameter container here, the MLP and the per-molecule reduction run in the HIP library."""
+"""Output heads (reference torchmdnet/models/output_modules.py).  Parameter containers with the reference's state-dict keys and
+initialisation order; the MLPs, the per-molecule reductions and the property heads' molecule moments run in the HIP library."""
 import torch
 from torch import nn
 
 from torchmdnet_amd.models.utils import MLP
 
-# the reference's own list (output_modules.py:19), which its tests parametrise over: of these only "Scalar" is in SURVEY section 8's
-# scope - the two property heads are defined below as classes that raise NotImplementedError on construction, so that
-# `from ...output_modules import *` works and create_model refuses them by name.  What the engine evaluates: __engine_heads__
+# the reference's own list (output_modules.py:19), which its tests parametrise over.  What the engine evaluates: __engine_heads__
 __all__ = ["Scalar", "DipoleMoment", "ElectronicSpatialExtent"]
-__engine_heads__ = ["Scalar", "EquivariantScalar", "ScalarPlusWeightedCoulomb"]
+__engine_heads__ = ["Scalar", "EquivariantScalar", "ScalarPlusWeightedCoulomb", "DipoleMoment", "ElectronicSpatialExtent",
+                    "EquivariantDipoleMoment", "EquivariantElectronicSpatialExtent", "EquivariantVectorOutput"]
 
 
 class OutputModel(nn.Module):
@@ -127,17 +126,59 @@ class ScalarPlusWeightedCoulomb(OutputModel):
         self.output_network.reset_parameters()
 
 
-class _OutOfScopeHead(OutputModel):
-    """Property heads of the reference (output_modules.py:166-341) outside SURVEY section 8's energy + force path."""
+def _mass_buffer(dtype):
+    from torchmdnet_amd.atomic_masses import atomic_masses
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError(f"output_model={type(self).__name__} is outside the HIP energy+force path (Scalar, EquivariantScalar, "
-                                  "ScalarPlusWeightedCoulomb)")
+    return torch.from_numpy(atomic_masses).to(dtype)
 
 
-class DipoleMoment(_OutOfScopeHead):
-    pass
+class DipoleMoment(Scalar):
+    """|| sum_i q_i (r_i - c) + mean || per molecule (output_modules.py:166-208): the Scalar MLP per atom, centre of mass c from the
+    ``atomic_mass`` buffer.  The molecule moments and their reverse seeds run in the HIP library (csrc/tn_heads.hip)."""
+
+    def __init__(self, hidden_channels, activation="silu", reduce_op="sum", dtype=torch.float, static_shapes=False, **kwargs):
+        super().__init__(hidden_channels, activation, allow_prior_model=False, reduce_op=reduce_op, dtype=dtype,
+                         static_shapes=static_shapes, **kwargs)
+        self.register_buffer("atomic_mass", _mass_buffer(dtype))
 
 
-class ElectronicSpatialExtent(_OutOfScopeHead):
-    pass
+class EquivariantDipoleMoment(EquivariantScalar):
+    """|| sum_i (q_i (r_i - c) + v_i) + mean || per molecule (output_modules.py:211-245): the two gated blocks with block 2's vector
+    output v_i kept; evaluated by the HIP library (csrc/tn_heads.hip, csrc/tn_et_api.hip)."""
+
+    def __init__(self, hidden_channels, activation="silu", reduce_op="sum", dtype=torch.float, static_shapes=False, **kwargs):
+        super().__init__(hidden_channels, activation, allow_prior_model=False, reduce_op=reduce_op, dtype=dtype,
+                         static_shapes=static_shapes, **kwargs)
+        self.register_buffer("atomic_mass", _mass_buffer(dtype))
+
+
+class ElectronicSpatialExtent(OutputModel):
+    """sum_i q_i ||r_i - c||^2 + mean per molecule (output_modules.py:248-293): the Scalar MLP per atom, centre of mass c from the
+    ``atomic_mass`` buffer; evaluated by the HIP library (csrc/tn_heads.hip)."""
+
+    def __init__(self, hidden_channels, activation="silu", reduce_op="sum", dtype=torch.float, static_shapes=False, **kwargs):
+        super().__init__(allow_prior_model=False, reduce_op=reduce_op, static_shapes=static_shapes)
+        if kwargs.get("num_layers", 0) != 0:
+            raise NotImplementedError("ElectronicSpatialExtent head with extra hidden layers has no HIP kernel yet")
+        if reduce_op not in ("sum", "add"):
+            raise NotImplementedError(f"reduce_op={reduce_op} has no HIP kernel (sum/add only)")
+        self.output_network = MLP(in_channels=hidden_channels, out_channels=1, hidden_channels=hidden_channels // 2,
+                                  activation=activation, num_hidden_layers=kwargs.get("num_layers", 0), dtype=dtype)
+        self.register_buffer("atomic_mass", _mass_buffer(dtype))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.output_network.reset_parameters()
+
+
+class EquivariantElectronicSpatialExtent(ElectronicSpatialExtent):
+    """The reference's EquivariantElectronicSpatialExtent (output_modules.py:296-297): the Scalar MLP on the Equivariant Transformer's
+    out_norm features, no gated blocks."""
+
+
+class EquivariantVectorOutput(EquivariantScalar):
+    """sum_i v_i + mean per molecule, [B,3] (output_modules.py:300-323): the vector output of the second gated block."""
+
+    def __init__(self, hidden_channels, activation="silu", reduce_op="sum", dtype=torch.float, static_shapes=False, **kwargs):
+        super().__init__(hidden_channels, activation, allow_prior_model=False, reduce_op="sum", dtype=dtype,
+                         static_shapes=static_shapes, **kwargs)

@@ -8,6 +8,7 @@ evaluation is ONE library call - so two ops are registered:
 
   tmdnet::energy_forces(z, pos, batch, box?, q?, engine, n_mol, want_forces) -> (energy [n_mol], forces [N,3] or [0,3])
       autograd: d(sum_m g_m E_m)/d pos_i = -g_{batch_i} F_i  (molecules are independent); no second derivatives
+      (EquivariantVectorOutput: energy [n_mol, 3]; the backward takes a gradient equal across the three components)
   tmdnet::neighbor_pairs(pos, batch, box?, cutoff_lower, cutoff_upper, max_num_pairs, loop, include_transpose, strategy)
       -> (neighbors [2,M] int64, deltas [M,3], distances [M], num_pairs [1] int32)      (reference op: same outputs)
       float32 or float64 positions, like the reference's (tmdnet_neighbor_pairs / tmdnet_neighbor_pairs_f64)
@@ -58,7 +59,9 @@ def energy_forces(z: Tensor, pos: Tensor, batch: Tensor, box: Optional[Tensor], 
 @energy_forces.register_fake
 def _(z, pos, batch, box, q, engine, n_mol, want_forces):
     n = pos.shape[0] if want_forces else 0
-    return pos.new_empty((n_mol,), dtype=torch.float32), pos.new_empty((n, 3), dtype=torch.float32)
+    module = _ENGINES.get(engine)
+    vector = module is not None and module._head_kind() == _C.HEAD_VECTOR  # EquivariantVectorOutput: [n_mol, 3]
+    return pos.new_empty((n_mol, 3) if vector else (n_mol,), dtype=torch.float32), pos.new_empty((n, 3), dtype=torch.float32)
 
 
 def _ef_setup(ctx, inputs, output):
@@ -74,6 +77,13 @@ def _ef_backward(ctx, g_energy, g_forces):
         raise RuntimeError("tmdnet::energy_forces was evaluated with want_forces=False: no position gradient is available")
     g_pos = None
     if g_energy is not None:
+        if g_energy.dim() == 2:
+            # vector output [n_mol, 3]: the forces are - d (sum of the three components) / d pos, so only a gradient that is the same
+            # for the three components of a molecule maps onto them; any other one would need a pass per component
+            if not torch.equal(g_energy, g_energy[:, :1].expand_as(g_energy)):
+                raise NotImplementedError("tmdnet::energy_forces: the vector output's backward takes a gradient equal across the three "
+                                          "components of each molecule (e.g. y.sum().backward())")
+            g_energy = g_energy[:, 0]
         g_pos = -forces * g_energy.reshape(-1)[batch.to(torch.long)].unsqueeze(-1)
     # g_forces (second derivatives, force-matching training) is not implemented on the HIP path
     return None, g_pos, None, None, None, None, None, None
