@@ -261,6 +261,28 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
                          int64_t n_mol, int64_t n_pairs, const int64_t* z, const int64_t* batch, const float* q,
                          int32_t want_forces, float* energy, float* forces);
 
+/* The same call that also returns the virial of every molecule (TensorNet and Equivariant Transformer handles, scalar head; the
+ * reference has no counterpart).  Definition, with row vectors: under the homogeneous strain pos -> pos (I + eps), box -> box (I + eps),
+ * one eps[3,3] per molecule,
+ *     W_m[a][b] = - d E_m / d eps_ab |_(eps = 0) = - sum over the pairs p of molecule m of  delta_p[a] * (d E / d delta_p)[b]
+ * with delta_p = pos_i - pos_j (+ minimum image) as the graph phase stored it: the box scales with the positions, so every pair keeps
+ * its image and the pair form is exact.  Self pairs contribute nothing; mean, std and atomref enter as they enter the forces.  Sign:
+ * W is MINUS the strain derivative (for a pair potential, W = sum_p delta_p (x) f_p with f_p the force on the pair's i end), and the
+ * stress of molecule m in a cell of volume V_m = |det box_m| is  sigma_m = - W_m / V_m.  `virial` is device memory, [n_mol][9],
+ * row-major a * 3 + b, the full tensor: it is NOT symmetrised (it is symmetric up to rounding because the energy is rotation
+ * invariant; the tests check that).  A molecule index without atoms gets zeros.
+ * Arguments as tmdnet_energy_forces (want_forces is accepted for symmetry and ignored: the virial is a by-product of the force pass,
+ * the call behaves as if it were 1; `forces` is required) plus the scratch `virial_ws` of tmdnet_virial_workspace_bytes(n_atoms, n_mol)
+ * bytes (device; 36 bytes per atom plus the slice sums of large molecules).  `energy` and `forces` are bit-identical to those
+ * tmdnet_energy_forces writes for the same inputs; the virial is reduced in a fixed order without atomics (bit-identical repeats).
+ * Enqueues only: no allocation, no synchronisation, capturable (static mode: skipped on overflow like the rest of the step).
+ * TMDNET_ERR_INVALID for a TensorNet2 handle (its Coulomb forces do not come from the per-pair gradient), a property head
+ * (tmdnet_set_output_head), atom weights or a halo exchange set, or inside the parameter-gradient / second-order passes. */
+int tmdnet_virial_workspace_bytes(const tmdnet_model* m, int64_t n_atoms, int64_t n_mol, size_t* bytes);
+int tmdnet_energy_forces_virial(tmdnet_model* m, void* stream, void* graph_ws, void* ws, size_t ws_bytes, void* virial_ws,
+                                size_t virial_ws_bytes, int64_t n_atoms, int64_t n_mol, int64_t n_pairs, const int64_t* z,
+                                const int64_t* batch, const float* q, int32_t want_forces, float* energy, float* forces, float* virial);
+
 /* ---- fine-grained operator: the reference's neighbour op --------------------------------------
  * Same outputs as torch.ops.torchmdnet.warp_neighbor_brute_fwd (warp_ops/neighbors.py:34-148):
  * neighbors int64 [2,max_num_pairs] padded with -1, deltas [max_num_pairs,3], distances

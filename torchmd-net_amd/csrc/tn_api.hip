@@ -22,6 +22,7 @@
 #include "tn_tlin9.h"
 #include "tn_small.h"
 #include "tn_interp.h"
+#include "tn_virial.h"
 
 using namespace tn;
 
@@ -1719,7 +1720,10 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
     KR(CAT_PAIR, Pd * (24 * Fd + 24) + Nd * 10 * Fd * 4,
        launch_embed_pair_gd(g, P, F, z, W.Utab, W.Vtab, b.Q, b.dQ, b.C, b.dC, b.gA, b.gd, b.g_rhat, s, b.g_delta, b.gd_slots, L * gd_nw,
                             gd_stride));
-    KR(CAT_ELEMENTWISE, E_ * 8 + Nd * 12, launch_force_gather(g, N, b.g_delta, perm, forces, s));
+    if (m->virial_out)
+      KR(CAT_ELEMENTWISE, E_ * 8 + Nd * 84 + Pd * 12, launch_force_virial(g, N, B, b.g_delta, perm, batch, forces, m->virial_out, m->virial_ws, s));
+    else
+      KR(CAT_ELEMENTWISE, E_ * 8 + Nd * 12, launch_force_gather(g, N, b.g_delta, perm, forces, s));
   } else if (want_forces && run_bwd) {
     NODE();  // g_ao = d energy / d ao came out of the head kernel
     const RowMap rH = rows_plain(H), rF = rows_plain(F), r2F = rows_plain(2 * F), r3F = rows_plain(3 * F), rK = rows_plain(K);
@@ -1875,7 +1879,10 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
          launch_embed_pair_gd(g, P, F, z, W.Utab, W.Vtab, b.Q, b.dQ, b.C, b.dC, b.gA, b.gd, b.g_rhat, s, merged_gd ? b.g_delta : nullptr,
                               b.gd_slots, L * gd_nw, gd_stride));
     if (!merged_gd && !tc) KR(CAT_ELEMENTWISE, Pd * 40, launch_geom_gd(g, P, b.gd, b.g_rhat, b.g_delta, s, nullptr, 0, gd_stride));
-    if (!tc) KR(CAT_ELEMENTWISE, E_ * 8 + Nd * 12, launch_force_gather(g, N, b.g_delta, perm, forces, s, m->head_kind ? hbuf.direct : nullptr));
+    if (!tc && m->virial_out)  // scalar head, no TrainCtx (tmdnet_energy_forces_virial refuses the rest)
+      KR(CAT_ELEMENTWISE, E_ * 8 + Nd * 84 + Pd * 12, launch_force_virial(g, N, B, b.g_delta, perm, batch, forces, m->virial_out, m->virial_ws, s));
+    else if (!tc)
+      KR(CAT_ELEMENTWISE, E_ * 8 + Nd * 12, launch_force_gather(g, N, b.g_delta, perm, forces, s, m->head_kind ? hbuf.direct : nullptr));
   }
   NODE();
   HIP_TRY(m, hipGetLastError());

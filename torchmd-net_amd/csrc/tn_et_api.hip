@@ -14,6 +14,7 @@
 #include "tn_et.h"
 #include "tn_heads.h"
 #include "tn_model.h"
+#include "tn_virial.h"
 
 namespace {
 
@@ -793,7 +794,10 @@ int et_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, s
     } else {
       KR(CAT_PAIR, Pd * 48, launch_et_pair_combine(g, P, b.gd2, b.gr2, nwv * L, sstride, gd_emb, b.gd, b.g_rhat, s));
       KR(CAT_PAIR, Pd * 40, launch_geom_gd(g, P, b.gd, b.g_rhat, b.g_delta, s));
-      KR(CAT_PAIR, Ed * 12, launch_force_gather(g, N, b.g_delta, perm, forces, s, kind ? hbuf.direct : nullptr));
+      if (m->virial_out)  // scalar head (tmdnet_energy_forces_virial refuses the property heads)
+        KR(CAT_PAIR, Ed * 12 + Nd * 72 + Pd * 12, launch_force_virial(g, N, B, b.g_delta, perm, batch, forces, m->virial_out, m->virial_ws, s));
+      else
+        KR(CAT_PAIR, Ed * 12, launch_force_gather(g, N, b.g_delta, perm, forces, s, kind ? hbuf.direct : nullptr));
     }
   }
   m->et->last = b;

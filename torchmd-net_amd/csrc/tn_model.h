@@ -164,6 +164,9 @@ struct tmdnet_model {
   tmdnet_hparams hp;
   int head_kind = 0;  // tmdnet_set_output_head: 0 scalar, 1 dipole moment, 2 electronic spatial extent (tn_heads.hip)
   TrainCtx* train = nullptr;  // non-null while tmdnet_energy_param_grads drives tmdnet_energy_forces
+  // non-null while tmdnet_energy_forces_virial drives tmdnet_energy_forces: the force gather also writes the virial (tn_virial.hip)
+  float* virial_out = nullptr;  // [n_mol, 9] (device, the caller's)
+  void* virial_ws = nullptr;    // the caller's scratch (tmdnet_virial_workspace_bytes)
   std::vector<std::pair<std::string, int64_t>> train_entries;  // gradient buffer layout (name, numel), built on first use
   // optional (TMDNET_SIDE_STREAM=1) second stream + events: the edge MLPs of the interaction layers depend on the pair geometry only, so they are
   // enqueued on `side` (fork after the radial kernel, one join per layer before its message sweep) and run beside the

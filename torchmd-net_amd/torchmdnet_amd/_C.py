@@ -89,6 +89,8 @@ def lib():
     L.tmdnet_graph_cell_grid.argtypes = [vp, vp, vp, i64, i64, C.POINTER(i64)]
     L.tmdnet_forward_workspace_bytes.argtypes = [vp, i64, i64, i64, i64, i32, C.POINTER(sz)]
     L.tmdnet_energy_forces.argtypes = [vp, vp, vp, vp, sz, i64, i64, i64, vp, vp, vp, i32, vp, vp]
+    L.tmdnet_virial_workspace_bytes.argtypes = [vp, i64, i64, C.POINTER(sz)]
+    L.tmdnet_energy_forces_virial.argtypes = [vp, vp, vp, vp, sz, vp, sz, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp]
     L.tmdnet_neighbor_workspace_bytes.argtypes = [i64, i64, i64, C.POINTER(sz)]
     L.tmdnet_neighbor_pairs.argtypes = [vp, vp, sz, i64, i64, vp, vp, vp, i32, f32, f32, i64, i32, i32, i32, vp, vp, vp, vp]
     L.tmdnet_neighbor_grad.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, vp]

@@ -296,6 +296,7 @@ class _EngineState:
         self.tensors = None
         self.graph_ws = None
         self.fwd_ws = None
+        self.virial_ws = None  # scratch of tmdnet_energy_forces_virial
         self.counts = None
         self.op_key = None   # key of the owning module in torchmdnet_amd.ops' registry (custom-op calls carry it)
         self.generation = 0  # bumped whenever the handle or a workspace is re-created: captured graphs of older generations are stale
@@ -1051,14 +1052,17 @@ class TorchMD_Net(nn.Module):
         self._engine.mass_checked = key
 
     def energy_and_forces(self, z, pos, batch, box, q, n_mol, want_forces=True, atom_weights=None,
-                          halo_exchange=None, cell_grid=None) -> Tuple[Tensor, Optional[Tensor]]:
+                          halo_exchange=None, cell_grid=None, want_virial=False):
         """Raw engine call: returns (E [n_mol], F [N,3] or None), both fp32 on ``pos.device``.  ``atom_weights`` ([N] fp32, this
         framework's extension for domain decomposition, parallel.SpatialEvaluator): E_mol = sum_i w_i e_i + mean and F = -dE/dpos
         of that sum (TensorNet only).  ``halo_exchange(stage, rows, inv)`` (parallel.HaloExchangeEvaluator, TensorNet only) is
         called 2 L + 1 times inside the step (``tmdnet_set_halo_exchange``, include/tmdnet_amd.h): it overwrites the ghost rows of
         ``rows`` [N, row_floats] (a view of the engine's workspace) with their owners' values on the current stream; the row of
         the caller's atom i is ``rows[i]`` when ``inv`` is None and ``rows[inv[i]]`` otherwise (cell order).  ``cell_grid``
-        (n_x, n_y, n_z) fixes the neighbour search's grid (``tmdnet_set_cell_grid``; default: from the box on the device)."""
+        (n_x, n_y, n_z) fixes the neighbour search's grid (``tmdnet_set_cell_grid``; default: from the box on the device).
+        ``want_virial=True`` (TensorNet and Equivariant Transformer, scalar head) returns a third element W [n_mol,3,3], the virial
+        W_m[a][b] = -dE_m/d eps_ab under pos -> pos (I + eps), box -> box (I + eps) (``tmdnet_energy_forces_virial``); E and F are
+        bit-identical to the two-element call."""
         _require_cuda(pos, "TorchMD_Net.forward")
         L = _C.lib()
         dev = pos.device
@@ -1069,6 +1073,9 @@ class TorchMD_Net(nn.Module):
         self._check_input(batch, "batch", dev, (torch.long, torch.int32))
         if z.shape[0] != pos.shape[0] or batch.shape[0] != pos.shape[0]:
             raise ValueError(f"z [{z.shape[0]}], pos [{pos.shape[0]}] and batch [{batch.shape[0]}] must have one entry per atom")
+        if want_virial:
+            self._refuse_virial(atom_weights, halo_exchange)
+            want_forces = True  # the virial is a by-product of the force pass
         if self._head_kind() != _C.HEAD_SCALAR:
             if atom_weights is not None or halo_exchange is not None:
                 raise NotImplementedError(f"{type(self.output_model).__name__}: atom weights and the halo exchange have no HIP path "
@@ -1166,8 +1173,18 @@ class TorchMD_Net(nn.Module):
                 energy = torch.empty(shape, dtype=torch.float32, device=dev)
                 forces = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_forces else None
                 st.ws_epoch = getattr(st, "ws_epoch", 0) + 1  # the workspaces of a pending parameter-gradient pass are gone
-                rc = L.tmdnet_energy_forces(st.handle, stream, _ptr(st.graph_ws), _ptr(st.fwd_ws), st.fwd_ws.numel(), n, n_mol,
-                                            n_pairs, _ptr(z), _ptr(batch), _ptr(q), int(want_forces), _ptr(energy), _ptr(forces))
+                if want_virial:
+                    L.tmdnet_virial_workspace_bytes(st.handle, n, n_mol, C.byref(nbytes))
+                    if st.virial_ws is None:  # the first one: no captured graph can hold its address, the generation stays
+                        st.virial_ws = torch.empty(max(int(nbytes.value * 1.1), 256), dtype=torch.uint8, device=dev)
+                    st.virial_ws = self._grow(st.virial_ws, nbytes.value, dev)
+                    virial = torch.empty((n_mol, 3, 3), dtype=torch.float32, device=dev)
+                    rc = L.tmdnet_energy_forces_virial(st.handle, stream, _ptr(st.graph_ws), _ptr(st.fwd_ws), st.fwd_ws.numel(),
+                                                       _ptr(st.virial_ws), st.virial_ws.numel(), n, n_mol, n_pairs, _ptr(z), _ptr(batch),
+                                                       _ptr(q), 1, _ptr(energy), _ptr(forces), _ptr(virial))
+                else:
+                    rc = L.tmdnet_energy_forces(st.handle, stream, _ptr(st.graph_ws), _ptr(st.fwd_ws), st.fwd_ws.numel(), n, n_mol,
+                                                n_pairs, _ptr(z), _ptr(batch), _ptr(q), int(want_forces), _ptr(energy), _ptr(forces))
             finally:  # also when the graph phase raised: the handle must not keep a callback or weights that are about to be freed
                 if halo_exchange is not None:
                     L.tmdnet_set_halo_exchange(st.handle, _C.HALO_EXCHANGE_FN(), None)
@@ -1175,13 +1192,75 @@ class TorchMD_Net(nn.Module):
                     L.tmdnet_set_atom_weights(st.handle, None)
             if "error" in halo_state:
                 raise halo_state["error"]
+            if rc == _C.ERR_INVALID and want_virial:  # a refusal of the C entry that the checks above did not anticipate
+                raise NotImplementedError(f"tmdnet_energy_forces_virial: {L.tmdnet_last_error(st.handle).decode()}")
             if rc != _C.OK:
                 raise RuntimeError(f"tmdnet_energy_forces: {L.tmdnet_last_error(st.handle).decode()} (code {rc})")
             if static and self.static_check and not torch.cuda.is_current_stream_capturing():
                 # outside a capture the overflow flag is polled (one sync); replays of a captured graph are unchecked,
                 # like the reference's asynchronous assert (models/utils.py:297-300): call check_overflow() when convenient
                 self.check_overflow(n, n_mol)
+        if want_virial:
+            return energy, forces, virial
         return energy, forces
+
+    def _refuse_virial(self, atom_weights=None, halo_exchange=None):
+        """What the virial is not implemented for (``tmdnet_energy_forces_virial`` answers TMDNET_ERR_INVALID for the same cases):
+        raised before anything is set on the handle, which stays usable."""
+        if self._is_tn2():
+            raise NotImplementedError("the virial has no HIP path for TensorNet2: the Coulomb head's forces do not come from the "
+                                      "per-pair gradient")
+        if self._head_kind() != _C.HEAD_SCALAR:
+            raise NotImplementedError(f"the virial has no HIP path with output_model {type(self.output_model).__name__} "
+                                      "(scalar head only)")
+        if atom_weights is not None or halo_exchange is not None:
+            raise NotImplementedError("the virial has no HIP path with atom weights or the halo exchange")
+        if self.parameter_gradients and torch.is_grad_enabled():
+            raise NotImplementedError("the virial has no HIP path inside the parameter-gradient and second-order passes "
+                                      "(parameter_gradients=True): evaluate it under torch.no_grad()")
+
+    @staticmethod
+    def stress(W: Tensor, box: Tensor) -> Tensor:
+        """Stress of every molecule from its virial: sigma_m = -W_m / V_m with V_m = |det box_m|.  ``W`` [B,3,3] (or [3,3]), ``box``
+        one [3,3] box for all molecules or one per molecule [B,3,3]."""
+        vol = torch.linalg.det(box.to(device=W.device, dtype=W.dtype)).abs()
+        return -W / (vol.reshape(-1, 1, 1) if box.dim() == 3 else vol)
+
+    def energy_forces_virial(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
+                             q: Optional[Tensor] = None, num_systems: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """(E [B,1], F [N,3], W [B,3,3]): energies, forces and the virial W_m[a][b] = -dE_m/d eps_ab under the homogeneous strain
+        pos -> pos (I + eps), box -> box (I + eps) (row vectors; ``stress(W, box)`` = -W / V).  Inputs are staged and checked as in
+        ``forward``; E and F are bit-identical to ``forward``'s.  When ``pos`` or ``box`` requires grad, the call goes through the
+        registered operator ``tmdnet::energy_forces_virial``: ``E.backward()`` then fills ``pos.grad`` (from F) and ``box.grad``
+        (from W and F); F and W themselves carry no graph (second derivatives raise)."""
+        assert z.dim() == 1 and z.dtype == torch.long
+        batch = torch.zeros_like(z) if batch is None else batch
+        if pos.dtype != torch.float32:
+            raise NotImplementedError("torchmdnet_amd computes in fp32; cast positions to float32")
+        if pos.device.type == "cpu" and torch.cuda.is_available():  # host tensors: staged as in _forward_host_tensors
+            dev = torch.device("cuda", torch.cuda.current_device())
+            pdev = next(self.parameters()).device
+            if pdev.type == "cuda":
+                dev = pdev
+            mv = lambda t: None if t is None else t.to(dev)
+            e, f, w = self.energy_forces_virial(z.to(dev), pos.to(dev), mv(batch), mv(box), mv(q), num_systems)
+            return e.to(pos.device), f.to(pos.device), w.to(pos.device)
+        _require_cuda(pos, "TorchMD_Net.energy_forces_virial")
+        n_mol = int(num_systems) if num_systems is not None else (int(batch.max().item()) + 1 if z.numel() else 0)
+        rm = self.representation_model
+        if box is None and rm.distance.use_periodic:
+            box = rm.distance.box
+        if box is not None and box.device != pos.device:
+            box = box.to(pos.device)
+        self._refuse_virial()
+        grad = torch.is_grad_enabled() and (pos.requires_grad or (box is not None and box.requires_grad))
+        if grad:
+            if self._engine.op_key is None:
+                self._engine.op_key = ops.register_engine(self)
+            energy, forces, virial = torch.ops.tmdnet.energy_forces_virial(z, pos, batch, box, q, self._engine.op_key, n_mol)
+        else:
+            energy, forces, virial = self.energy_and_forces(z, pos, batch, box, q, n_mol, want_virial=True)
+        return energy.view(-1, 1), forces, virial
 
     @staticmethod
     def _raise_bad_indices(counts, msg):
@@ -1227,8 +1306,9 @@ class TorchMD_Net(nn.Module):
         return tuple(int(v) for v in grid)
 
     def capture(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
-                q: Optional[Tensor] = None, num_systems: Optional[int] = None, warmup: int = 3):
-        """Capture one energy+force evaluation into a HIP graph (needs ``static_shapes=True``).
+                q: Optional[Tensor] = None, num_systems: Optional[int] = None, warmup: int = 3, virial: bool = False):
+        """Capture one energy+force evaluation into a HIP graph (needs ``static_shapes=True``).  ``virial=True``: the graph also
+        computes the virial; the replay then returns ``(energy, forces, W [B,3,3])`` and ``replay.virial`` is the static W buffer.
         Returns ``replay(pos) -> (energy [B,1] ([B,3]: vector output), forces [N,3])`` writing into static buffers - the reference gets
         the same effect with torch.cuda.graphs around its model (calculators.py:117-128)."""
         if not getattr(self.representation_model, "static_shapes", False):
@@ -1253,11 +1333,15 @@ class TorchMD_Net(nn.Module):
         side.wait_stream(torch.cuda.current_stream(pos.device))
         with torch.cuda.stream(side):
             for _ in range(max(warmup, 1)):  # uploads parameters, sizes the workspaces, checks overflow
-                self.energy_and_forces(z, s_pos, batch, box, q, n_mol, want_forces=True)
+                self.energy_and_forces(z, s_pos, batch, box, q, n_mol, want_forces=True, want_virial=virial)
         torch.cuda.current_stream(pos.device).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
+        s_w = None
         with torch.cuda.graph(graph):
-            s_e, s_f = self.energy_and_forces(z, s_pos, batch, box, q, n_mol, want_forces=True)
+            if virial:
+                s_e, s_f, s_w = self.energy_and_forces(z, s_pos, batch, box, q, n_mol, want_forces=True, want_virial=True)
+            else:
+                s_e, s_f = self.energy_and_forces(z, s_pos, batch, box, q, n_mol, want_forces=True)
         engine, generation = self._engine, self._engine.generation
 
         def replay(new_pos: Optional[Tensor] = None):
@@ -1270,12 +1354,16 @@ class TorchMD_Net(nn.Module):
                 # costs ~3x a small kernel between two graph launches.  Integrators that can write in place use replay.pos.
                 torch.mul(new_pos.detach(), 1.0, out=s_pos)
             graph.replay()
+            if s_w is not None:
+                return s_e.view(-1, 1), s_f, s_w
             return (s_e.view(-1, 3) if s_e.dim() == 2 else s_e.view(-1, 1)), s_f
 
         replay.graph = graph
         replay.inputs = (z, batch, box, q)  # what the graph reads, kept alive for as long as it can be replayed
         replay.pos = s_pos  # the positions the graph reads: write them in place and call replay() to skip the copy
         replay.n_atoms, replay.n_mol = int(z.shape[0]), n_mol
+        if s_w is not None:
+            replay.virial = s_w  # static buffer the graph writes W into
         return replay
 
     def debug_tensor(self, name: str, shape) -> Tensor:

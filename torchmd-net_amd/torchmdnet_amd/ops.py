@@ -4,11 +4,15 @@ The reference exposes its native kernels as ``torch.library.custom_op``s with ``
 (torchmdnet/extensions/warp_ops/neighbors.py:34-148, warp_ops/tensornet_mp.py:538-548, entry binding
 torchmdnet/models/tensornet.py:54-66); that is what lets ``torch.compile`` (calculators.py:297), ``torch.export``
 (tests/test_export.py) and the CUDA-graph tests trace through them.  Here the seam is coarser - the whole energy+force
-evaluation is ONE library call - so two ops are registered:
+evaluation is ONE library call - so these ops are registered:
 
   tmdnet::energy_forces(z, pos, batch, box?, q?, engine, n_mol, want_forces) -> (energy [n_mol], forces [N,3] or [0,3])
       autograd: d(sum_m g_m E_m)/d pos_i = -g_{batch_i} F_i  (molecules are independent); no second derivatives
       (EquivariantVectorOutput: energy [n_mol, 3]; the backward takes a gradient equal across the three components)
+  tmdnet::energy_forces_virial(z, pos, batch, box?, q?, engine, n_mol) -> (energy [n_mol], forces [N,3], virial [n_mol,3,3])
+      the same evaluation with the virial W_m = - d E_m / d eps (tmdnet_energy_forces_virial; TensorNet / ET, scalar head)
+      autograd: g_pos as above, and a BOX gradient from the strain identity d E / d eps = X^T d E / d X + H^T d E / d H per molecule:
+      d E_m / d H_m = H_m^-T (-W_m + X_m^T F_m); no second derivatives (a gradient of F or W raises)
   tmdnet::neighbor_pairs(pos, batch, box?, cutoff_lower, cutoff_upper, max_num_pairs, loop, include_transpose, strategy)
       -> (neighbors [2,M] int64, deltas [M,3], distances [M], num_pairs [1] int32)      (reference op: same outputs)
       float32 or float64 positions, like the reference's (tmdnet_neighbor_pairs / tmdnet_neighbor_pairs_f64)
@@ -90,6 +94,58 @@ def _ef_backward(ctx, g_energy, g_forces):
 
 
 energy_forces.register_autograd(_ef_backward, setup_context=_ef_setup)
+
+
+# ------------------------------------------------------------------------------------------------ energy + forces + virial
+@torch.library.custom_op("tmdnet::energy_forces_virial", mutates_args=(), device_types="cuda")
+def energy_forces_virial(z: Tensor, pos: Tensor, batch: Tensor, box: Optional[Tensor], q: Optional[Tensor], engine: int,
+                         n_mol: int) -> Tuple[Tensor, Tensor, Tensor]:
+    module = _ENGINES.get(engine)
+    if module is None:
+        raise RuntimeError(f"tmdnet::energy_forces_virial: engine {engine} is gone (its TorchMD_Net module was deleted)")
+    return module.energy_and_forces(z, pos, batch, box, q, n_mol, want_virial=True)
+
+
+@energy_forces_virial.register_fake
+def _(z, pos, batch, box, q, engine, n_mol):
+    return (pos.new_empty((n_mol,), dtype=torch.float32), pos.new_empty((pos.shape[0], 3), dtype=torch.float32),
+            pos.new_empty((n_mol, 3, 3), dtype=torch.float32))
+
+
+def _efv_setup(ctx, inputs, output):
+    z, pos, batch, box, q, engine, n_mol = inputs
+    energy, forces, virial = output
+    ctx.set_materialize_grads(False)  # an unused output arrives as None: a gradient of F or W is then told apart from none
+    ctx.n_mol = int(n_mol)
+    ctx.save_for_backward(forces, virial, batch, pos, box)
+
+
+def _efv_backward(ctx, g_energy, g_forces, g_virial):
+    forces, virial, batch, pos, box = ctx.saved_tensors
+    if g_forces is not None or g_virial is not None:
+        raise NotImplementedError("tmdnet::energy_forces_virial: gradients of the forces or the virial (second derivatives) are not "
+                                  "implemented on the HIP path")
+    if g_energy is None:
+        return None, None, None, None, None, None, None
+    bl = batch.to(torch.long)
+    g = g_energy.reshape(-1)
+    g_pos = -forces * g[bl].unsqueeze(-1) if ctx.needs_input_grad[1] else None
+    g_box = None
+    if box is not None and ctx.needs_input_grad[3]:
+        # off the hot path: torch ops in fp64 on the device.  X^T F per molecule, then H^-T (-W + X^T F) scaled by the incoming seed;
+        # one shared box takes the sum over the molecules
+        X, F64 = pos.detach().to(torch.float64), forces.to(torch.float64)
+        xtf = torch.zeros((ctx.n_mol, 3, 3), dtype=torch.float64, device=pos.device)
+        xtf.index_add_(0, bl, X.unsqueeze(2) * F64.unsqueeze(1))
+        rhs = (xtf - virial.to(torch.float64)) * g.to(torch.float64).view(-1, 1, 1)
+        H = box.detach().to(torch.float64)
+        if H.dim() == 2:
+            rhs = rhs.sum(0)
+        g_box = torch.linalg.solve(H.transpose(-1, -2), rhs).to(box.dtype)
+    return None, g_pos, None, g_box, None, None, None
+
+
+energy_forces_virial.register_autograd(_efv_backward, setup_context=_efv_setup)
 
 
 # ------------------------------------------------------------------------------------------------ neighbour pairs
