@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "tn_chain.h"
 #include "tn_heads.h"
 #include "tn_model.h"
 #include "tn_tlin9.h"
@@ -951,20 +952,32 @@ int tmdnet_finalize_params(tmdnet_model* m) {
     add_sb("O1T", F, H);
     // fragment-major images of the 9-component tensor linears' weights (tn_tlin9.hip), same buffer
     std::vector<Img> fms;
-    auto add_fm = [&](const std::string& key) {
-      if (F % 32) return;
-      fms.push_back({key, F, F, sb_elems});
-      sb_elems += split_weight_fm_elems(F, F);
+    auto add_fm = [&](const std::string& key, int64_t n, int64_t k) {  // packed matrix `key` is [n][k] row-major
+      if ((n % 32) || (k % 16)) return;
+      fms.push_back({key, n, k, sb_elems});
+      sb_elems += split_weight_fm_elems(n, k);
     };
     for (int k = 0; k < 3; ++k) {
-      add_fm("Ue" + std::to_string(k));
-      add_fm("UeT" + std::to_string(k));
+      add_fm("Ue" + std::to_string(k), F, F);
+      add_fm("UeT" + std::to_string(k), F, F);
     }
     for (int l = 0; l < L; ++l)
       for (int k = 0; k < 6; ++k) {
-        add_fm("l" + std::to_string(l) + ".V" + std::to_string(k));
-        add_fm("l" + std::to_string(l) + ".VT" + std::to_string(k));
+        add_fm("l" + std::to_string(l) + ".V" + std::to_string(k), F, F);
+        add_fm("l" + std::to_string(l) + ".VT" + std::to_string(k), F, F);
       }
+    if (!m->tn2 && chain_readout_shape_ok(F, H)) {  // the readout chain (tn_chain.hip)
+      add_fm("Lin", F, 3 * F);
+      add_fm("LinT", 3 * F, F);
+      add_fm("O1", H, F);
+      add_fm("O1T", F, H);
+    }
+    if (!m->tn2 && chain_gate_shape_ok(F)) {  // the gate chains
+      add_fm("L1", 2 * F, F);
+      add_fm("L2", 3 * F, 2 * F);
+      add_fm("L2T", 2 * F, 3 * F);
+      add_fm("L1T", F, 2 * F);
+    }
     if (m->dev_sb && m->dev_sb_cap < sb_elems) {
       HIP_TRY(m, hipFree(m->dev_sb));
       m->dev_sb = nullptr;
@@ -1130,6 +1143,14 @@ int tmdnet_set_option(tmdnet_model* m, const char* name, double value) {
     m->rb_min_atoms = value < 0 ? 0 : (int64_t)value;
     return TMDNET_OK;
   }
+  if (n == "chain_min_atoms") {
+    m->chain_min_atoms = value < 0 ? 0 : (value > 9e18 ? INT64_MAX : (int64_t)value);
+    return TMDNET_OK;
+  }
+  if (n == "chain_mask") {
+    m->chain_mask = (int)value & 7;
+    return TMDNET_OK;
+  }
   if (n == "pair_rows_bf16") {
     if (!m->et) return fail(m, TMDNET_ERR_INVALID, "pair_rows_bf16 applies to the Equivariant Transformer handle only");
     m->pair_bf16 = value != 0.0 ? 1 : 0;
@@ -1154,6 +1175,9 @@ int tmdnet_get_info(const tmdnet_model* m, const char* name, double* value) {
   else if (n == "edge_table_min_pairs") *value = (double)m->tab_min_pairs;
   else if (n == "pair_rows_bf16") *value = (double)m->pair_bf16;
   else if (n == "embed_rb_min_atoms") *value = (double)m->rb_min_atoms;
+  else if (n == "chain_min_atoms") *value = (double)m->chain_min_atoms;
+  else if (n == "chain_mask") *value = (double)m->chain_mask;
+  else if (n == "chain_last") *value = (double)m->chain_last;  // chains (bits of chain_mask) the last energy / force call ran
   else if (n == "recompute_pair_rows") *value = m->recompute_rows ? 1.0 : 0.0;
   else if (n == "embed_rb") *value = m->rb_fwd ? 1.0 : 0.0;
   else if (n == "species_last_build") *value = (double)m->last_nt;
@@ -1513,6 +1537,22 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
   const int64_t* const batch_a = batch_k ? batch_k + o1_ : nullptr;  // their molecule index
   const bool fused_small = !tc && !ntp && !recompute && !m->halo_fn && !m->head_kind && (small_fused_ok(N, F, H, L) || mid_fused_ok(N, F, H, L)) &&
                            (!want_forces || (message_adjoint_gd_ok(N, F) && !getenv("TMDNET_SEPARATE_PAIR_GD")));
+  // per-atom chain kernels (tn_chain.hip).  Readout + head + adjoint in one pass: needs forward and reverse in the same call and
+  // forces as the only gradient (the head's reverse seed is then local to the atom); the property heads seed g_ao from molecule
+  // sums, the halo exchange runs the per-atom kernels on a row range, the parameter-gradient pass keeps every intermediate: those
+  // keep the launches below.  Atom weights are supported (applied per atom as k_head_energy does).
+  auto fm_image = [&](const float* w) -> const uint16_t* {
+    auto it = m->fm_of.find(w);
+    return it == m->fm_of.end() ? nullptr : it->second;
+  };
+  const bool chain_any = !tc && !m->head_kind && !m->halo_fn && Na == N && !fused_small && (int64_t)N >= m->chain_min_atoms;
+  const bool chain_ro = chain_any && (m->chain_mask & 1) && want_forces && run_fwd && run_bwd && chain_readout_shape_ok(F, H) &&
+                        fm_image(W.Lin) && fm_image(W.LinT) && fm_image(W.O1) && fm_image(W.O1T);
+  // the embedding's gate MLP and its adjoint: same conditions (an energy-only call keeps today's launches as a whole)
+  const bool chain_gate = chain_any && want_forces && run_fwd && run_bwd && chain_gate_shape_ok(F);
+  const bool chain_gf = chain_gate && (m->chain_mask & 2) && fm_image(W.L1) && fm_image(W.L2);
+  const bool chain_gb = chain_gate && (m->chain_mask & 4) && fm_image(W.L2T) && fm_image(W.L1T);
+  m->chain_last = (chain_ro ? 1 : 0) | (chain_gf ? 2 : 0) | (chain_gb ? 4 : 0);
   if (run_fwd) {
     if (use_tab) {
       // radial tables (tn_edge_table.hip): sort the pairs by distance, one streaming Hermite-interpolation kernel for all
@@ -1620,11 +1660,22 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
       KR(CAT_SCATTER, Pd * 12 * Fd + E_ * 12 + Nd * 10 * Fd * 4,
          launch_embed_scatter(g, N, F, z, W.Utab, W.Vtab, b.Q, b.C, b.u0, b.s0n, s));
     }
+    NODE();
+    if (chain_gf) {
+      // one launch from s0n to the gates: ln0 and h1 are not written
+      ChainGateFwdArgs ca{};
+      ca.s0n = b.s0n; ca.xh0 = b.xh0; ca.rstd0 = b.rstd0; ca.a1 = b.a1; ca.a2 = b.a2; ca.gates = b.gates;
+      ca.ln_w = W.ln0_w; ca.ln_b = W.ln0_b; ca.bL1 = W.bL1; ca.bL2 = W.bL2; ca.L1_fm = fm_image(W.L1); ca.L2_fm = fm_image(W.L2); ca.N = N;
+      char lab[64];
+      std::snprintf(lab, sizeof(lab), "chain gate_fwd %dx%d", N, F);
+      ProfScope ps_(s, CAT_GEMM_NODE, 2.0 * Nd * 8.0 * Fd * Fd, Nd * 10 * Fd * 4 + Nd * 4 + 4.0 * 8.0 * Fd * Fd, lab);
+      if (launch_chain_gate_fwd(ca, F, s)) return fail(m, TMDNET_ERR_HIP, "launch_chain_gate_fwd");
+    } else {
     KR(CAT_ELEMENTWISE, Nd * Fd * 12,
        launch_layernorm_fwd(b.s0n + oF, W.ln0_w, W.ln0_b, Na, F, b.ln0 + oF, b.xh0 + oF, b.rstd0 + o1_, s));
-    NODE();
     gemm(s, b.ln0 + oF, F, W.L1, F, W.bL1, b.h1 + o2F, 2 * F, Na, 2 * F, F, GEMM_ACT_SILU, b.a1 + o2F, 2 * F);
     gemm(s, b.h1 + o2F, 2 * F, W.L2, 2 * F, W.bL2, b.gates + o3F, 3 * F, Na, 3 * F, 2 * F, GEMM_ACT_SILU, b.a2 + o3F, 3 * F);
+    }
     // fused 9-component tensor linears (tn_tlin9.hip) at batch scale; the parameter-gradient pass keeps the unfused schedule,
     // whose intermediates (X_hat, C_hat, g_D, g_C_hat per layer) are operands of its weight-gradient products
     if (t9) {
@@ -1668,6 +1719,22 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
     }
     // ---- readout + head + per-molecule sum
     if (L == 0) KR(CAT_ELEMENTWISE, nodeB + Nd * 3 * Fd * 4, launch_readout_feat(b.X[L] + o9F, Na, F, b.feat + o3F, s));
+    if (chain_ro) {
+      // one launch from feat to G (and the per-atom energies): none of lnr, xhr, rstdr, al, ao, g_ao, g_al, g_ln is written
+      ChainReadoutArgs ca{};
+      ca.feat = b.feat; ca.X = b.X[L]; ca.G = b.G; ca.x = b.x; ca.ea = b.ea;
+      ca.lnr_w = W.lnr_w; ca.lnr_b = W.lnr_b; ca.bLin = W.bLin; ca.bO1 = W.bO1; ca.O2 = W.O2; ca.bO2 = W.bO2;
+      ca.Lin_fm = fm_image(W.Lin); ca.LinT_fm = fm_image(W.LinT); ca.O1_fm = fm_image(W.O1); ca.O1T_fm = fm_image(W.O1T);
+      ca.atomref = W.atomref; ca.z = z; ca.aw = m->atom_w; ca.perm = perm; ca.std_ = W.std; ca.N = N;
+      {
+        char lab[64];
+        std::snprintf(lab, sizeof(lab), "chain readout_fb %dx%dx%d", N, F, H);
+        ProfScope ps_(s, CAT_GEMM_NODE, 2.0 * Nd * (2.0 * 3 * Fd * Fd + 2.0 * Fd * H),
+                      2 * nodeB + Nd * 4 * Fd * 4 + Nd * 4 + 4.0 * (2.0 * 3 * Fd * Fd + 2.0 * Fd * H), lab);
+        if (launch_chain_readout_fb(ca, F, H, s)) return fail(m, TMDNET_ERR_HIP, "launch_chain_readout_fb");
+      }
+      KR(CAT_ELEMENTWISE, Nd * 4, launch_mol_sum(g, b.ea, batch, N, B, W.mean, energy, s));
+    } else {
     KR(CAT_ELEMENTWISE, Nd * 3 * Fd * 12,
        launch_layernorm_fwd(b.feat + o3F, W.lnr_w, W.lnr_b, Na, 3 * F, b.lnr + o3F, b.xhr + o3F, b.rstdr + o1_, s));
     NODE();
@@ -1689,6 +1756,7 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
                             perm ? m->atom_w : (m->atom_w ? m->atom_w + o1_ : nullptr), perm ? perm + o1_ : nullptr));
       KR(CAT_ELEMENTWISE, Nd * 4, launch_mol_sum(g, b.ea, batch, N, B, W.mean, energy, s));
     }
+    }  // !chain_ro
     }  // !fused_small
   }
   if (m->head_kind && want_forces && run_bwd)  // reverse seeds into g_ao, and the centre-of-mass term of the forces
@@ -1743,15 +1811,17 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
       launch_tn_gemm(s, b.g_ao, rH, b.x, rF, nullptr, nullptr, N, H, F, tc->at("O1"), false, tc->part);
       launch_colsum(s, b.g_ao, rH, nullptr, rH, nullptr, nullptr, N, H, tc->at("bO1"), false, tc->part);
     }
-    gemm(s, b.g_ao + oH, H, W.O1T, H, nullptr, b.g_al + oF, F, Na, F, H, GEMM_MUL_DSILU_AUX, nullptr, 0, b.al + oF, F);
-    gemm(s, b.g_al + oF, F, W.LinT, F, nullptr, b.g_ln + o3F, 3 * F, Na, 3 * F, F);
+    // (chain_ro: G came out of the readout chain of the forward half)
+    if (!chain_ro) gemm(s, b.g_ao + oH, H, W.O1T, H, nullptr, b.g_al + oF, F, Na, F, H, GEMM_MUL_DSILU_AUX, nullptr, 0, b.al + oF, F);
+    if (!chain_ro) gemm(s, b.g_al + oF, F, W.LinT, F, nullptr, b.g_ln + o3F, 3 * F, Na, 3 * F, F);
     if (tc) {
       launch_tn_gemm(s, b.g_al, rF, b.lnr, r3F, nullptr, nullptr, N, F, 3 * F, tc->at("Lin"), false, tc->part);
       launch_colsum(s, b.g_al, rF, nullptr, rF, nullptr, nullptr, N, F, tc->at("bLin"), false, tc->part);
       launch_colsum(s, b.g_ln, r3F, b.xhr, r3F, nullptr, nullptr, N, 3 * F, tc->at("lnr_w"), false, tc->part);
       launch_colsum(s, b.g_ln, r3F, nullptr, r3F, nullptr, nullptr, N, 3 * F, tc->at("lnr_b"), false, tc->part);
     }
-    if (F % 64 == 0) {
+    if (chain_ro) {
+    } else if (F % 64 == 0) {
       KR(CAT_ELEMENTWISE, 2 * nodeB + Nd * 3 * Fd * 8,
          launch_lnbwd_readout_bwd(b.g_ln + o3F, b.xhr + o3F, b.rstdr + o1_, W.lnr_w, Na, F, b.X[L] + o9F, b.G + o9F, s));
     } else {
@@ -1836,9 +1906,20 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
       KR(CAT_ELEMENTWISE, 3 * nodeB + Nd * 3 * Fd * 12,
          launch_embed_gate_bwd(b.G + o9F, b.UX + o9F, b.gates + o3F, b.a2 + o3F, Na, F, b.gUX + o9F, b.g_a2 + o3F, s));
     NODE();
+    if (chain_gb) {
+      // one launch from g_a2 to g_s0n: g_a1 and g_ln0 are not written
+      ChainGateBwdArgs ca{};
+      ca.g_a2 = b.g_a2; ca.a1 = b.a1; ca.xh0 = b.xh0; ca.rstd0 = b.rstd0; ca.ln_w = W.ln0_w; ca.g_s0n = b.g_s0n;
+      ca.L2T_fm = fm_image(W.L2T); ca.L1T_fm = fm_image(W.L1T); ca.N = N;
+      char lab[64];
+      std::snprintf(lab, sizeof(lab), "chain gate_bwd %dx%d", N, F);
+      ProfScope ps_(s, CAT_GEMM_NODE, 2.0 * Nd * 8.0 * Fd * Fd, Nd * 7 * Fd * 4 + Nd * 4 + 4.0 * 8.0 * Fd * Fd, lab);
+      if (launch_chain_gate_bwd(ca, F, s)) return fail(m, TMDNET_ERR_HIP, "launch_chain_gate_bwd");
+    } else {
     gemm(s, b.g_a2 + o3F, 3 * F, W.L2T, 3 * F, nullptr, b.g_a1 + o2F, 2 * F, Na, 2 * F, 3 * F, GEMM_MUL_DSILU_AUX, nullptr, 0, b.a1 + o2F, 2 * F);
     gemm(s, b.g_a1 + o2F, 2 * F, W.L1T, 2 * F, nullptr, b.g_ln0 + oF, F, Na, F, 2 * F);
     KR(CAT_ELEMENTWISE, Nd * Fd * 12, launch_layernorm_bwd(b.g_ln0 + oF, b.xh0 + oF, b.rstd0 + o1_, W.ln0_w, Na, F, b.g_s0n + oF, s));
+    }
     if (!tc && tlin9_ok(Na, F, rng) && tlin9_images(W.UeT)) {
       Tl9Args ta{};
       ta.A = b.gUX + o9F; ta.e0 = b.u0 + o9F; ta.e1 = b.g_s0n + oF; ta.o1 = b.gA + 10 * oF; ta.N = Na; ta.F = F;

@@ -214,6 +214,12 @@ struct tmdnet_model {
   const uint16_t *rb_fwd = nullptr, *rb_rev = nullptr;
   int last_nt = 0;
   int64_t rb_min_atoms = 1024;
+  // per-atom chain kernels (tn_chain.hip): atom threshold (option "chain_min_atoms"; default: where the general schedule switches to
+  // k_tlin9, 128 tiles of 32 atoms), which chains may run (option "chain_mask": bit 0 readout + head + adjoint, bit 1 gate MLP forward, bit 2 gate
+  // MLP adjoint) and which ran in the last call (info "chain_last", same bits)
+  int64_t chain_min_atoms = 4096;
+  int chain_mask = 7;
+  int chain_last = 0;
   int pair_bf16 = 0;          // option "pair_rows_bf16" (Equivariant Transformer): per-pair filter rows stored as bf16
   bool tabs_pending = false;  // parameters changed since the radial tables were built: rebuilt by the next call that uses them
   int64_t tab_min_pairs = 1;  // developer / test switch (option "edge_table_min_pairs"): fewer pairs take the value + tangent GEMMs
