@@ -407,6 +407,60 @@ int tmdnet_loss_param_grads(tmdnet_model* m, void* stream, void* graph_ws, void*
  * out == NULL: returns the element count instead of a status. */
 int tmdnet_hvp_debug_tensor(tmdnet_model* m, void* stream, const char* name, float* out, int64_t numel);
 
+/* ---- Device-resident molecular dynamics (csrc/tn_md.hip; additive exports, the ABI revision stays 10) ------------------------
+ * The integrator launches that sit between two tmdnet_energy_forces calls of a captured step, so that K full MD steps replay as
+ * one HIP graph without host work in between (the reference has no counterpart: its MD loops live in the caller's Python).
+ * Scheme, per atom i, with hk_i = dt force_scale / (2 m_i):
+ *     v <- v + hk_i F    x <- x + dt v    F = F(x)    v <- v + hk_i F    [ v <- c1 v + c2 sigma_i xi ]
+ * Units: whatever the caller's are, as long as force_scale turns [F] / [m] into [x] / [dt]^2 - with eV, Angstrom, amu and fs,
+ * force_scale = 9.648533e-3 (1 eV / (Angstrom amu) = 9.648533e-3 Angstrom / fs^2).  `pos` is never wrapped: the engine takes
+ * unwrapped positions.  sigma_i = sqrt(kT force_scale / m_i) is the thermal velocity, c1 = exp(-gamma dt), c2 = sqrt(1 - c1^2).
+ * An atom with m = inf (hk = sigma = 0) and zero velocity is frozen: its position and velocity keep their bits, and it
+ * adds nothing to the kinetic energy.
+ * Rounding contract: every product and every sum above is a single round-to-nearest fp32 operation in the order written (hk F,
+ * then + v; dt v, then + x; c1 v, c2 sigma, that times xi, then the sum), never contracted into an FMA and never reassociated; a
+ * launch that closes one step and opens the next performs the two kicks as two additions.  Without a thermostat a trajectory is
+ * therefore bit-identical to any fp32 mirror that evaluates the same operations one by one on the same forces.
+ * Noise: Philox4x32-10, key = `seed` (low word first), counter = (step low, step high, atom index in the CALLER's order, 0)
+ * with `step` the number of steps completed before this one; words 0 / 1 give (xi_x, xi_y) by Box-Muller, words 2 / 3 give xi_z
+ * (cosine branch), from u = ((word >> 8) + 0.5) 2^-24 and the accurate logf / cosf / sinf.  It depends on (seed, step, atom) only.
+ * All pointers are caller-owned device memory unless stated; nothing allocates, and only tmdnet_md_status synchronises. */
+#define TMDNET_MD_OPEN 0   /* B, A of the first step of a replay (reads `forces` of the state the loop starts from) */
+#define TMDNET_MD_MIDDLE 1 /* after an evaluation: B [, O], kinetic energy of that step, then B, A of the next, in one launch */
+#define TMDNET_MD_CLOSE 2  /* after the last evaluation: B [, O], kinetic energy */
+/* Bytes of the MD state `md_ws` for n_atoms atoms in n_mol molecules: a 256-byte header (64-bit step counter, sticky status),
+ * the positions and velocities of the last completed step (24 bytes per atom), 4 bytes per atom of kinetic-energy terms and the
+ * slice sums of molecules above 1 024 atoms. */
+int tmdnet_md_workspace_bytes(int64_t n_atoms, int64_t n_mol, size_t* bytes);
+/* Enqueues: step counter = step0, status = 0.  Required once before the first tmdnet_md_advance on a workspace. */
+int tmdnet_md_reset(void* stream, void* md_ws, uint64_t step0);
+/* Enqueues one integrator launch (TMDNET_MD_MIDDLE / _CLOSE: plus the per-molecule reduction of the kinetic energy, one launch,
+ * two when a molecule has more than 1 024 atoms on average).  K steps are OPEN, then K times { evaluation at `pos`; MIDDLE, or CLOSE
+ * after the last }.
+ *   m, graph_ws   the handle and graph workspace of the evaluation before this launch: its overflow flag is read, and the atom
+ *                 ranges of the molecules are taken from it.  graph_ws == NULL (m may then be NULL): no overflow test, the
+ *                 kinetic energy is summed over `batch` (NULL: one molecule).
+ *   pos, vel      [n_atoms, 3], updated in place.
+ *   forces        [n_atoms, 3], read only: any buffer, the evaluation's output or the caller's own.
+ *   energy        [n_mol] or NULL: copied to epot_log_row (the next evaluation overwrites it).
+ *   hk, mass, sigma   [n_atoms]; sigma == NULL: no thermostat (c1, c2, seed unused); mass is read by MIDDLE / CLOSE only.
+ *   batch         [n_atoms] int64 molecule index in the caller's order, or NULL.
+ *   forces_keep   [n_atoms, 3] or NULL: MIDDLE / CLOSE copy `forces` here, so that a buffer the caller owns always holds the
+ *                 forces at the last completed step (the `forces` of the next replay's OPEN).
+ *   epot_log_row, ekin_log_row   [n_mol] each, or NULL: energies of the step just completed; ekin = sum of 0.5 m v^2 after the
+ *                 closing kick and the O step, in the unit of m v^2 (divide by force_scale for the unit of the energies), summed
+ *                 in a fixed order without floating-point atomics: bit-identical repeats.
+ * Overflow: when the evaluation before a MIDDLE / CLOSE launch overflowed (static shapes: its forces are stale), pos and vel go
+ * back to the last completed step and the status word is set; from then on every launch leaves pos, vel, forces_keep, the log
+ * rows and the step counter alone, until tmdnet_md_reset. */
+int tmdnet_md_advance(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, int64_t n_atoms, int64_t n_mol, int32_t phase,
+                      float* pos, float* vel, const float* forces, const float* energy, const float* hk, const float* mass,
+                      const float* sigma, float dt, float c1, float c2, uint64_t seed, const int64_t* batch, float* forces_keep,
+                      float* epot_log_row, float* ekin_log_row);
+/* host[0] = steps completed (the device counter), host[1] = status (1: an evaluation overflowed; the state is that of step
+ * host[0]).  Synchronises the stream.  Returns TMDNET_ERR_OVERFLOW when the status is set. */
+int tmdnet_md_status(void* stream, void* md_ws, uint64_t host[2]);
+
 #ifdef __cplusplus
 }
 #endif

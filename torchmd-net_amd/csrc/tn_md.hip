@@ -1,0 +1,295 @@
+// Device-resident molecular dynamics: the integrator kernels that sit between two energy+force evaluations of a captured step,
+// so that K full MD steps replay as one HIP graph with no host work in between.
+//
+// One step (velocity Verlet; with a thermostat the BAOAB-like "B A [F] B O" splitting):
+//   v <- v + hk F      (B)      hk_i = dt force_scale / (2 m_i), one value per atom
+//   x <- x + dt v      (A)      unwrapped positions
+//   F  = F(x)                   the engine's evaluation (any force buffer: the kernels take a plain pointer)
+//   v <- v + hk F      (B)
+//   v <- c1 v + c2 sigma_i xi   (O, only with a thermostat; xi from Philox4x32-10 keyed by (seed, step, caller's atom index))
+// The launch that follows an evaluation closes step k (B, O, kinetic-energy term) and opens step k + 1 (B, A) for the same atom in
+// the same thread - phase TMDNET_MD_MIDDLE -, so K steps are K evaluations and K + 1 per-atom launches (OPEN, K - 1 x MIDDLE, CLOSE),
+// each closing launch followed by the per-molecule reduction of the kinetic energy.  The arithmetic is tn_md_math.h; every
+// product and sum is one fp32 round-to-nearest operation in the order written there.
+//
+// State (tmdnet_md_workspace_bytes, caller-owned, device): a header {step lo, step hi, status}, the positions and velocities
+// at the last completed step (written by the opening half before it moves the atoms), the per-atom kinetic-energy terms and the
+// slice sums of large molecules.  Nothing allocates or synchronises; everything is capturable.
+//
+// Overflow.  The graph phase rebuilds its overflow flag counts[2] on every evaluation, and an overflowed evaluation leaves stale
+// forces.  The launch after an evaluation reads the flag: when it is set, every atom goes back to the saved state of the last
+// completed step, the reduction kernel sets the sticky status word, and from then on every launch returns at once - positions,
+// velocities, logs and the step counter stay at the last valid step until tmdnet_md_reset.  The per-atom kernel never writes the
+// status word (a block that saw it early would skip the restore); the reduction kernel, next in stream order, does.
+//
+// Kinetic energy per molecule: sum of 0.5 m v^2 at the full step, no floating-point atomics, fixed order - the two stages of
+// tn_virial.hip: grid (B, S), slices of at most 1 024 atoms on average, the slice sums added in slice order by a second kernel
+// when S > 1.  The terms are stored in the CALLER's atom order, which is the order of mstart..mend whenever those ranges are
+// valid; when they are not (Graph::counts[3]: unsorted batch, or molecules interleaved by the cell list), or without a graph
+// workspace, a slice is a range of all atoms filtered by `batch`.
+#include <string>
+
+#include "tmdnet_amd.h"
+#include "tn_common.h"
+#include "tn_md_math.h"
+#include "tn_model.h"
+
+namespace tn {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr size_t kHeaderBytes = 256;
+
+struct MdState {  // views into the caller's workspace
+  uint32_t* head;  // [0] step lo, [1] step hi, [2] status (sticky, 1 = an evaluation overflowed)
+  float* x_keep;   // [N, 3] positions at the last completed step
+  float* v_keep;   // [N, 3]
+  float* part;     // [N]    0.5 m v^2 per atom, caller's order
+  float* slices;   // [B, S] (S > 1 only)
+};
+
+struct MdArgs {
+  int N;
+  float* pos;
+  float* vel;
+  const float* forces;
+  float* forces_keep;
+  const float* hk;
+  const float* mass;
+  const float* sigma;
+  float dt, c1, c2;
+  uint64_t seed;
+  int thermostat;
+  const int* counts;  // the graph's counters, or NULL
+  MdState st;
+};
+
+inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
+
+int ke_slices(int64_t N, int64_t B) {
+  if (B <= 0 || N <= 1024 * B) return 1;
+  const int64_t s = (N + 1024 * B - 1) / (1024 * B);
+  return (int)(s > 256 ? 256 : s);
+}
+
+size_t md_bytes(int64_t N, int64_t B) {
+  const int S = ke_slices(N, B);
+  const size_t n = (size_t)(N > 0 ? N : 0);
+  size_t t = kHeaderBytes + 2 * align256(n * 3 * sizeof(float)) + align256(n * sizeof(float));
+  if (S > 1) t += align256((size_t)B * S * sizeof(float));
+  return t + 256;  // room to align the caller's pointer
+}
+
+MdState carve_md(void* ws, int64_t N, int64_t B) {
+  char* p = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(ws)));
+  const size_t n = (size_t)(N > 0 ? N : 0);
+  MdState st;
+  st.head = reinterpret_cast<uint32_t*>(p);
+  p += kHeaderBytes;
+  st.x_keep = reinterpret_cast<float*>(p);
+  p += align256(n * 3 * sizeof(float));
+  st.v_keep = reinterpret_cast<float*>(p);
+  p += align256(n * 3 * sizeof(float));
+  st.part = reinterpret_cast<float*>(p);
+  p += align256(n * sizeof(float));
+  st.slices = reinterpret_cast<float*>(p);
+  return st;
+}
+
+// one thread per atom.  CLOSE: B, O, kinetic term of the step that the evaluation before this launch belongs to; OPEN: save the
+// state, B, A of the next step.  MIDDLE = CLOSE then OPEN on the same registers, with the same force.
+template <bool CLOSE, bool OPEN>
+__global__ __launch_bounds__(kThreads) void k_md_atoms(MdArgs a) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= a.N) return;
+  if (a.st.head[2]) return;  // frozen since an earlier overflow
+  float x[3], v[3], f[3];
+  if (CLOSE && a.counts && a.counts[2]) {  // this evaluation overflowed: back to the last completed step
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      a.pos[i * 3 + d] = a.st.x_keep[i * 3 + d];
+      a.vel[i * 3 + d] = a.st.v_keep[i * 3 + d];
+    }
+    return;
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    v[d] = a.vel[i * 3 + d];
+    f[d] = a.forces[i * 3 + d];
+  }
+  const float hk = a.hk[i];
+  if (CLOSE) {
+    const uint64_t step = (uint64_t)a.st.head[0] | ((uint64_t)a.st.head[1] << 32);
+    a.st.part[i] = tn_md::close_step(v, f, hk, a.mass[i], a.thermostat, a.c1, a.c2, a.thermostat ? a.sigma[i] : 0.f, a.seed, step,
+                                     (uint32_t)i);
+    if (a.forces_keep)
+#pragma unroll
+      for (int d = 0; d < 3; ++d) a.forces_keep[i * 3 + d] = f[d];
+  }
+  if (OPEN) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      x[d] = a.pos[i * 3 + d];
+      a.st.x_keep[i * 3 + d] = x[d];
+      a.st.v_keep[i * 3 + d] = v[d];
+    }
+    tn_md::open_step(x, v, f, hk, a.dt);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) a.pos[i * 3 + d] = x[d];
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) a.vel[i * 3 + d] = v[d];
+}
+
+// sum over the block in a fixed order (lanes by the wave tree, waves in turn), result in every thread
+__device__ __forceinline__ float block_sum(float v, float* sh) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+// grid (B, S), after a closing launch: slice s of molecule m -> out[m * S + s] (S == 1: the log row itself).  Block (0, 0) also
+// keeps the books of the step: it latches an overflow into the status word, or copies the energies into the log row and
+// advances the step counter (plain stores from one vector lane; no other block of this launch reads the counter).
+__global__ __launch_bounds__(kThreads) void k_md_ke_reduce(MdState st, const int* __restrict__ counts, const int* __restrict__ mstart,
+                                                           const int* __restrict__ mend, int N, int B, int S,
+                                                           const int64_t* __restrict__ batch, const float* __restrict__ energy,
+                                                           float* __restrict__ epot_row, float* __restrict__ out) {
+  __shared__ float sh[4];
+  if (st.head[2]) return;
+  const int m = blockIdx.x, s = blockIdx.y;
+  const bool first = m == 0 && s == 0 && threadIdx.x == 0;
+  if (counts && counts[2]) {
+    if (first) st.head[2] = 1u;
+    return;
+  }
+  const bool filter = counts ? counts[3] != 0 : batch != nullptr;
+  int a = 0, b = N;
+  if (counts && !filter) {
+    a = mstart[m];
+    b = mend[m];
+  }
+  const int64_t len = b - a;
+  const int i0 = a + (int)(len * s / S), i1 = a + (int)(len * (s + 1) / S);
+  float v = 0.f;
+  for (int i = i0 + (int)threadIdx.x; i < i1; i += kThreads) {
+    if (filter && batch && batch[i] != m) continue;  // (no batch vector: one molecule)
+    v += st.part[i];
+  }
+  v = block_sum(v, sh);
+  if (threadIdx.x == 0) {
+    if (out) out[(int64_t)m * S + s] = v;
+    if (s == 0 && energy && epot_row) epot_row[m] = energy[m];
+  }
+  if (first) {
+    const uint64_t step = ((uint64_t)st.head[0] | ((uint64_t)st.head[1] << 32)) + 1;
+    st.head[0] = (uint32_t)step;
+    st.head[1] = (uint32_t)(step >> 32);
+  }
+}
+
+// one thread per molecule: the slice sums in slice order.  The status word is already latched by k_md_ke_reduce.
+__global__ __launch_bounds__(kThreads) void k_md_ke_finish(MdState st, const int* __restrict__ counts, int B, int S, float* __restrict__ ekin_row) {
+  const int m = blockIdx.x * kThreads + threadIdx.x;
+  if (m >= B || st.head[2] || (counts && counts[2])) return;
+  float v = 0.f;
+  for (int s = 0; s < S; ++s) v += st.slices[(int64_t)m * S + s];
+  ekin_row[m] = v;
+}
+
+__global__ void k_md_reset(MdState st, uint64_t step0) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    st.head[0] = (uint32_t)step0;
+    st.head[1] = (uint32_t)(step0 >> 32);
+    st.head[2] = 0u;
+  }
+}
+
+}  // namespace
+
+}  // namespace tn
+
+using namespace tn;
+
+extern "C" {
+
+int tmdnet_md_workspace_bytes(int64_t n_atoms, int64_t n_mol, size_t* bytes) {
+  if (!bytes || n_atoms < 0 || n_mol < 0 || n_atoms > INT32_MAX / 4) return TMDNET_ERR_INVALID;
+  *bytes = md_bytes(n_atoms, n_mol);
+  return TMDNET_OK;
+}
+
+int tmdnet_md_reset(void* stream, void* md_ws, uint64_t step0) {
+  if (!md_ws) return TMDNET_ERR_INVALID;
+  hipLaunchKernelGGL(k_md_reset, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), carve_md(md_ws, 0, 0), step0);
+  return hipGetLastError() == hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
+}
+
+int tmdnet_md_advance(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, int64_t n_atoms, int64_t n_mol, int32_t phase,
+                      float* pos, float* vel, const float* forces, const float* energy, const float* hk, const float* mass,
+                      const float* sigma, float dt, float c1, float c2, uint64_t seed, const int64_t* batch, float* forces_keep,
+                      float* epot_log_row, float* ekin_log_row) {
+  if (!md_ws || !pos || !vel || !forces || !hk || n_atoms < 0 || n_atoms > INT32_MAX / 4 || n_mol < 1) return TMDNET_ERR_INVALID;
+  if (phase != TMDNET_MD_OPEN && phase != TMDNET_MD_MIDDLE && phase != TMDNET_MD_CLOSE) return TMDNET_ERR_INVALID;
+  if (graph_ws && !m) return TMDNET_ERR_INVALID;
+  if (phase != TMDNET_MD_OPEN && !mass) return TMDNET_ERR_INVALID;
+  if (n_atoms == 0) return TMDNET_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int N = (int)n_atoms, B = (int)n_mol;
+  MdArgs a;
+  a.N = N;
+  a.pos = pos;
+  a.vel = vel;
+  a.forces = forces;
+  a.forces_keep = forces_keep;
+  a.hk = hk;
+  a.mass = mass;
+  a.sigma = sigma;
+  a.dt = dt;
+  a.c1 = c1;
+  a.c2 = c2;
+  a.seed = seed;
+  a.thermostat = sigma != nullptr;
+  a.counts = nullptr;
+  a.st = carve_md(md_ws, n_atoms, n_mol);
+  const int* mstart = nullptr;
+  const int* mend = nullptr;
+  if (graph_ws) {
+    const Graph g = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr);
+    a.counts = g.counts;
+    mstart = g.mstart;
+    mend = g.mend;
+  }
+  const dim3 grid((N + kThreads - 1) / kThreads), block(kThreads);
+  if (phase == TMDNET_MD_OPEN)
+    hipLaunchKernelGGL((k_md_atoms<false, true>), grid, block, 0, s, a);
+  else if (phase == TMDNET_MD_MIDDLE)
+    hipLaunchKernelGGL((k_md_atoms<true, true>), grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL((k_md_atoms<true, false>), grid, block, 0, s, a);
+  if (phase != TMDNET_MD_OPEN) {
+    const int S = ke_slices(n_atoms, n_mol);
+    float* out = S == 1 ? ekin_log_row : a.st.slices;
+    hipLaunchKernelGGL(k_md_ke_reduce, dim3(B, S), block, 0, s, a.st, a.counts, mstart, mend, N, B, S, batch, energy, epot_log_row, out);
+    if (S > 1 && ekin_log_row)
+      hipLaunchKernelGGL(k_md_ke_finish, dim3((B + kThreads - 1) / kThreads), block, 0, s, a.st, a.counts, B, S, ekin_log_row);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_md_advance: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
+  return TMDNET_OK;
+}
+
+int tmdnet_md_status(void* stream, void* md_ws, uint64_t host[2]) {
+  if (!md_ws || !host) return TMDNET_ERR_INVALID;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  uint32_t head[3] = {0, 0, 0};
+  if (hipMemcpyAsync(head, carve_md(md_ws, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
+  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
+  host[0] = (uint64_t)head[0] | ((uint64_t)head[1] << 32);
+  host[1] = head[2];
+  return head[2] ? TMDNET_ERR_OVERFLOW : TMDNET_OK;
+}
+
+}  // extern "C"

@@ -118,6 +118,11 @@ def lib():
     L.tmdnet_loss_param_grads.argtypes = [vp, vp, vp, vp, sz, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
     L.tmdnet_hvp_debug_tensor.argtypes = [vp, vp, C.c_char_p, vp, i64]
     L.tmdnet_set_output_head.argtypes = [vp, i32]
+    u64 = C.c_uint64
+    L.tmdnet_md_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
+    L.tmdnet_md_reset.argtypes = [vp, vp, u64]
+    L.tmdnet_md_advance.argtypes = [vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, u64, vp, vp, vp, vp]
+    L.tmdnet_md_status.argtypes = [vp, vp, C.POINTER(u64)]
     for name in declared_symbols():
         fn = getattr(L, name)
         if fn.restype is C.c_int:

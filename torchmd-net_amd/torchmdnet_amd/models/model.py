@@ -1366,6 +1366,48 @@ class TorchMD_Net(nn.Module):
             replay.virial = s_w  # static buffer the graph writes W into
         return replay
 
+    def capture_md(self, z: Tensor, pos: Tensor, vel: Tensor, masses: Tensor, dt: float, batch: Optional[Tensor] = None,
+                   box: Optional[Tensor] = None, q: Optional[Tensor] = None, num_systems: Optional[int] = None,
+                   steps_per_replay: int = 10, force_scale: float = 1.0, thermostat: Optional[dict] = None, warmup: int = 3,
+                   atom_weights=None, halo_exchange=None):
+        """Capture ``steps_per_replay`` full MD steps into ONE HIP graph (needs ``static_shapes=True``): per step half-kick, drift,
+        neighbour list + energy + forces, half-kick, the Langevin O step when ``thermostat=dict(friction=, kT=, seed=)`` is given, and
+        the energy bookkeeping, with the integrator as HIP kernels between the evaluations (``tmdnet_md_advance``) - no host work
+        between steps.  ``masses`` [N]; per atom hk = dt force_scale / (2 m) and sigma = sqrt(kT force_scale / m), so ``force_scale``
+        converts force / mass into length / time^2: 9.648533e-3 for eV, Angstrom, amu and fs (``md.FORCE_SCALE_EV_A_AMU_FS``).
+        Positions are never wrapped.  Works for every architecture ``capture`` serves and for a batch of independent replicas.
+        Returns a ``torchmdnet_amd.md.DeviceMD``: ``md(n)`` replays n times; ``md.pos / vel / forces``, ``md.epot / ekin`` [K,B],
+        ``md.steps_done``, ``md.check()``, ``md.reset(pos, vel, step)``.  Inputs are staged and kept alive as in ``capture``; a ``box``
+        that needs no conversion stays the caller's object.  ``atom_weights`` / ``halo_exchange`` are accepted only to be refused."""
+        from torchmdnet_amd.md import DeviceMD
+
+        if not getattr(self.representation_model, "static_shapes", False):
+            raise RuntimeError("capture_md() needs a model created with static_shapes=True")
+        if self._head_kind() != _C.HEAD_SCALAR:
+            raise NotImplementedError(f"capture_md has no HIP path with output_model {type(self.output_model).__name__}: molecular "
+                                      "dynamics needs energies and their forces (scalar head)")
+        if self.parameter_gradients:
+            raise NotImplementedError("capture_md has no HIP path with parameter_gradients=True (a training model); create the model "
+                                      "without it")
+        if atom_weights is not None or halo_exchange is not None:
+            raise NotImplementedError("capture_md has no HIP path with atom weights or the halo exchange (domain decomposition)")
+        if int(steps_per_replay) < 1:
+            raise ValueError(f"steps_per_replay must be at least 1, got {steps_per_replay}")
+        _require_cuda(pos, "capture_md")
+        if pos.dtype != torch.float32:
+            raise NotImplementedError("torchmdnet_amd computes in fp32; cast positions to float32")
+        batch = torch.zeros_like(z) if batch is None else batch
+        n_mol = int(num_systems) if num_systems is not None else int(batch.max().item()) + 1
+        rm = self.representation_model
+        if box is None and rm.distance.use_periodic:
+            box = rm.distance.box
+        dev = pos.device  # staged as in capture(): the graph records raw pointers, conversions must not be temporaries
+        z = z.detach().to(device=dev, dtype=torch.long).contiguous()
+        batch = batch.detach().to(device=dev, dtype=torch.long).contiguous()
+        box = None if box is None else box.detach().to(device=dev, dtype=torch.float32).contiguous()
+        q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).contiguous()
+        return DeviceMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup)
+
     def debug_tensor(self, name: str, shape) -> Tensor:
         L = _C.lib()
         st = self._engine
