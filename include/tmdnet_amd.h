@@ -458,8 +458,47 @@ int tmdnet_md_advance(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws
                       const float* sigma, float dt, float c1, float c2, uint64_t seed, const int64_t* batch, float* forces_keep,
                       float* epot_log_row, float* ekin_log_row);
 /* host[0] = steps completed (the device counter), host[1] = status (1: an evaluation overflowed; the state is that of step
- * host[0]).  Synchronises the stream.  Returns TMDNET_ERR_OVERFLOW when the status is set. */
+ * host[0].  2: a barostat move was unusable, see tmdnet_md_barostat; step host[0] is complete but for that move).  Synchronises the
+ * stream.  Returns TMDNET_ERR_OVERFLOW for status 1 and TMDNET_ERR_STATE for status 2. */
 int tmdnet_md_status(void* stream, void* md_ws, uint64_t host[2]);
+
+/* ---- Barostat of the device-resident MD loop (csrc/tn_md.hip; additive exports, the ABI revision stays 10) --------------------
+ * Isotropic stochastic cell rescaling (Bernetti and Bussi, J. Chem. Phys. 153, 114107, 2020), one barostat per molecule (replica),
+ * first order in the log-volume.  After the closing half of a step (tmdnet_md_advance with TMDNET_MD_CLOSE), per molecule m, in fp64:
+ *     V  = |det box_m|                                  K = ekin_row[m] / force_scale
+ *     P  = (2 K + W_m[0][0] + W_m[1][1] + W_m[2][2]) / (3 V)         (W of tmdnet_energy_forces_virial: tr W = -3 V dE/dV)
+ *     a  = compressibility dt / tau                      d = -a (P0 - P) + sqrt(2 kT a / V) xi
+ *     mu = exp(d / 3), nu = exp(-d / 3), both rounded to fp32 once
+ * then box_m <- box_m mu (all nine entries: any triclinic box), x <- x mu and v <- v nu for the atoms of m, each ONE rounded fp32
+ * product under the rounding contract above.  kT = 0 is weak coupling (no noise).  Units: pressure in E / length^3, compressibility
+ * in length^3 / E, kT in E (1 bar = 6.2415091e-7 eV / Angstrom^3).  The forces are NOT evaluated again after the scaling: the next
+ * opening kick uses F(x) of before the move (first-order splitting).
+ * Noise: xi = xi_x of the Box-Muller map above on one Philox4x32-10 call, key = `seed`, counter = (step low, step high, molecule,
+ * 1) with `step` the value the O step of this MD step used; counter word 3 keeps the stream apart from the atoms' (0).
+ * Enqueues two launches: one block that computes every molecule's move and, when all are usable, writes the factors, scales the
+ * boxes and fills the log rows; then one thread per atom that scales x and v and, with open_next != 0, saves the scaled state and
+ * runs B, A of the next step on it (what TMDNET_MD_OPEN does).  A captured step with a barostat is therefore
+ *     evaluation with the virial;  tmdnet_md_advance(TMDNET_MD_CLOSE);  tmdnet_md_barostat(open_next = another step follows)
+ * after one TMDNET_MD_OPEN at the start of the replay; TMDNET_MD_MIDDLE is not used (the kinetic energy of the closing half has to
+ * be reduced before the move).
+ *   m, graph_ws   as in tmdnet_md_advance: when the evaluation overflowed, nothing is written (the CLOSE launch before has latched
+ *                 status 1, so the box is always that of the last completed step).  graph_ws == NULL (m may be NULL): no such test.
+ *   baro_ws       tmdnet_md_barostat_workspace_bytes(n_mol) bytes of scratch: the factors mu | nu of every molecule.
+ *   forces, hk, dt   read with open_next only.
+ *   batch         [n_atoms] int64 or NULL (one molecule), as in tmdnet_md_advance.
+ *   box, box_mode    2: [n_mol, 3, 3], one box per molecule; 1: one [3, 3] box, n_mol == 1 only.  Scaled in place.
+ *   virial        [n_mol, 3, 3] of the evaluation of this step;  ekin_row   [n_mol], the ekin_log_row of the CLOSE launch.
+ *   volume_log_row, pressure_log_row, scale_log_row   [n_mol] each or NULL: V before the move, P, and mu as fp32.
+ * A move is unusable when V = 0 or anything on the way to mu, nu is not finite (a NaN in the virial): the status word becomes 2,
+ * box, pos, vel and the log rows keep their bits, and every later launch returns at once until tmdnet_md_reset.
+ * TMDNET_ERR_INVALID: box_mode 0, box_mode 1 with n_mol > 1, tau <= 0, compressibility <= 0, kT < 0, force_scale <= 0, or a NULL
+ * box / virial / ekin_row / workspace. */
+int tmdnet_md_barostat_workspace_bytes(int64_t n_mol, size_t* bytes);
+int tmdnet_md_barostat(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, void* baro_ws, int64_t n_atoms, int64_t n_mol,
+                       int32_t open_next, float* pos, float* vel, const float* forces, const float* hk, float dt, const int64_t* batch,
+                       float* box, int32_t box_mode, const float* virial, const float* ekin_row, double pressure, double kT,
+                       double compressibility, double tau, double force_scale, uint64_t seed, float* volume_log_row,
+                       float* pressure_log_row, float* scale_log_row);
 
 #ifdef __cplusplus
 }

@@ -42,7 +42,7 @@ constexpr int kThreads = 256;
 constexpr size_t kHeaderBytes = 256;
 
 struct MdState {  // views into the caller's workspace
-  uint32_t* head;  // [0] step lo, [1] step hi, [2] status (sticky, 1 = an evaluation overflowed)
+  uint32_t* head;  // [0] step lo, [1] step hi, [2] status (sticky, 1 = an evaluation overflowed, 2 = an unusable barostat move)
   float* x_keep;   // [N, 3] positions at the last completed step
   float* v_keep;   // [N, 3]
   float* part;     // [N]    0.5 m v^2 per atom, caller's order
@@ -207,6 +207,106 @@ __global__ void k_md_reset(MdState st, uint64_t step0) {
   }
 }
 
+// ---- barostat: isotropic stochastic cell rescaling, one per molecule (tn_md_math.h: baro_move) ------------------------------------
+struct BaroArgs {
+  int B;
+  float* box;           // [B, 3, 3] (box_mode 1: B == 1, [3, 3])
+  const float* virial;  // [B, 3, 3]
+  const float* ekin;    // [B]
+  double P0, kT, a, force_scale;
+  uint64_t seed;
+  float* factors;  // [2, B]: mu32 | nu32
+  float* volume_row;
+  float* pressure_row;
+  float* scale_row;
+  const int* counts;  // the graph's counters, or NULL
+  MdState st;
+};
+
+// ONE block, after the closing launch and its kinetic-energy reduction (which has latched an overflow and advanced the step
+// counter).  Pass 1: every molecule's move, and whether any of them is unusable; pass 2, only when none is: the factors for
+// k_md_scale, the box and the log rows.  Otherwise the status word becomes 2 and nothing else is written.  A molecule belongs to
+// one thread in both passes, and the move is a function of what pass 1 read, so pass 2 evaluates it again instead of keeping it.
+__global__ __launch_bounds__(kThreads) void k_md_baro(BaroArgs a) {
+  __shared__ int bad;
+  if (a.st.head[2]) return;                // frozen
+  if (a.counts && a.counts[2]) return;     // (k_md_ke_reduce has latched it: the box stays that of the last completed step)
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  // the counter was advanced by the reduction: the O step of this MD step used the value before
+  const uint64_t step = ((uint64_t)a.st.head[0] | ((uint64_t)a.st.head[1] << 32)) - 1;
+  int flag = 0;
+  double V, P;
+  float mu, nu;
+  for (int m = threadIdx.x; m < a.B; m += kThreads)
+    flag |= tn_md::baro_move(a.box + 9 * (int64_t)m, a.virial + 9 * (int64_t)m, a.ekin[m], a.force_scale, a.P0, a.kT, a.a, a.seed, step,
+                             (uint32_t)m, &V, &P, &mu, &nu);
+  if (flag) bad = 1;  // (every writer stores the same value)
+  __syncthreads();
+  if (bad) {
+    if (threadIdx.x == 0) a.st.head[2] = 2u;
+    return;
+  }
+  for (int m = threadIdx.x; m < a.B; m += kThreads) {
+    float* box = a.box + 9 * (int64_t)m;
+    tn_md::baro_move(box, a.virial + 9 * (int64_t)m, a.ekin[m], a.force_scale, a.P0, a.kT, a.a, a.seed, step, (uint32_t)m, &V, &P, &mu, &nu);
+    a.factors[m] = mu;
+    a.factors[a.B + m] = nu;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) tn_md::scale3(box + 3 * r, mu);
+    if (a.volume_row) a.volume_row[m] = (float)V;
+    if (a.pressure_row) a.pressure_row[m] = (float)P;
+    if (a.scale_row) a.scale_row[m] = mu;
+  }
+}
+
+struct ScaleArgs {
+  int N, B;
+  float* pos;
+  float* vel;
+  const float* forces;
+  const float* hk;
+  float dt;
+  const int64_t* batch;
+  const float* factors;
+  MdState st;
+};
+
+// one thread per atom, after k_md_baro: x <- x mu, v <- v nu with the factors of the atom's molecule.  OPEN: then the opening half
+// of the next step on the same registers - the saved state is the scaled one, consistent with the new box.
+template <bool OPEN>
+__global__ __launch_bounds__(kThreads) void k_md_scale(ScaleArgs a) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= a.N) return;
+  if (a.st.head[2]) return;  // overflow (1) or an unusable move (2): k_md_baro wrote no factors
+  const int64_t m = a.batch ? a.batch[i] : 0;
+  if (m < 0 || m >= a.B) return;
+  const float mu = a.factors[m], nu = a.factors[a.B + m];
+  float x[3], v[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    x[d] = a.pos[i * 3 + d];
+    v[d] = a.vel[i * 3 + d];
+  }
+  tn_md::scale3(x, mu);
+  tn_md::scale3(v, nu);
+  if (OPEN) {
+    float f[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      f[d] = a.forces[i * 3 + d];
+      a.st.x_keep[i * 3 + d] = x[d];
+      a.st.v_keep[i * 3 + d] = v[d];
+    }
+    tn_md::open_step(x, v, f, a.hk[i], a.dt);
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    a.pos[i * 3 + d] = x[d];
+    a.vel[i * 3 + d] = v[d];
+  }
+}
+
 }  // namespace
 
 }  // namespace tn
@@ -281,6 +381,68 @@ int tmdnet_md_advance(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws
   return TMDNET_OK;
 }
 
+int tmdnet_md_barostat_workspace_bytes(int64_t n_mol, size_t* bytes) {
+  if (!bytes || n_mol < 0 || n_mol > INT32_MAX / 16) return TMDNET_ERR_INVALID;
+  *bytes = align256((size_t)n_mol * 2 * sizeof(float)) + 256;  // mu32 | nu32, and room to align the caller's pointer
+  return TMDNET_OK;
+}
+
+int tmdnet_md_barostat(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, void* baro_ws, int64_t n_atoms, int64_t n_mol,
+                       int32_t open_next, float* pos, float* vel, const float* forces, const float* hk, float dt, const int64_t* batch,
+                       float* box, int32_t box_mode, const float* virial, const float* ekin_row, double pressure, double kT,
+                       double compressibility, double tau, double force_scale, uint64_t seed, float* volume_log_row,
+                       float* pressure_log_row, float* scale_log_row) {
+  if (!md_ws || !baro_ws || !pos || !vel || n_atoms < 0 || n_atoms > INT32_MAX / 4 || n_mol < 1 || n_mol > INT32_MAX / 16)
+    return TMDNET_ERR_INVALID;
+  if (!box || !virial || !ekin_row) return TMDNET_ERR_INVALID;
+  if (box_mode != 1 && box_mode != 2) return TMDNET_ERR_INVALID;
+  if (box_mode == 1 && n_mol != 1) return TMDNET_ERR_INVALID;  // one barostat per molecule: a shared box has no single pressure
+  if (!(tau > 0.0) || !(compressibility > 0.0) || !(kT >= 0.0) || !(force_scale > 0.0)) return TMDNET_ERR_INVALID;
+  if (graph_ws && !m) return TMDNET_ERR_INVALID;
+  if (open_next && (!forces || !hk)) return TMDNET_ERR_INVALID;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int N = (int)n_atoms, B = (int)n_mol;
+  BaroArgs b;
+  b.B = B;
+  b.box = box;
+  b.virial = virial;
+  b.ekin = ekin_row;
+  b.P0 = pressure;
+  b.kT = kT;
+  b.a = compressibility * (double)dt / tau;
+  b.force_scale = force_scale;
+  b.seed = seed;
+  b.factors = reinterpret_cast<float*>(align256(reinterpret_cast<size_t>(baro_ws)));
+  b.volume_row = volume_log_row;
+  b.pressure_row = pressure_log_row;
+  b.scale_row = scale_log_row;
+  b.counts = nullptr;
+  b.st = carve_md(md_ws, n_atoms, n_mol);
+  if (graph_ws) b.counts = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr).counts;
+  hipLaunchKernelGGL(k_md_baro, dim3(1), dim3(kThreads), 0, s, b);
+  if (N > 0) {
+    ScaleArgs a;
+    a.N = N;
+    a.B = B;
+    a.pos = pos;
+    a.vel = vel;
+    a.forces = forces;
+    a.hk = hk;
+    a.dt = dt;
+    a.batch = batch;
+    a.factors = b.factors;
+    a.st = b.st;
+    const dim3 grid((N + kThreads - 1) / kThreads), block(kThreads);
+    if (open_next)
+      hipLaunchKernelGGL((k_md_scale<true>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((k_md_scale<false>), grid, block, 0, s, a);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_md_barostat: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
+  return TMDNET_OK;
+}
+
 int tmdnet_md_status(void* stream, void* md_ws, uint64_t host[2]) {
   if (!md_ws || !host) return TMDNET_ERR_INVALID;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -289,7 +451,7 @@ int tmdnet_md_status(void* stream, void* md_ws, uint64_t host[2]) {
   if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
   host[0] = (uint64_t)head[0] | ((uint64_t)head[1] << 32);
   host[1] = head[2];
-  return head[2] ? TMDNET_ERR_OVERFLOW : TMDNET_OK;
+  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
 }
 
 }  // extern "C"

@@ -119,4 +119,54 @@ MD_FN void open_step(float x[3], float v[3], const float f[3], float hk, float d
   }
 }
 
+// ---- isotropic stochastic cell rescaling (Bernetti, Bussi: J. Chem. Phys. 153, 114107, 2020), one barostat per molecule ---------
+// First order in the log-volume: d = -a (P0 - P) + sqrt(2 kT a / V) xi with a = compressibility dt / tau; the box and the positions
+// are scaled by mu = exp(d / 3), the velocities by nu = exp(-d / 3).  Everything up to mu and nu is fp64, in the order written; the
+// two factors are rounded to fp32 once, and every scaling is then ONE md_mul, subject to the rounding contract above.
+
+// V = |det box| of a row-major 3 x 3 box, fp32 entries widened
+MD_FN double box_volume(const float b[9]) {
+  const double b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3], b4 = b[4], b5 = b[5], b6 = b[6], b7 = b[7], b8 = b[8];
+  return fabs((b0 * (b4 * b8 - b5 * b7) - b1 * (b3 * b8 - b5 * b6)) + b2 * (b3 * b7 - b4 * b6));
+}
+
+// P = (2 K + tr W) / (3 V): K the kinetic energy in the unit of the potential energy, W = -dE/d eps (tr W = -3 V dE/dV)
+MD_FN double baro_pressure(double V, double K, const float W[9]) {
+  return (2.0 * K + (((double)W[0] + (double)W[4]) + (double)W[8])) / (3.0 * V);
+}
+
+// the noise of molecule `mol` in the barostat move that follows `step` completed steps: xi[0] of normals3 on one Philox call,
+// key = the 64-bit seed, counter = (step lo, step hi, mol, 1) - word 3 keeps the stream apart from the atoms' (langevin_noise: 0)
+MD_FN double baro_noise(uint64_t seed, uint64_t step, uint32_t mol) {
+  const uint32_t c[4] = {(uint32_t)step, (uint32_t)(step >> 32), mol, 1u};
+  const uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+  uint32_t w[4];
+  float xi[3];
+  philox4x32_10(c, k, w);
+  normals3(w, xi);
+  return (double)xi[0];
+}
+
+// One barostat move of one molecule.  ekin = sum of 0.5 m v^2 in the unit of m v^2 (the kinetic-energy log row).  Writes the volume
+// before the move, the pressure and the two fp32 factors; returns 0 when the move is usable, 1 when it is not (V = 0, or anything
+// not finite on the way: a NaN in the virial, a box about to vanish or explode).  kT = 0: no Philox call, weak coupling.
+MD_FN int baro_move(const float box[9], const float W[9], float ekin, double force_scale, double P0, double kT, double a,
+                    uint64_t seed, uint64_t step, uint32_t mol, double* V_out, double* P_out, float* mu32, float* nu32) {
+  const double V = box_volume(box);
+  const double P = baro_pressure(V, (double)ekin / force_scale, W);
+  double d = -a * (P0 - P);
+  if (kT > 0.0) d = d + sqrt(2.0 * kT * a / V) * baro_noise(seed, step, mol);
+  const double mu = exp(d / 3.0), nu = exp(-d / 3.0);
+  *V_out = V;
+  *P_out = P;
+  *mu32 = (float)mu;
+  *nu32 = (float)nu;
+  return !(V > 0.0) || !isfinite(d) || !isfinite(*mu32) || !isfinite(*nu32) || !(*mu32 > 0.f) || !(*nu32 > 0.f);
+}
+
+// scale the nine entries of a box, or the position / velocity of one atom: one rounded product each
+MD_FN void scale3(float x[3], float s) {
+  for (int d = 0; d < 3; ++d) x[d] = md_mul(x[d], s);
+}
+
 }  // namespace tn_md

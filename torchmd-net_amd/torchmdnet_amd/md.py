@@ -2,8 +2,9 @@
 
 One step is half-kick, drift, neighbour list + energy + forces, half-kick, optional Langevin O step and the energy bookkeeping; the
 integrator runs as HIP kernels (csrc/tn_md.hip, ``tmdnet_md_advance``) inside the captured graph, between the evaluations, so
-nothing is issued from the host between two steps.  The scheme, its rounding contract and the noise generator are documented
-with the C entries in include/tmdnet_amd.h and in DESIGN.md section 13."""
+nothing is issued from the host between two steps.  With ``barostat=`` every step ends with an isotropic stochastic-cell-rescaling
+move per molecule (``tmdnet_md_barostat``): box, positions and velocities are scaled inside the graph (NPT).  The scheme, its
+rounding contract and the noise generator are documented with the C entries in include/tmdnet_amd.h and in DESIGN.md section 13."""
 import ctypes as C
 import math
 from typing import Optional
@@ -18,6 +19,33 @@ MD_OPEN, MD_MIDDLE, MD_CLOSE = 0, 1, 2  # TMDNET_MD_* of include/tmdnet_amd.h
 
 #: eV / (Angstrom amu) in Angstrom / fs^2: ``force_scale`` for energies in eV, lengths in Angstrom, masses in amu and dt in fs
 FORCE_SCALE_EV_A_AMU_FS = 9.648533e-3
+#: 1 bar in eV / Angstrom^3: the barostat's ``pressure`` (and 1 / ``compressibility``) for energies in eV and lengths in Angstrom
+BAR_IN_EV_PER_A3 = 6.2415091e-7
+
+_BAROSTAT_KEYS = ("pressure", "tau", "compressibility", "kT", "seed")
+
+
+def parse_barostat(barostat, thermostat):
+    """``barostat=dict(pressure=, tau=, compressibility=, kT=, seed=)`` -> the same with every key present.  ``kT`` defaults to the
+    thermostat's and is required without one; ``seed`` defaults to the thermostat's seed, or 0.  Raises ValueError."""
+    b = dict(barostat)
+    unknown = set(b) - set(_BAROSTAT_KEYS)
+    if unknown:
+        raise ValueError(f"barostat: unknown keys {sorted(unknown)} ({', '.join(_BAROSTAT_KEYS)})")
+    for key in ("pressure", "tau", "compressibility"):
+        if key not in b:
+            raise ValueError(f"barostat: '{key}' is required")
+    th = thermostat or {}
+    if "kT" not in b:
+        if "kT" not in th:
+            raise ValueError("barostat: 'kT' is required when there is no thermostat to take it from (0: weak coupling, no noise)")
+        b["kT"] = th["kT"]
+    b.setdefault("seed", th.get("seed", 0))
+    out = {k: float(b[k]) for k in ("pressure", "tau", "compressibility", "kT")}
+    out["seed"] = int(b["seed"]) & (2 ** 64 - 1)
+    if not out["tau"] > 0 or not out["compressibility"] > 0 or not out["kT"] >= 0:
+        raise ValueError(f"barostat: tau and compressibility must be positive and kT must not be negative, got {out}")
+    return out
 
 
 class DeviceMD:
@@ -25,9 +53,12 @@ class DeviceMD:
     each) and returns ``md``; nothing is read back.  Static tensors, rewritten by every replay: ``pos``, ``vel``, ``forces``
     [N,3] at the last completed step, ``epot`` and ``ekin`` [K,B] of the last replay's steps (``ekin`` = sum of 0.5 m v^2 in the
     unit of m v^2: divide by ``force_scale`` for the unit of ``epot``).  ``steps_done`` counts on the host; ``check()`` reads the
-    device (one synchronisation)."""
+    device (one synchronisation).  With a barostat: ``box`` is the static box the graph reads AND writes (the caller's own object
+    when it needed no conversion), and ``volume`` (before the move), ``pressure`` and ``scale`` (the fp32 factor mu) [K,B] are the
+    barostat's logs of the last replay's steps; ``forces`` stay the forces of the last evaluation, at the positions before the move."""
 
-    def __init__(self, model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup):
+    def __init__(self, model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
+                 barostat=None):
         L = _C.lib()
         dev = pos.device
         n = int(z.shape[0])
@@ -58,6 +89,13 @@ class DeviceMD:
             self.sigma = torch.sqrt(float(self.thermostat["kT"]) * self.force_scale / m64).to(torch.float32).contiguous()
         self.epot = torch.zeros((K, n_mol), dtype=torch.float32, device=dev)
         self.ekin = torch.zeros((K, n_mol), dtype=torch.float32, device=dev)
+        self.barostat = None if barostat is None else parse_barostat(barostat, self.thermostat)
+        self.box = box
+        if self.barostat is not None:
+            self.volume, self.pressure, self.scale = (torch.zeros((K, n_mol), dtype=torch.float32, device=dev) for _ in range(3))
+            nbytes = C.c_size_t(0)
+            L.tmdnet_md_barostat_workspace_bytes(n_mol, C.byref(nbytes))
+            self._baro_ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
         nbytes = C.c_size_t(0)
         L.tmdnet_md_workspace_bytes(n, n_mol, C.byref(nbytes))
         self._ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
@@ -67,7 +105,7 @@ class DeviceMD:
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
                 for _ in range(max(warmup, 1)):  # uploads parameters, sizes the workspaces, checks overflow
-                    _, f0 = self._evaluate()
+                    f0 = self._evaluate()[1]
                 self.forces = f0.clone()  # forces at the initial positions: what the first OPEN launch reads
                 L.tmdnet_md_reset(_stream_ptr(dev), _ptr(self._ws), 0)
             torch.cuda.current_stream(dev).wait_stream(side)
@@ -76,14 +114,19 @@ class DeviceMD:
             with torch.cuda.graph(self.graph):
                 self._advance(MD_OPEN, self.forces, None, 0)
                 for k in range(K):
-                    e, f = self._evaluate()
-                    self._step_outputs.append((e, f))
-                    self._advance(MD_MIDDLE if k + 1 < K else MD_CLOSE, f, e, k)
+                    out = self._evaluate()
+                    self._step_outputs.append(out)
+                    if self.barostat is None:
+                        self._advance(MD_MIDDLE if k + 1 < K else MD_CLOSE, out[1], out[0], k)
+                    else:  # the kinetic energy of the closing half is reduced before the move: CLOSE, then scale (and open)
+                        self._advance(MD_CLOSE, out[1], out[0], k)
+                        self._barostat_move(k + 1 < K, out[1], out[2], k)
         self._engine, self._generation = model._engine, model._engine.generation
 
     def _evaluate(self):
         z, batch, box, q = self.inputs
-        return self._model.energy_and_forces(z, self.pos, batch, box, q, self.n_mol, want_forces=True)
+        return self._model.energy_and_forces(z, self.pos, batch, box, q, self.n_mol, want_forces=True,
+                                             want_virial=self.barostat is not None)
 
     def _advance(self, phase, forces, energy, k):
         st = self._model._engine
@@ -94,6 +137,18 @@ class DeviceMD:
                                         None if phase == MD_OPEN else _ptr(self.forces), _ptr(self.epot[k]), _ptr(self.ekin[k]))
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_md_advance: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
+
+    def _barostat_move(self, open_next, forces, virial, k):
+        st = self._model._engine
+        dev = self.pos.device
+        b = self.barostat
+        rc = _C.lib().tmdnet_md_barostat(st.handle, _stream_ptr(dev), _ptr(st.graph_ws), _ptr(self._ws), _ptr(self._baro_ws),
+                                         self.n_atoms, self.n_mol, int(open_next), _ptr(self.pos), _ptr(self.vel), _ptr(forces),
+                                         _ptr(self.hk), self.dt, _ptr(self.inputs[1]), _ptr(self.box), 1 if self.box.dim() == 2 else 2,
+                                         _ptr(virial), _ptr(self.ekin[k]), b["pressure"], b["kT"], b["compressibility"], b["tau"],
+                                         self.force_scale, b["seed"], _ptr(self.volume[k]), _ptr(self.pressure[k]), _ptr(self.scale[k]))
+        if rc != _C.OK:
+            raise RuntimeError(f"tmdnet_md_barostat: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
 
     def _check_fresh(self):
         # the graph holds raw pointers into the engine's parameter block and workspaces (TorchMD_Net.capture's replay)
@@ -109,8 +164,10 @@ class DeviceMD:
 
     def check(self) -> int:
         """Read the device's step counter and status (one synchronisation).  Raises the reference's overflow RuntimeError when an
-        evaluation found more neighbours than ``max_num_neighbors`` allows: ``pos`` / ``vel`` / ``forces`` and the counter are
-        then those of the last valid step, and replays change nothing until ``reset``.  Returns the step counter."""
+        evaluation found more neighbours than ``max_num_neighbors`` allows: ``pos`` / ``vel`` / ``forces`` (and ``box``) and the
+        counter are then those of the last valid step, and replays change nothing until ``reset``.  Raises a RuntimeError naming
+        the barostat when one of its moves was unusable (zero volume, or a NaN from the virial): the state is frozen before that
+        move.  Returns the step counter."""
         host = (C.c_uint64 * 2)()
         dev = self.pos.device
         with torch.cuda.device(dev):
@@ -119,20 +176,28 @@ class DeviceMD:
             raise RuntimeError("Found num_pairs > max_num_pairs, please increase max_num_pairs "
                                f"(max_num_neighbors={self._model.representation_model.max_num_neighbors}; the MD state is frozen at "
                                f"step {int(host[0])})")
+        if int(host[1]) == 2:
+            raise RuntimeError(f"barostat: the move after step {int(host[0])} was not finite (zero volume, or a NaN in the virial or "
+                               "the kinetic energy); the MD state is frozen before that move")
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_md_status failed (code {rc})")
         return int(host[0])
 
-    def reset(self, pos: Optional[Tensor] = None, vel: Optional[Tensor] = None, step: int = 0):
+    def reset(self, pos: Optional[Tensor] = None, vel: Optional[Tensor] = None, step: int = 0, box: Optional[Tensor] = None):
         """New positions and / or velocities (copied into the static buffers), forces evaluated there, status cleared, device step
-        counter and ``steps_done`` set to ``step`` (the Langevin noise is a function of (seed, step, atom))."""
+        counter and ``steps_done`` set to ``step`` (the Langevin noise is a function of (seed, step, atom)).  ``box`` is copied into
+        the static box (a barostat has scaled it since the capture)."""
         self._check_fresh()
         dev = self.pos.device
+        if box is not None:
+            if self.box is None:
+                raise ValueError("reset(box=...): this loop was captured without a box")
+            self.box.copy_(box.detach().to(device=dev, dtype=torch.float32).reshape(self.box.shape))
         if pos is not None:
             self.pos.copy_(pos.detach().to(device=dev, dtype=torch.float32))
         if vel is not None:
             self.vel.copy_(vel.detach().to(device=dev, dtype=torch.float32))
-        _, f = self._evaluate()  # raises when these positions overflow
+        f = self._evaluate()[1]  # raises when these positions overflow
         self.forces.copy_(f)
         with torch.cuda.device(dev):
             _C.lib().tmdnet_md_reset(_stream_ptr(dev), _ptr(self._ws), int(step))

@@ -1369,7 +1369,7 @@ class TorchMD_Net(nn.Module):
     def capture_md(self, z: Tensor, pos: Tensor, vel: Tensor, masses: Tensor, dt: float, batch: Optional[Tensor] = None,
                    box: Optional[Tensor] = None, q: Optional[Tensor] = None, num_systems: Optional[int] = None,
                    steps_per_replay: int = 10, force_scale: float = 1.0, thermostat: Optional[dict] = None, warmup: int = 3,
-                   atom_weights=None, halo_exchange=None):
+                   atom_weights=None, halo_exchange=None, barostat: Optional[dict] = None):
         """Capture ``steps_per_replay`` full MD steps into ONE HIP graph (needs ``static_shapes=True``): per step half-kick, drift,
         neighbour list + energy + forces, half-kick, the Langevin O step when ``thermostat=dict(friction=, kT=, seed=)`` is given, and
         the energy bookkeeping, with the integrator as HIP kernels between the evaluations (``tmdnet_md_advance``) - no host work
@@ -1378,8 +1378,14 @@ class TorchMD_Net(nn.Module):
         Positions are never wrapped.  Works for every architecture ``capture`` serves and for a batch of independent replicas.
         Returns a ``torchmdnet_amd.md.DeviceMD``: ``md(n)`` replays n times; ``md.pos / vel / forces``, ``md.epot / ekin`` [K,B],
         ``md.steps_done``, ``md.check()``, ``md.reset(pos, vel, step)``.  Inputs are staged and kept alive as in ``capture``; a ``box``
-        that needs no conversion stays the caller's object.  ``atom_weights`` / ``halo_exchange`` are accepted only to be refused."""
-        from torchmdnet_amd.md import DeviceMD
+        that needs no conversion stays the caller's object.  ``atom_weights`` / ``halo_exchange`` are accepted only to be refused.
+        ``barostat=dict(pressure=, tau=, compressibility=, kT=, seed=)`` (NPT): after every step an isotropic stochastic-cell-rescaling
+        move per molecule scales ``md.box``, positions and velocities inside the graph (``tmdnet_md_barostat``), from the virial
+        of that step's evaluation; pressure in E / length^3 (``md.BAR_IN_EV_PER_A3``), compressibility in length^3 / E, ``kT``
+        (default: the thermostat's; 0 = weak coupling) in E, ``seed`` default the thermostat's.  Needs a box per molecule ([3,3] for
+        one molecule, [B,3,3] otherwise) and an architecture with a virial (not TensorNet2); logs in ``md.volume / pressure /
+        scale`` [K,B]."""
+        from torchmdnet_amd.md import DeviceMD, parse_barostat
 
         if not getattr(self.representation_model, "static_shapes", False):
             raise RuntimeError("capture_md() needs a model created with static_shapes=True")
@@ -1404,9 +1410,23 @@ class TorchMD_Net(nn.Module):
         dev = pos.device  # staged as in capture(): the graph records raw pointers, conversions must not be temporaries
         z = z.detach().to(device=dev, dtype=torch.long).contiguous()
         batch = batch.detach().to(device=dev, dtype=torch.long).contiguous()
-        box = None if box is None else box.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if barostat is not None:  # refused before anything is staged or captured
+            parse_barostat(barostat, thermostat)
+            self._refuse_virial()
+            if box is None:
+                raise ValueError("capture_md(barostat=...) needs a box: the barostat scales it")
+            if box.dim() == 2 and n_mol > 1:
+                raise NotImplementedError("capture_md(barostat=...) has one barostat per molecule: give every molecule its own box "
+                                          f"[{n_mol},3,3], not one shared [3,3] box")
+            if box is getattr(rm.distance, "box", None):
+                box = box.clone()  # the model's own box stays as it was created
+        if box is not None:
+            staged = box.detach().to(device=dev, dtype=torch.float32).contiguous()
+            # no conversion: the caller's own object, so that md.box IS the tensor the caller scales or reads
+            box = box if staged.data_ptr() == box.data_ptr() and not box.requires_grad else staged
         q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).contiguous()
-        return DeviceMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup)
+        return DeviceMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
+                        barostat)
 
     def debug_tensor(self, name: str, shape) -> Tensor:
         L = _C.lib()
