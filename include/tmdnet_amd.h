@@ -500,6 +500,70 @@ int tmdnet_md_barostat(tmdnet_model* m, void* stream, void* graph_ws, void* md_w
                        double compressibility, double tau, double force_scale, uint64_t seed, float* volume_log_row,
                        float* pressure_log_row, float* scale_log_row);
 
+/* ---- Device-resident geometry minimisation (csrc/tn_min.hip; additive exports, the ABI revision stays 10) ---------------------
+ * FIRE (Bitzek et al., Phys. Rev. Lett. 97, 170201, 2006) in the form ASE ships: unit masses, the whole-molecule step clamp, and
+ * one controller per molecule (replica), so that every molecule of a batch has its own time step and converges at its own step.
+ * The launches sit between two tmdnet_energy_forces calls of a captured step: K steps replay as one HIP graph.  The box is fixed.
+ * Per step, from the forces F at the current positions (an atom with fixed[i] != 0 contributes nothing and never moves):
+ *   per atom, fp32 under the rounding contract of the MD loop (one rounded product, one rounded sum, in this order):
+ *     t_vf = (Fx vx + Fy vy) + Fz vz,  t_ff and t_vv likewise
+ *   per molecule, the fp32 terms widened and added in fp64 in a fixed order (threads stride the atoms, a wave tree, waves in turn,
+ *   slices in slice order; no floating-point atomics):  vf, ff, vv, fmax2 = max_i t_ff
+ *   per molecule, one thread, fp64, in this order (`step` = steps completed, this one included):
+ *     1. converged_at >= 0: nothing (the molecule stays frozen)
+ *     2. a sum is not finite: status 2 (below)
+ *     3. sqrt(fmax2) < fmax: converged_at = step, frozen
+ *     4. vf > 0:  c_v = 1 - alpha;  mix = (ff > 0 && vv > 0) ? alpha sqrt(vv / ff) : 0;
+ *                 n_pos > n_min: dt = min(dt f_inc, dt_max), alpha = alpha f_alpha;   n_pos += 1
+ *     5. else:    c_v = 0, mix = 0, alpha = alpha0, dt = dt f_dec, n_pos = 0
+ *     6. c_f = mix + dt                                      (the new dt)
+ *     7. n2 = ((c_v c_v) vv + ((2 c_v) c_f) vf) + (c_f c_f) ff        (|v_new|^2 from the sums: the clamp needs no second reduction)
+ *     8. len = dt sqrt(max(n2, 0));   d = len > max_step ? dt (max_step / len) : dt
+ *     9. c_v, c_f, d rounded to fp32 once
+ *   per atom, fp32 under the contract:  v <- (c_v v) + (c_f F),  x <- x + (d v);  frozen molecule or fixed atom: v <- 0 and x is
+ *   not touched (a branch, not a product with 0).
+ * Without a thermostat there is no noise: a minimisation is a fixed sequence of IEEE operations, bit-identical from run to run. */
+#define TMDNET_MIN_OPEN 0   /* the per-atom update alone, from the coefficients the workspace holds (first launch of a replay) */
+#define TMDNET_MIN_MIDDLE 1 /* after an evaluation: accept it, reduce, control, update */
+#define TMDNET_MIN_CLOSE 2  /* after the last evaluation of a replay, and once after a reset: accept, reduce, control */
+/* Bytes of the minimiser state `min_ws`: a 256-byte header (64-bit step counter, sticky status, the start values), per molecule
+ * dt and alpha (fp64), n_pos (int32), converged_at (int64) and the three coefficients, the positions and velocities before the
+ * last move (24 bytes per atom) and the slice sums (32 bytes per molecule and slice of at most 1 024 atoms on average). */
+int tmdnet_min_workspace_bytes(int64_t n_atoms, int64_t n_mol, size_t* bytes);
+/* Enqueues: step counter = step0, status = 0; every molecule restarts from dt0, alpha0, n_pos = 0, converged_at = -1 at the next
+ * control.  After a reset the first launch must be tmdnet_min_advance(TMDNET_MIN_CLOSE) on the forces at the start geometry (with
+ * vel = 0): it computes the first coefficients - a molecule already below fmax converges at step0 - and counts no step.  An
+ * OPEN or MIDDLE launch's update before that does nothing. */
+int tmdnet_min_reset(void* stream, void* min_ws, uint64_t step0, double dt0, double alpha0);
+/* Enqueues one phase.  A replay of K steps is OPEN, then K times { evaluation at `pos`; MIDDLE, or CLOSE after the last }: every
+ * evaluated force set drives the controller exactly once, whatever K is.  MIDDLE / CLOSE are three launches (the reduction on a
+ * grid (n_mol, slices), the controller as one block, one thread per atom), OPEN is one.
+ *   m, graph_ws   the handle and graph workspace of the evaluation before this launch: its overflow flag is read, and the atom
+ *                 ranges of the molecules are taken from it when they are valid.  graph_ws == NULL (m may then be NULL): no
+ *                 overflow test, the sums run over all atoms filtered by `batch` (NULL: one molecule).
+ *   pos, vel      [n_atoms, 3], updated in place; vel is the minimiser's own velocity (zero at the start).
+ *   forces        [n_atoms, 3], read only: the evaluation's output (MIDDLE / CLOSE) or the kept forces (OPEN).
+ *   energy        [n_mol] or NULL: copied to epot_log_row.
+ *   fixed         [n_atoms] bytes or NULL;  batch   [n_atoms] int64 molecule index in the caller's order, or NULL.
+ *   forces_keep   [n_atoms, 3] or NULL: MIDDLE / CLOSE copy `forces` here once the step is accepted, so that a buffer the caller
+ *                 owns holds the forces at `pos` after a CLOSE (the `forces` of the next replay's OPEN).
+ *   dt_max ... fmax   the FIRE parameters above (dt0 and the first alpha are tmdnet_min_reset's); fmax > 0.
+ *   log rows      each [n_mol] or NULL, of the force set just controlled: epot, fmax = sqrt(fmax2) as fp32, sums [n_mol, 4] fp64
+ *                 (vf, ff, vv, fmax2), coef [n_mol, 3] fp32 (c_v, c_f, d of the NEXT move; 0 for a frozen molecule), dt and alpha
+ *                 (fp64, after the update), converged_at (int64, -1: not yet).
+ * Overflow: when the evaluation before a MIDDLE / CLOSE launch overflowed, the controller sets status 1 and pos and vel go back
+ * to what the last move saved.  Status 2: a sum of a molecule that still moves was not finite (a NaN force); nothing of that step
+ * is written.  Either way every later launch leaves pos, vel, forces_keep, the log rows, the controller state and the step counter
+ * alone until tmdnet_min_reset. */
+int tmdnet_min_advance(tmdnet_model* m, void* stream, void* graph_ws, void* min_ws, int64_t n_atoms, int64_t n_mol, int32_t phase,
+                       float* pos, float* vel, const float* forces, const float* energy, const uint8_t* fixed, const int64_t* batch,
+                       float* forces_keep, double dt_max, int32_t n_min, double f_inc, double f_dec, double alpha0, double f_alpha,
+                       double max_step, double fmax, float* epot_log_row, float* fmax_log_row, double* sums_log_row,
+                       float* coef_log_row, double* dt_log_row, double* alpha_log_row, int64_t* converged_log_row);
+/* host[0] = steps completed (the device counter), host[1] = status (1: an evaluation overflowed, 2: a non-finite force sum; the
+ * state is that of step host[0]).  Synchronises the stream.  Returns TMDNET_ERR_OVERFLOW for status 1, TMDNET_ERR_STATE for 2. */
+int tmdnet_min_status(void* stream, void* min_ws, uint64_t host[2]);
+
 #ifdef __cplusplus
 }
 #endif

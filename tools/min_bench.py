@@ -1,0 +1,139 @@
+#!/usr/bin/env python
+"""A/B of the geometry minimiser: ms per FIRE step of
+
+  (a) ``a_eager``: the loop a caller builds on ``capture()`` - one graph launch per step and FIRE as eager torch ops between the
+      launches, one controller per molecule (``index_add_`` sums over ``batch``, ``torch.where`` for the branches), everything on
+      the device and nothing read back;
+  (b) ``b_K10``: ``capture_minimize`` with K = 10 steps per graph launch,
+
+for 1 x 64 atoms, 256 x 64 atoms (bench.py's flagship batch) and the 192-atom periodic water box, TensorNet F = 128, L = 2.
+Alternating blocks of (a) and (b) in one process, each block at least ``--seconds`` of stepping with the final synchronise inside
+the clock; median and min / max over ``--rounds`` blocks.  The random-weight potential is no force field, so the steps are kept
+tiny (dt, dt_max and max_step scaled down: the atoms must not travel) and fmax is far below what is reached: no molecule freezes
+and both legs do the full work at every step.  Writes profiles/minimize.json."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "torchmd-net_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def _block(step_fn, steps_per_call, seconds, sync):
+    """ms per step of one block: calls until `seconds` have passed, the synchronise inside the clock"""
+    step_fn()
+    sync()
+    calls = 0
+    t0 = time.perf_counter()
+    while True:
+        for _ in range(max(1, 200 // steps_per_call)):
+            step_fn()
+            calls += 1
+        sync()  # the queue must not run ahead of the clock
+        t = time.perf_counter() - t0
+        if t >= seconds:
+            return 1e3 * t / (calls * steps_per_call)
+
+
+def eager_fire(torch, replay, batch, n_mol, fire, fmax):
+    """-> step(): one FIRE step of every molecule as eager torch ops on replay.pos, then one graph launch"""
+    dev = replay.pos.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    _, forces = replay()
+    vel = torch.zeros_like(replay.pos)
+    s = dict(dt=torch.full((n_mol,), fire["dt"], **f64), alpha=torch.full((n_mol,), fire["alpha"], **f64),
+             n_pos=torch.zeros(n_mol, dtype=torch.int64, device=dev), done=torch.zeros(n_mol, dtype=torch.bool, device=dev))
+    zero = torch.zeros(n_mol, **f64)
+
+    def mol_sum(t):
+        return torch.zeros(n_mol, **f64).index_add_(0, batch, t.sum(1).double())
+
+    def step():
+        vf, ff, vv = mol_sum(vel * forces), mol_sum(forces * forces), mol_sum(vel * vel)
+        fmax2 = torch.zeros(n_mol, dtype=torch.float32, device=dev).index_reduce_(0, batch, (forces * forces).sum(1), "amax")
+        s["done"] |= fmax2.double().sqrt() < fmax
+        down = vf > 0
+        c_v = torch.where(down, 1.0 - s["alpha"], zero)
+        mix = torch.where(down & (ff > 0) & (vv > 0), s["alpha"] * torch.sqrt(vv / ff.clamp_min(1e-300)), zero)
+        grow = down & (s["n_pos"] > fire["n_min"])
+        s["dt"] = torch.where(grow, (s["dt"] * fire["f_inc"]).clamp_max(fire["dt_max"]), torch.where(down, s["dt"], s["dt"] * fire["f_dec"]))
+        s["alpha"] = torch.where(grow, s["alpha"] * fire["f_alpha"], torch.where(down, s["alpha"], torch.full_like(zero, fire["alpha"])))
+        s["n_pos"] = torch.where(down, s["n_pos"] + 1, torch.zeros_like(s["n_pos"]))
+        c_f = mix + s["dt"]
+        n2 = c_v * c_v * vv + 2.0 * c_v * c_f * vf + c_f * c_f * ff
+        length = s["dt"] * torch.sqrt(n2.clamp_min(0.0))
+        d = s["dt"] * (fire["max_step"] / length.clamp_min(1e-300)).clamp_max(1.0)
+        moving = (~s["done"]).to(torch.float32)
+        coef = (torch.stack([c_v, c_f, d], 1).to(torch.float32) * moving[:, None])[batch]
+        vel.mul_(coef[:, 0:1]).addcmul_(coef[:, 1:2], forces)
+        replay.pos.addcmul_(coef[:, 2:3], vel)
+        replay()
+
+    return step, s
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seconds", type=float, default=2.0)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "minimize.json"))
+    a = ap.parse_args()
+
+    import torch
+
+    import __graft_entry__ as ge
+
+    ge.build_hip(verbose=False)
+    from torchmdnet_amd import workloads as W
+    from torchmdnet_amd.models.model import create_model
+
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)
+    K, fmax = 10, 1e-9
+    fire = dict(dt=1e-4, dt_max=1e-3, n_min=5, f_inc=1.1, f_dec=0.5, alpha=0.1, f_alpha=0.99, max_step=1e-4)
+    result = {"device": torch.cuda.get_device_name(dev), "model": "TensorNet F=128 L=2 (C2_ARGS), static_shapes", "steps_per_replay": K,
+              "seconds_per_block": a.seconds, "rounds": a.rounds, "fire": fire, "fmax": fmax, "sizes": {}}
+    for name in ("1x64", "256x64", "water192"):
+        torch.manual_seed(0)
+        if name == "water192":
+            model = create_model(dict(W.C2_ARGS, static_shapes=True, max_num_neighbors=128)).to(dev)
+            z, pos, box = W.water_box(n_side=4)
+            batch, box = torch.zeros_like(z), box.to(dev).float().contiguous()
+        else:
+            model = create_model(dict(W.C2_ARGS, static_shapes=True)).to(dev)
+            z, pos, batch = W.synthetic_batch(n_mol=int(name.split("x")[0]), n_atoms=64)
+            box = None
+        z, pos, batch = z.to(dev), pos.to(dev).float().contiguous(), batch.to(dev)
+        n_mol = int(batch.max()) + 1
+        replay = model.capture(z, pos, batch, box)
+        replay(pos)
+        eager, state = eager_fire(torch, replay, batch, n_mol, fire, fmax)
+        opt = model.capture_minimize(z, pos, batch=batch, box=box, steps_per_replay=K, fmax=fmax, fire=fire)
+        legs = {"a_eager": (eager, 1), "b_K10": (opt, K)}
+        times = {k: [] for k in legs}
+        for _ in range(a.rounds):  # alternating blocks: every round visits every leg once
+            for k, (fn, spc) in legs.items():
+                times[k].append(_block(fn, spc, a.seconds, sync))
+        opt.check()  # raises if the minimisation overflowed: its timings would be of a frozen loop
+        entry = {k: {"ms_per_step": statistics.median(v), "min": min(v), "max": max(v)} for k, v in times.items()}
+        entry["n_atoms"], entry["n_mol"] = int(z.shape[0]), n_mol
+        entry["converged"] = {"eager": int(state["done"].sum()), "capture_minimize": int((opt.converged_at >= 0).sum())}
+        entry["displacement_max"] = {"eager": float((replay.pos - pos).abs().max()), "capture_minimize": float((opt.pos - pos).abs().max())}
+        entry["ratio_b_over_a"] = entry["b_K10"]["ms_per_step"] / entry["a_eager"]["ms_per_step"]
+        entry["b_K10_not_slower_than_eager"] = entry["b_K10"]["ms_per_step"] <= entry["a_eager"]["ms_per_step"]
+        result["sizes"][name] = entry
+        print(name, json.dumps(entry), flush=True)
+        del replay, opt, legs
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()

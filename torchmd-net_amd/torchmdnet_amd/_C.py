@@ -126,6 +126,11 @@ def lib():
     L.tmdnet_md_barostat_workspace_bytes.argtypes = [i64, C.POINTER(sz)]
     L.tmdnet_md_barostat.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, f64, f64, f64, f64, f64,
                                      u64, vp, vp, vp]
+    L.tmdnet_min_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
+    L.tmdnet_min_reset.argtypes = [vp, vp, u64, f64, f64]
+    L.tmdnet_min_advance.argtypes = [vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, f64, i32, f64, f64, f64, f64, f64, f64,
+                                     vp, vp, vp, vp, vp, vp, vp]
+    L.tmdnet_min_status.argtypes = [vp, vp, C.POINTER(u64)]
     for name in declared_symbols():
         fn = getattr(L, name)
         if fn.restype is C.c_int:

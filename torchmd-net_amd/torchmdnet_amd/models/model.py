@@ -1428,6 +1428,54 @@ class TorchMD_Net(nn.Module):
         return DeviceMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
                         barostat)
 
+    def capture_minimize(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
+                         q: Optional[Tensor] = None, num_systems: Optional[int] = None, steps_per_replay: int = 10,
+                         fmax: float = 0.05, fire: Optional[dict] = None, fixed: Optional[Tensor] = None, warmup: int = 3,
+                         atom_weights=None, halo_exchange=None):
+        """Capture ``steps_per_replay`` steps of a FIRE geometry minimisation into ONE HIP graph (needs ``static_shapes=True``): per
+        step the per-atom update, neighbour list + energy + forces, the per-molecule sums and the controller, all as HIP kernels
+        between the evaluations (``tmdnet_min_advance``) - no host work between steps.  FIRE as ASE ships it, unit masses, one
+        controller per molecule: every molecule of a batch has its own time step and stops moving at the step where its largest
+        atomic force norm falls below ``fmax``.  ``fire`` overrides ASE's defaults ``dict(dt=0.1, dt_max=1.0, n_min=5, f_inc=1.1,
+        f_dec=0.5, alpha=0.1, f_alpha=0.99, max_step=0.2)``; ``fixed`` [N] marks atoms that never move.  The box is fixed (no cell
+        relaxation).  Works for every architecture ``capture`` serves.  Returns a ``torchmdnet_amd.minimize.DeviceMinimizer``:
+        ``opt(n)`` replays n times; ``opt.pos / forces``, ``opt.epot / fmax`` [K,B], ``opt.converged_at / step_size`` [B],
+        ``opt.check()``, ``opt.reset(pos)``, ``opt.run(max_steps, check_every)``.  Inputs are staged and kept alive as in
+        ``capture``.  ``atom_weights`` / ``halo_exchange`` are accepted only to be refused."""
+        from torchmdnet_amd.minimize import DeviceMinimizer, parse_fire
+
+        if not getattr(self.representation_model, "static_shapes", False):
+            raise RuntimeError("capture_minimize() needs a model created with static_shapes=True")
+        if self._head_kind() != _C.HEAD_SCALAR:
+            raise NotImplementedError(f"capture_minimize has no HIP path with output_model {type(self.output_model).__name__}: a "
+                                      "minimisation needs energies and their forces (scalar head)")
+        if self.parameter_gradients:
+            raise NotImplementedError("capture_minimize has no HIP path with parameter_gradients=True (a training model); create the "
+                                      "model without it")
+        if atom_weights is not None or halo_exchange is not None:
+            raise NotImplementedError("capture_minimize has no HIP path with atom weights or the halo exchange (domain decomposition)")
+        if int(steps_per_replay) < 1:
+            raise ValueError(f"steps_per_replay must be at least 1, got {steps_per_replay}")
+        if not float(fmax) > 0:
+            raise ValueError(f"fmax must be positive, got {fmax}")
+        parse_fire(fire)  # refused before anything is staged or captured
+        if fixed is not None and fixed.numel() != z.shape[0]:
+            raise ValueError(f"fixed must have one entry per atom ({z.shape[0]}), got {fixed.numel()}")
+        _require_cuda(pos, "capture_minimize")
+        if pos.dtype != torch.float32:
+            raise NotImplementedError("torchmdnet_amd computes in fp32; cast positions to float32")
+        batch = torch.zeros_like(z) if batch is None else batch
+        n_mol = int(num_systems) if num_systems is not None else int(batch.max().item()) + 1
+        rm = self.representation_model
+        if box is None and rm.distance.use_periodic:
+            box = rm.distance.box
+        dev = pos.device  # staged as in capture(): the graph records raw pointers, conversions must not be temporaries
+        z = z.detach().to(device=dev, dtype=torch.long).contiguous()
+        batch = batch.detach().to(device=dev, dtype=torch.long).contiguous()
+        box = None if box is None else box.detach().to(device=dev, dtype=torch.float32).contiguous()
+        q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).contiguous()
+        return DeviceMinimizer(self, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, fire, fixed, warmup)
+
     def debug_tensor(self, name: str, shape) -> Tensor:
         L = _C.lib()
         st = self._engine
