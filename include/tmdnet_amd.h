@@ -458,8 +458,9 @@ int tmdnet_md_advance(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws
                       const float* sigma, float dt, float c1, float c2, uint64_t seed, const int64_t* batch, float* forces_keep,
                       float* epot_log_row, float* ekin_log_row);
 /* host[0] = steps completed (the device counter), host[1] = status (1: an evaluation overflowed; the state is that of step
- * host[0].  2: a barostat move was unusable, see tmdnet_md_barostat; step host[0] is complete but for that move).  Synchronises the
- * stream.  Returns TMDNET_ERR_OVERFLOW for status 1 and TMDNET_ERR_STATE for status 2. */
+ * host[0].  2: a barostat move was unusable, see tmdnet_md_barostat; step host[0] is complete but for that move.  3: a constraint
+ * cluster did not converge, see tmdnet_md_advance_constrained).  Synchronises the stream.  Returns TMDNET_ERR_OVERFLOW for status 1
+ * and TMDNET_ERR_STATE for status 2 and 3. */
 int tmdnet_md_status(void* stream, void* md_ws, uint64_t host[2]);
 
 /* ---- Barostat of the device-resident MD loop (csrc/tn_md.hip; additive exports, the ABI revision stays 10) --------------------
@@ -499,6 +500,57 @@ int tmdnet_md_barostat(tmdnet_model* m, void* stream, void* graph_ws, void* md_w
                        float* box, int32_t box_mode, const float* virial, const float* ekin_row, double pressure, double kT,
                        double compressibility, double tau, double force_scale, uint64_t seed, float* volume_log_row,
                        float* pressure_log_row, float* scale_log_row);
+
+/* ---- Distance constraints of the device-resident MD loop (csrc/tn_md_cons.hip; additive exports, the ABI revision stays 10) ------
+ * Holonomic constraints |x_i - x_j| = d_c by RATTLE (Andersen, J. Comput. Phys. 52, 24, 1983) in the splitting above:
+ *     B  v <- v + hk F
+ *     A  x <- x + dt v
+ *     S  SHAKE: x <- x + Dx so that every constraint holds, v <- v + Dx / dt
+ *        F = F(x)
+ *     B  v <- v + hk F    [ O  v <- c1 v + c2 sigma xi ]
+ *     R  RATTLE: v <- v + Dv so that (x_i - x_j).(v_i - v_j) = 0 for every constraint; kinetic energy of the projected v
+ * The caller groups the constraints into clusters, the connected components of the constraint graph: at most 8 atoms and 12
+ * constraints each.  Atoms in no constraint are packed, up to 8 at a time, into clusters without constraints, so that every atom is in
+ * exactly one cluster and goes through the same launch; such an atom gets bit for bit what tmdnet_md_advance gives it (x, v,
+ * kinetic term, noise by the caller's atom index).  One group of 8 lanes does a cluster's whole step, so the phases mean what they
+ * mean for tmdnet_md_advance and K steps stay K + 1 integrator launches: OPEN = B A S, MIDDLE = B [O] R + kinetic terms, then
+ * B A S of the next step, CLOSE = B [O] R + kinetic terms.  TMDNET_MD_PROJECT = R alone at the current positions, no kick and no
+ * kinetic energy: once before the first step (and after new velocities), so that velocities drawn from a Maxwell-Boltzmann
+ * distribution start consistent with the constraints.
+ * The iterations run in fp64 on the cluster's fp32 coordinates, one constraint after the other in table order (Gauss-Seidel), with
+ * w = 1 / m from the fp32 masses (1 / inf = 0: that end does not move) and s_c = x_keep_i - x_keep_j, the saved positions of the
+ * step's start, as the direction of the SHAKE moves:
+ *     S: g = (d^2 - r.r) / (2 (w_a + w_b) s.r),  x_a += g w_a s,  x_b -= g w_b s      until every |r.r - d^2| <= 2 tol d^2
+ *     R: k = -r.(v_a - v_b) / ((w_a + w_b) r.r),  v_a += k w_a r,  v_b -= k w_b r     until every |r.(v_a - v_b)| dt <= tol d^2
+ * An iteration has converged when one whole sweep over the cluster finds every constraint within tolerance; at most max_iter
+ * correcting sweeps are followed by one that only tests.  x, v and the velocity Dx / dt that S adds are each rounded to fp32 once,
+ * after the iteration.  Fixed order, no atomics in the arithmetic, no dependence on the launch geometry: repeats are bit-identical,
+ * as long as no cluster fails (below).
+ * Failure: a cluster that has not converged, or that met a non-finite value, writes x_keep / v_keep of its atoms back to pos /
+ * vel (PROJECT: leaves vel alone), ORs the fail word in cons_ws and does nothing else - unconverged positions are never written, the
+ * evaluation that follows always sees finite coordinates.  The next reduction (PROJECT: a latch of its own) sets status 3, writes no
+ * log row and does not advance the step counter; from then on every launch returns at once.  The state is then frozen and finite,
+ * but not a point of the trajectory: other clusters may be half a step ahead.  Which ones is not reproducible: a cluster reads the
+ * fail word when it starts, while other clusters of the same launch may be setting it, so the clusters of a failing launch that
+ * still complete their half step depend on the scheduling, and the frozen state can differ from run to run.  To continue: zero cons_ws, tmdnet_md_reset, new
+ * positions and velocities.  Overflow (status 1) is handled as by tmdnet_md_advance.
+ *   cons_ws       tmdnet_md_constraints_workspace_bytes bytes, ZEROED by the caller before the first launch and with every
+ *                 tmdnet_md_reset.
+ *   md_ws, pos ... ekin_log_row   as in tmdnet_md_advance, but mass is read in every phase; forces, hk may be NULL for PROJECT.
+ *   cluster_atoms    [n_clusters, 8] int32: the caller's atom indices, -1 = no atom; every atom exactly once.
+ *   cluster_offsets  [n_clusters + 1] int32: the constraints of cluster c are rows cluster_offsets[c] .. cluster_offsets[c + 1] of
+ *   constraint_ends  [n_constraints, 2] int32: the two ends as positions 0 .. 7 in the cluster's row of cluster_atoms, and
+ *   constraint_d2    [n_constraints] double: d_c^2.
+ *   tol > 0, max_iter >= 1. */
+#define TMDNET_MD_PROJECT 3 /* tmdnet_md_advance_constrained only: R alone */
+int tmdnet_md_constraints_workspace_bytes(int64_t n_atoms, int64_t n_clusters, int64_t n_constraints, size_t* bytes);
+int tmdnet_md_advance_constrained(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, void* cons_ws, int64_t n_atoms,
+                                  int64_t n_mol, int32_t phase, float* pos, float* vel, const float* forces, const float* energy,
+                                  const float* hk, const float* mass, const float* sigma, float dt, float c1, float c2, uint64_t seed,
+                                  const int64_t* batch, float* forces_keep, float* epot_log_row, float* ekin_log_row,
+                                  int64_t n_clusters, int64_t n_constraints, const int32_t* cluster_atoms,
+                                  const int32_t* cluster_offsets, const int32_t* constraint_ends, const double* constraint_d2, double tol,
+                                  int32_t max_iter);
 
 /* ---- Device-resident geometry minimisation (csrc/tn_min.hip; additive exports, the ABI revision stays 10) ---------------------
  * FIRE (Bitzek et al., Phys. Rev. Lett. 97, 170201, 2006) in the form ASE ships: unit masses, the whole-molecule step clamp, and

@@ -20,7 +20,23 @@ holds it with a cutoff of margin (same atoms, same pairs):
   (b) ``b_K10_npt``: ``capture_md(thermostat=, barostat=)`` with K = 10, and ``b_K10_nvt``: the same without the barostat,
 
 same alternating blocks, median and min / max.  The coupling is weak enough that the box stays where it is (the random-weight
-potential is no force field).  Records the NPT / NVT ratio and NPT against the eager loop per size; writes profiles/md_npt.json."""
+potential is no force field).  Records the NPT / NVT ratio and NPT against the eager loop per size; writes profiles/md_npt.json.
+
+``--constraints``: the constrained loop, on the 192-atom water box (rigid water: three coupled constraints per molecule) and on the
+64-atom molecule above (its X-H bonds, ``md.hydrogen_pairs``), in a state where the atoms move so that the iterations have work to
+do: dt = 2 fs, thermal velocities (300 K), and ``force_scale`` such that the random-weight model's largest initial force counts as
+0.2 eV / A:
+
+  (a) ``a_eager_shake``: the loop a caller builds on ``capture()`` - one graph launch per step, velocity Verlet, SHAKE and the
+      velocity projection as eager torch ops (a fixed number of Gauss-Seidel sweeps - the largest number any cluster needed, see
+      below -, the constraints of equal rank in their cluster relaxed together; nothing read back);
+  (b) ``b_K10_constrained``: ``capture_md_constrained(constraints=)`` with K = 10, and ``b_K10_free``: the same without constraints.
+
+A block is ``--block-steps`` steps from the same start (the atoms must not travel far: no force field), restarted outside the clock;
+alternating blocks, median and min / max over ``--rounds`` blocks after one that warms up.  ``iteration`` records what SHAKE and
+RATTLE had to do at the middle step of a block - the residual before SHAKE over its bound, and the correcting sweeps per cluster,
+counted by the same Gauss-Seidel iteration in fp64 on the host from the device's state -, and ``residual_over_bound_end`` what the
+unconstrained leg's positions have become.  Writes profiles/md_constraints.json."""
 import argparse
 import json
 import os
@@ -146,16 +162,205 @@ def npt_main(a):
     print("wrote", out)
 
 
+def _count_sweeps(x, ref, rows, d2, cluster, n_clusters, tol, dt, velocity, limit=64):
+    """The Gauss-Seidel iteration of csrc/tn_md_cons_math.h in fp64 torch on the host, for counting only: correcting sweeps per
+    cluster until every constraint is within tolerance.  `rows`: per rank r the table rows of the r-th constraint of every cluster
+    (different clusters share no atom, so relaxing a rank together IS the cluster's table order).  velocity: RATTLE on x = velocities
+    at the positions `ref`; else SHAKE on x = positions with the saved positions `ref`.  -> sweeps [n_clusters] int64"""
+    import torch
+
+    sweeps = torch.zeros(n_clusters, dtype=torch.int64)
+    for _ in range(limit):
+        hit = torch.zeros(n_clusters, dtype=torch.bool)
+        for sel, ia, ib, wa, wb in rows:
+            s = ref[ia] - ref[ib]
+            if velocity:
+                rv = (s * (x[ia] - x[ib])).sum(1)
+                bad = rv.abs() * dt > tol * d2[sel]
+                g = -rv / ((wa + wb) * (s * s).sum(1))
+            else:
+                r = x[ia] - x[ib]
+                diff = d2[sel] - (r * r).sum(1)
+                bad = diff.abs() > 2.0 * tol * d2[sel]
+                g = diff / (2.0 * (wa + wb) * (s * r).sum(1))
+            g = torch.where(bad, g, torch.zeros_like(g))[:, None]
+            x.index_add_(0, ia, g * wa[:, None] * s)
+            x.index_add_(0, ib, -g * wb[:, None] * s)
+            hit[cluster[sel][bad]] = True
+        if not bool(hit.any()):
+            break
+        sweeps += hit
+    return sweeps
+
+
+def constraints_main(a):
+    import torch
+
+    import __graft_entry__ as ge
+
+    ge.build_hip(verbose=False)
+    from torchmdnet_amd import md as MD
+    from torchmdnet_amd import workloads as W
+    from torchmdnet_amd.models.model import create_model
+
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)
+    dt, FS, K, kT, block_steps = 2.0, MD.FORCE_SCALE_EV_A_AMU_FS, 10, 0.0259, a.block_steps
+    assert block_steps % K == 0
+    result = {"device": torch.cuda.get_device_name(dev), "model": "TensorNet F=128 L=2 (C2_ARGS), static_shapes", "steps_per_replay": K,
+              "dt_fs": dt, "kT_of_the_velocities_eV": kT, "largest_initial_force_eV_per_A": 0.2, "steps_per_block": block_steps,
+              "rounds": a.rounds, "sizes": {}}
+    for name in ("water192", "synthetic64"):
+        torch.manual_seed(0)
+        if name == "water192":
+            model = create_model(dict(W.C2_ARGS, static_shapes=True, max_num_neighbors=128)).to(dev)
+            z, pos, box = W.water_box(n_side=4)
+            pairs = MD.hydrogen_pairs(z, pos, rigid_water=True)
+        else:
+            model = create_model(dict(W.C2_ARGS, static_shapes=True, max_num_neighbors=64)).to(dev)
+            z, pos, _ = W.synthetic_batch(n_mol=1, n_atoms=64)
+            box = None
+            pairs = MD.hydrogen_pairs(z, pos, cutoff=1.6)
+        z, pos = z.to(dev), pos.to(dev).float().contiguous()
+        box = None if box is None else box.to(dev).float().contiguous()
+        n = int(z.shape[0])
+        batch = torch.zeros_like(z)
+        masses = torch.where(z == 1, 1.008, 12.0).float()
+        # a state in which the atoms move: thermal velocities (300 K) and a 2 fs step; the random-weight model is no force field,
+        # so its largest initial force counts as 0.2 eV / A (tests/test_gpu_md_constraints.py does the same)
+        vel0 = (torch.sqrt(kT * FS / masses)[:, None] * torch.randn(n, 3, generator=torch.Generator().manual_seed(8)).to(dev)).float()
+        replay = model.capture(z, pos, batch, box)
+        _, forces = replay(pos)
+        fs = FS * 0.2 / float(forces.abs().max())
+        con = MD.prepare_constraints(dict(pairs=pairs), pos, batch, masses, 1)
+        mds = {}
+        for leg, c in (("b_K10_free", None), ("b_K10_constrained", dict(pairs=pairs))):
+            mds[leg] = model.capture_md_constrained(z, pos, vel0, masses, dt, batch=batch, box=box, steps_per_replay=K, force_scale=fs,
+                                                    constraints=c)
+        mdc = mds["b_K10_constrained"]
+        vel0p = mdc.vel.clone()  # projected onto the constraints: where every leg starts
+        hk = mdc.hk[:, None]
+
+        # ---- what the iteration has to do: its sweeps, counted on the host from the device's state in the middle of a block
+        off = con["cluster_offsets"].long()
+        cnt = (off[1:] - off[:-1])[:con["n_bound"]]
+        cluster = torch.repeat_interleave(torch.arange(con["n_bound"]), cnt)
+        rank = torch.cat([torch.arange(int(c)) for c in cnt]) if pairs.shape[0] else torch.zeros(0).long()
+        table = pairs[con["order"]]
+        d2 = con["constraint_d2"].double()
+        w64 = 1.0 / masses.double().cpu()
+        rows = []
+        for r in range(int(rank.max()) + 1 if rank.numel() else 0):
+            sel = (rank == r).nonzero().reshape(-1)
+            rows.append((sel, table[sel, 0], table[sel, 1], w64[table[sel, 0]], w64[table[sel, 1]]))
+        mdc(block_steps // K // 2)
+        assert mdc.check() == block_steps // 2
+        x0, v0, f0 = mdc.pos.clone(), mdc.vel.clone(), mdc.forces.clone()
+        v_half = v0 + hk * f0
+        x_free = x0 + dt * v_half  # after B, A: what SHAKE is given
+        res, bound = MD.constraint_residuals(x_free, con["pairs"], con["lengths"], con["tol"])
+        x64 = x_free.double().cpu()
+        shake = _count_sweeps(x64, x0.double().cpu(), rows, d2, cluster, con["n_bound"], con["tol"], dt, False)
+        x1 = x64.float().to(dev)
+        _, f1 = replay(x1)
+        v1 = v_half + ((x64 - x_free.double().cpu()) / dt).float().to(dev) + hk * f1
+        rattle = _count_sweeps(v1.double().cpu(), x64.float().double(), rows, d2, cluster, con["n_bound"], con["tol"], dt, True)
+        work = {"at_step": block_steps // 2, "residual_over_bound_before_shake": float((res / bound).max()),
+                "shake_sweeps_per_cluster": {"mean": float(shake.double().mean()), "min": int(shake.min()), "max": int(shake.max())},
+                "rattle_sweeps_per_cluster": {"mean": float(rattle.double().mean()), "min": int(rattle.min()), "max": int(rattle.max())}}
+        sweeps = max(int(shake.max()), int(rattle.max()), 1)  # what a loop with a fixed number of sweeps needs
+
+        # ---- the eager alternative: the constraints of rank r in their cluster form group r, relaxed together
+        groups = []
+        for sel, ia, ib, _, _ in rows:
+            ia, ib = ia.to(dev), ib.to(dev)
+            groups.append((ia, ib, con["constraint_d2"][sel].to(dev).float(), (1.0 / masses[ia])[:, None], (1.0 / masses[ib])[:, None]))
+        vel = vel0p.clone()
+        keep = pos.clone()
+
+        def a_eager_shake():
+            x = replay.pos
+            keep.copy_(x)
+            vel.addcmul_(hk, forces)
+            x.add_(vel, alpha=dt)
+            for _ in range(sweeps):
+                for ia, ib, d2_, wa, wb in groups:
+                    r, s = x[ia] - x[ib], keep[ia] - keep[ib]
+                    g = ((d2_ - (r * r).sum(1)) / (2.0 * (wa + wb)[:, 0] * (s * r).sum(1)))[:, None]
+                    x.index_add_(0, ia, g * wa * s)
+                    x.index_add_(0, ib, -g * wb * s)
+                    vel.index_add_(0, ia, g * wa * s / dt)
+                    vel.index_add_(0, ib, -g * wb * s / dt)
+            replay()
+            vel.addcmul_(hk, forces)
+            for _ in range(sweeps):
+                for ia, ib, d2_, wa, wb in groups:
+                    r, u = x[ia] - x[ib], vel[ia] - vel[ib]
+                    k = (-(r * u).sum(1) / ((wa + wb)[:, 0] * (r * r).sum(1)))[:, None]
+                    vel.index_add_(0, ia, k * wa * r)
+                    vel.index_add_(0, ib, -k * wb * r)
+
+        def restart_eager():
+            vel.copy_(vel0p)
+            replay(pos)
+
+        legs = {"a_eager_shake": (a_eager_shake, 1, restart_eager)}
+        for leg, md in mds.items():
+            legs[leg] = (md, K, lambda md=md: md.reset(pos=pos, vel=vel0p))
+        times = {k: [] for k in legs}
+        ends = {}
+        for rnd in range(a.rounds + 1):  # alternating blocks: every round visits every leg once; round 0 warms up
+            for k, (fn, spc, restart) in legs.items():
+                restart()  # every block walks the same block_steps steps from the same start, outside the clock
+                sync()
+                t0 = time.perf_counter()
+                for _ in range(block_steps // spc):
+                    fn()
+                sync()
+                t = time.perf_counter() - t0
+                if rnd:
+                    times[k].append(1e3 * t / block_steps)
+                if k in mds:  # raises if the block overflowed or a cluster did not converge: it would have timed a frozen loop
+                    assert mds[k].check() == block_steps
+                ends[k] = (mds[k].pos if k in mds else replay.pos).clone()
+        entry = _summary(times)
+        entry["n_atoms"], entry["n_constraints"], entry["n_clusters"] = n, int(pairs.shape[0]), int(con["cluster_atoms"].shape[0])
+        entry["iteration"] = work
+        entry["eager_sweeps"] = sweeps
+        entry["largest_displacement_end_A"] = float((ends["b_K10_constrained"] - pos).norm(dim=1).max())
+        entry["residual_over_bound_end"] = {}
+        for k, key in (("b_K10_constrained", "capture_md"), ("a_eager_shake", "eager"), ("b_K10_free", "unconstrained")):
+            res, bound = MD.constraint_residuals(ends[k], con["pairs"], con["lengths"], con["tol"])
+            entry["residual_over_bound_end"][key] = float((res / bound).max())
+        entry["ns_per_day_constrained_at_2fs"] = 2.0 * entry["b_K10_constrained"]["ns_per_day_at_1fs"]
+        entry["ratio_constrained_over_free"] = entry["b_K10_constrained"]["ms_per_step"] / entry["b_K10_free"]["ms_per_step"]
+        entry["ratio_constrained_over_eager_shake"] = entry["b_K10_constrained"]["ms_per_step"] / entry["a_eager_shake"]["ms_per_step"]
+        entry["b_K10_constrained_not_slower_than_eager"] = entry["b_K10_constrained"]["ms_per_step"] <= entry["a_eager_shake"]["ms_per_step"]
+        result["sizes"][name] = entry
+        print(name, json.dumps(entry), flush=True)
+        del replay, mds, mdc, legs
+    out = a.out if a.out else os.path.join(ROOT, "profiles", "md_constraints.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--sizes", type=int, nargs="+", default=[64, 256, 1024])
     ap.add_argument("--npt", action="store_true", help="time the constant-pressure loop instead (profiles/md_npt.json)")
-    ap.add_argument("--out", default=None, help="default: profiles/md_loop.json, with --npt profiles/md_npt.json")
+    ap.add_argument("--constraints", action="store_true", help="time the constrained loop instead (profiles/md_constraints.json)")
+    ap.add_argument("--block-steps", type=int, default=100, help="--constraints: steps of one timed block (a multiple of 10)")
+    ap.add_argument("--out", default=None, help="default: profiles/md_loop.json, with --npt profiles/md_npt.json, with --constraints "
+                                                "profiles/md_constraints.json")
     a = ap.parse_args()
     if a.npt:
         return npt_main(a)
+    if a.constraints:
+        return constraints_main(a)
     a.out = a.out or os.path.join(ROOT, "profiles", "md_loop.json")
 
     import torch

@@ -126,6 +126,9 @@ def lib():
     L.tmdnet_md_barostat_workspace_bytes.argtypes = [i64, C.POINTER(sz)]
     L.tmdnet_md_barostat.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, f64, f64, f64, f64, f64,
                                      u64, vp, vp, vp]
+    L.tmdnet_md_constraints_workspace_bytes.argtypes = [i64, i64, i64, C.POINTER(sz)]
+    L.tmdnet_md_advance_constrained.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, u64, vp, vp,
+                                                vp, vp, i64, i64, vp, vp, vp, vp, f64, i32]
     L.tmdnet_min_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
     L.tmdnet_min_reset.argtypes = [vp, vp, u64, f64, f64]
     L.tmdnet_min_advance.argtypes = [vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, f64, i32, f64, f64, f64, f64, f64, f64,

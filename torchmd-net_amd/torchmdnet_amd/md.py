@@ -4,7 +4,10 @@ One step is half-kick, drift, neighbour list + energy + forces, half-kick, optio
 integrator runs as HIP kernels (csrc/tn_md.hip, ``tmdnet_md_advance``) inside the captured graph, between the evaluations, so
 nothing is issued from the host between two steps.  With ``barostat=`` every step ends with an isotropic stochastic-cell-rescaling
 move per molecule (``tmdnet_md_barostat``): box, positions and velocities are scaled inside the graph (NPT).  The scheme, its
-rounding contract and the noise generator are documented with the C entries in include/tmdnet_amd.h and in DESIGN.md section 13."""
+rounding contract and the noise generator are documented with the C entries in include/tmdnet_amd.h and in DESIGN.md section 13.
+With ``constraints=`` (``TorchMD_Net.capture_md_constrained``) the integrator launches are those of csrc/tn_md_cons.hip
+(``tmdnet_md_advance_constrained``): SHAKE after the drift and RATTLE after the closing kick, one group of lanes per cluster of
+coupled constraints, still one launch between two evaluations."""
 import ctypes as C
 import math
 from typing import Optional
@@ -15,7 +18,9 @@ from torch import Tensor
 from torchmdnet_amd import _C
 from torchmdnet_amd.models.utils import _ptr, _stream_ptr
 
-MD_OPEN, MD_MIDDLE, MD_CLOSE = 0, 1, 2  # TMDNET_MD_* of include/tmdnet_amd.h
+MD_OPEN, MD_MIDDLE, MD_CLOSE, MD_PROJECT = 0, 1, 2, 3  # TMDNET_MD_* of include/tmdnet_amd.h
+#: limits of one cluster of coupled constraints (csrc/tn_md_cons_math.h: one lane per atom of a group of 8)
+MAX_CLUSTER_ATOMS, MAX_CLUSTER_CONSTRAINTS = 8, 12
 
 #: eV / (Angstrom amu) in Angstrom / fs^2: ``force_scale`` for energies in eV, lengths in Angstrom, masses in amu and dt in fs
 FORCE_SCALE_EV_A_AMU_FS = 9.648533e-3
@@ -23,6 +28,7 @@ FORCE_SCALE_EV_A_AMU_FS = 9.648533e-3
 BAR_IN_EV_PER_A3 = 6.2415091e-7
 
 _BAROSTAT_KEYS = ("pressure", "tau", "compressibility", "kT", "seed")
+_CONSTRAINT_KEYS = ("pairs", "lengths", "tol", "max_iter")
 
 
 def parse_barostat(barostat, thermostat):
@@ -48,6 +54,174 @@ def parse_barostat(barostat, thermostat):
     return out
 
 
+def build_clusters(pairs, n_atoms, batch=None, masses=None):
+    """Group the constraint pairs [C,2] (caller's atom order) into clusters, the connected components of the constraint graph, as
+    ``tmdnet_md_advance_constrained`` takes them.  Clusters come in the order of their smallest atom, the atoms of a cluster in
+    ascending order, its constraints in the caller's order; the atoms in no constraint follow, 8 to a cluster without constraints.
+    -> dict of CPU tensors: ``cluster_atoms`` [n_clusters,8] int32 (-1: no atom), ``cluster_offsets`` [n_clusters+1] int32,
+    ``constraint_ends`` [C,2] int32 (positions in the cluster's row), ``order`` [C] int64 (table row -> row of ``pairs``), and
+    ``n_bound``, the number of clusters that have constraints.  Raises ValueError for an index out of range, i == j, a duplicate
+    pair, a pair across two molecules, a constraint between two atoms of infinite mass and a cluster over 8 atoms or 12
+    constraints."""
+    n = int(n_atoms)
+    pairs = torch.as_tensor(pairs).detach().cpu()
+    if pairs.numel() == 0:
+        pairs = pairs.reshape(0, 2)
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype.is_floating_point:
+        raise ValueError(f"constraints: pairs must be an integer tensor [C,2], got {tuple(pairs.shape)} {pairs.dtype}")
+    pl = [(int(i), int(j)) for i, j in pairs.tolist()]
+    bl = None if batch is None else torch.as_tensor(batch).detach().cpu().tolist()
+    ml = None if masses is None else torch.as_tensor(masses).detach().cpu().reshape(-1).tolist()
+    parent = list(range(n))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    seen = set()
+    for c, (i, j) in enumerate(pl):
+        if not (0 <= i < n and 0 <= j < n):
+            raise ValueError(f"constraints: pair {c} = ({i}, {j}) has an index outside 0..{n - 1}")
+        if i == j:
+            raise ValueError(f"constraints: pair {c} = ({i}, {j}) constrains an atom to itself")
+        key = (min(i, j), max(i, j))
+        if key in seen:
+            raise ValueError(f"constraints: pair {c} = ({i}, {j}) is a duplicate")
+        seen.add(key)
+        if bl is not None and bl[i] != bl[j]:
+            raise ValueError(f"constraints: pair {c} = ({i}, {j}) joins molecules {bl[i]} and {bl[j]}")
+        if ml is not None and math.isinf(ml[i]) and math.isinf(ml[j]):
+            raise ValueError(f"constraints: pair {c} = ({i}, {j}) joins two atoms of infinite mass")
+        ri, rj = find(i), find(j)
+        if ri != rj:
+            parent[max(ri, rj)] = min(ri, rj)  # the root is the component's smallest atom
+    members, rows = {}, {}
+    for a in sorted({a for p in pl for a in p}):
+        members.setdefault(find(a), []).append(a)
+    for c, (i, j) in enumerate(pl):
+        rows.setdefault(find(i), []).append(c)
+    atoms, offsets, ends, order = [], [0], [], []
+    for root in sorted(members):
+        mem, cons = members[root], rows[root]
+        if len(mem) > MAX_CLUSTER_ATOMS or len(cons) > MAX_CLUSTER_CONSTRAINTS:
+            raise ValueError(f"constraints: the cluster of atom {root} has {len(mem)} atoms and {len(cons)} constraints (atoms {mem}); "
+                             f"a cluster holds at most {MAX_CLUSTER_ATOMS} atoms and {MAX_CLUSTER_CONSTRAINTS} constraints")
+        local = {a: l for l, a in enumerate(mem)}
+        atoms.append(mem + [-1] * (MAX_CLUSTER_ATOMS - len(mem)))
+        for c in cons:
+            ends.append([local[pl[c][0]], local[pl[c][1]]])
+            order.append(c)
+        offsets.append(len(ends))
+    n_bound = len(atoms)
+    bound = {a for p in pl for a in p}
+    free = [a for a in range(n) if a not in bound]
+    for k in range(0, len(free), MAX_CLUSTER_ATOMS):
+        mem = free[k:k + MAX_CLUSTER_ATOMS]
+        atoms.append(mem + [-1] * (MAX_CLUSTER_ATOMS - len(mem)))
+        offsets.append(len(ends))
+    return dict(cluster_atoms=torch.tensor(atoms, dtype=torch.int32).reshape(-1, MAX_CLUSTER_ATOMS),
+                cluster_offsets=torch.tensor(offsets, dtype=torch.int32),
+                constraint_ends=torch.tensor(ends, dtype=torch.int32).reshape(-1, 2),
+                order=torch.tensor(order, dtype=torch.int64), n_bound=n_bound)
+
+
+def constraint_residuals(pos, pairs, lengths, tol):
+    """Host check (fp64, one read-back): relative residual | |x_i - x_j| - d | / d of every pair and the bound it has to meet,
+    tol + 2 * 2^-23 * max|x| / d - the second term is the worst case of rounding the six coordinates to fp32.  -> (res, bound) [C]"""
+    x = pos.detach().to(device="cpu", dtype=torch.float64)
+    pairs = pairs.detach().cpu()
+    d = lengths.detach().to(device="cpu", dtype=torch.float64)
+    xi, xj = x[pairs[:, 0]], x[pairs[:, 1]]
+    res = ((xi - xj).norm(dim=1) - d).abs() / d
+    big = torch.maximum(xi.abs().amax(1), xj.abs().amax(1))
+    return res, float(tol) + 2.0 * 2.0 ** -23 * big / d
+
+
+def _check_positions(pos, con):
+    if con["pairs"].shape[0] == 0:
+        return
+    res, bound = constraint_residuals(pos, con["pairs"], con["lengths"], con["tol"])
+    over = res - bound
+    over = torch.where(torch.isnan(over), torch.full_like(over, float("inf")), over)
+    if bool((over > 0).any()):
+        c = int(over.argmax())
+        i, j = con["pairs"][c].tolist()
+        raise ValueError(f"constraints: the positions do not satisfy the constraints; worst is pair {c} = ({i}, {j}): "
+                         f"|r| / d - 1 = {float(res[c]):.3e} against a bound of {float(bound[c]):.3e} (d = {float(con['lengths'][c]):.6g})")
+
+
+def prepare_constraints(constraints, pos, batch, masses, n_mol):
+    """``constraints=dict(pairs=, lengths=None, tol=1e-6, max_iter=64)`` -> everything ``DeviceMD`` needs, on the host, before
+    anything is staged: the clusters (``build_clusters``), the lengths (measured from ``pos`` in fp64 when None), the degrees of
+    freedom per molecule, and the check that ``pos`` satisfies the constraints.  Raises ValueError."""
+    con = dict(constraints)
+    unknown = set(con) - set(_CONSTRAINT_KEYS)
+    if unknown:
+        raise ValueError(f"constraints: unknown keys {sorted(unknown)} ({', '.join(_CONSTRAINT_KEYS)})")
+    if "pairs" not in con:
+        raise ValueError("constraints: 'pairs' is required")
+    tol, max_iter = float(con.get("tol", 1e-6)), int(con.get("max_iter", 64))
+    if not tol > 0 or max_iter < 1:
+        raise ValueError(f"constraints: tol must be positive and max_iter at least 1, got tol={tol}, max_iter={max_iter}")
+    n = int(pos.shape[0])
+    m64 = torch.as_tensor(masses).detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+    if m64.numel() != n:
+        raise ValueError(f"masses must have one entry per atom ({n}), got {m64.numel()}")
+    b_cpu = batch.detach().cpu()
+    pairs = torch.as_tensor(con["pairs"]).detach().cpu()
+    out = build_clusters(pairs, n, b_cpu, m64)
+    pairs = pairs.reshape(-1, 2).to(torch.int64)
+    x = pos.detach().to(device="cpu", dtype=torch.float64)
+    if con.get("lengths") is None:
+        lengths = (x[pairs[:, 0]] - x[pairs[:, 1]]).norm(dim=1)
+    else:
+        lengths = torch.as_tensor(con["lengths"]).detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+        if lengths.numel() != pairs.shape[0]:
+            raise ValueError(f"constraints: lengths must have one entry per pair ({pairs.shape[0]}), got {lengths.numel()}")
+    if pairs.shape[0] and not bool((torch.isfinite(lengths) & (lengths > 0)).all()):
+        c = int((~(torch.isfinite(lengths) & (lengths > 0))).nonzero()[0])
+        raise ValueError(f"constraints: pair {c} = {tuple(pairs[c].tolist())} has length {float(lengths[c])}; lengths must be positive")
+    ndof = torch.zeros(n_mol, dtype=torch.int64).index_add_(0, b_cpu, 3 * torch.isfinite(m64).to(torch.int64))
+    if pairs.shape[0]:
+        ndof -= torch.bincount(b_cpu[pairs[:, 0]], minlength=n_mol)
+    out.update(pairs=pairs, lengths=lengths, tol=tol, max_iter=max_iter, ndof=ndof,
+               constraint_d2=(lengths * lengths)[out["order"]].contiguous())
+    _check_positions(pos, out)
+    return out
+
+
+def hydrogen_pairs(z, pos, batch=None, cutoff=1.3, rigid_water=False):
+    """Constraint pairs that freeze the X-H bonds (host, plain torch, off the hot path): every atom with z == 1 is paired with its
+    nearest heavy atom (z > 1) of the same molecule within ``cutoff``; a hydrogen with none is left free.  ``rigid_water``: the H-H
+    pair of every oxygen with exactly two hydrogens and no other atom within ``cutoff`` is added, which makes the water rigid.
+    Positions are taken as they are (unwrapped: a molecule must not be split across a periodic boundary).
+    -> pairs [C,2] int64 in the caller's atom order: (heavy, H) by ascending H, then (H, H) by ascending O."""
+    z = z.detach().cpu()
+    x = pos.detach().to(device="cpu", dtype=torch.float64)
+    b = torch.zeros_like(z) if batch is None else batch.detach().cpu()
+    hyd, heavy = (z == 1).nonzero().reshape(-1), (z > 1).nonzero().reshape(-1)
+    pairs, partners = [], {}
+    if hyd.numel() and heavy.numel():
+        for k in range(0, hyd.numel(), 4096):  # [4096, heavy] distances at a time
+            h = hyd[k:k + 4096]
+            d = torch.cdist(x[h], x[heavy])
+            d = torch.where(b[h][:, None] == b[heavy][None, :], d, torch.full_like(d, float("inf")))
+            dmin, arg = d.min(dim=1)
+            for hi, dm, a in zip(h.tolist(), dmin.tolist(), heavy[arg].tolist()):
+                if dm <= cutoff:
+                    pairs.append([a, hi])
+                    partners.setdefault(a, []).append(hi)
+    if rigid_water:
+        for o in sorted(a for a, hs in partners.items() if len(hs) == 2 and int(z[a]) == 8):
+            d = (x - x[o]).norm(dim=1)
+            near = ((d <= cutoff) & (b == b[o])).nonzero().reshape(-1).tolist()
+            if sorted(near) == sorted([o] + partners[o]):
+                pairs.append(sorted(partners[o]))
+    return torch.tensor(pairs, dtype=torch.int64).reshape(-1, 2)
+
+
 class DeviceMD:
     """The object ``TorchMD_Net.capture_md`` returns.  ``md(n)`` replays the captured graph n times (``steps_per_replay`` steps
     each) and returns ``md``; nothing is read back.  Static tensors, rewritten by every replay: ``pos``, ``vel``, ``forces``
@@ -55,10 +229,13 @@ class DeviceMD:
     unit of m v^2: divide by ``force_scale`` for the unit of ``epot``).  ``steps_done`` counts on the host; ``check()`` reads the
     device (one synchronisation).  With a barostat: ``box`` is the static box the graph reads AND writes (the caller's own object
     when it needed no conversion), and ``volume`` (before the move), ``pressure`` and ``scale`` (the fp32 factor mu) [K,B] are the
-    barostat's logs of the last replay's steps; ``forces`` stay the forces of the last evaluation, at the positions before the move."""
+    barostat's logs of the last replay's steps; ``forces`` stay the forces of the last evaluation, at the positions before the move.
+    With constraints (``prepare_constraints``): ``constraints`` is the dict of pairs, lengths, tol, max_iter and cluster tables,
+    ``ndof`` [B] int64 the degrees of freedom per molecule (three per atom of finite mass, minus the molecule's constraints), and
+    ``vel`` is projected onto the constraints at capture and at every ``reset``."""
 
     def __init__(self, model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
-                 barostat=None):
+                 barostat=None, constraints=None):
         L = _C.lib()
         dev = pos.device
         n = int(z.shape[0])
@@ -99,6 +276,12 @@ class DeviceMD:
         nbytes = C.c_size_t(0)
         L.tmdnet_md_workspace_bytes(n, n_mol, C.byref(nbytes))
         self._ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
+        self.constraints = constraints
+        if constraints is not None:
+            self._tables = tuple(constraints[k].to(dev).contiguous()
+                                 for k in ("cluster_atoms", "cluster_offsets", "constraint_ends", "constraint_d2"))
+            L.tmdnet_md_constraints_workspace_bytes(n, self._tables[0].shape[0], self._tables[2].shape[0], C.byref(nbytes))
+            self._cons_ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
         self.steps_done = 0
         with torch.cuda.device(dev):
             side = torch.cuda.Stream(device=dev)
@@ -108,7 +291,11 @@ class DeviceMD:
                     f0 = self._evaluate()[1]
                 self.forces = f0.clone()  # forces at the initial positions: what the first OPEN launch reads
                 L.tmdnet_md_reset(_stream_ptr(dev), _ptr(self._ws), 0)
+                if constraints is not None:  # velocities drawn from a Maxwell-Boltzmann distribution: consistent before step 1
+                    self._advance(MD_PROJECT, None, None, 0)
             torch.cuda.current_stream(dev).wait_stream(side)
+            if constraints is not None:
+                self.check()
             self.graph = torch.cuda.CUDAGraph()
             self._step_outputs = []  # the evaluations' output buffers live in the graph's pool; kept for the graph's lifetime
             with torch.cuda.graph(self.graph):
@@ -123,6 +310,14 @@ class DeviceMD:
                         self._barostat_move(k + 1 < K, out[1], out[2], k)
         self._engine, self._generation = model._engine, model._engine.generation
 
+    @property
+    def ndof(self) -> Tensor:
+        """[B] int64 (host): three degrees of freedom per atom of finite mass, minus the molecule's constraints"""
+        if self.constraints is not None:
+            return self.constraints["ndof"]
+        free = 3 * torch.isfinite(self.masses).to(torch.int64).cpu()
+        return torch.zeros(self.n_mol, dtype=torch.int64).index_add_(0, self.inputs[1].cpu(), free)
+
     def _evaluate(self):
         z, batch, box, q = self.inputs
         return self._model.energy_and_forces(z, self.pos, batch, box, q, self.n_mol, want_forces=True,
@@ -131,12 +326,28 @@ class DeviceMD:
     def _advance(self, phase, forces, energy, k):
         st = self._model._engine
         dev = self.pos.device
+        if self.constraints is not None:
+            return self._advance_constrained(phase, forces, energy, k)
         rc = _C.lib().tmdnet_md_advance(st.handle, _stream_ptr(dev), _ptr(st.graph_ws), _ptr(self._ws), self.n_atoms, self.n_mol, phase,
                                         _ptr(self.pos), _ptr(self.vel), _ptr(forces), _ptr(energy), _ptr(self.hk), _ptr(self.masses),
                                         _ptr(self.sigma), self.dt, self.c1, self.c2, self.seed, _ptr(self.inputs[1]),
                                         None if phase == MD_OPEN else _ptr(self.forces), _ptr(self.epot[k]), _ptr(self.ekin[k]))
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_md_advance: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
+
+    def _advance_constrained(self, phase, forces, energy, k):
+        st = self._model._engine
+        dev = self.pos.device
+        atoms, offsets, ends, d2 = self._tables
+        con = self.constraints
+        rc = _C.lib().tmdnet_md_advance_constrained(
+            st.handle, _stream_ptr(dev), _ptr(st.graph_ws), _ptr(self._ws), _ptr(self._cons_ws), self.n_atoms, self.n_mol, phase,
+            _ptr(self.pos), _ptr(self.vel), _ptr(forces), _ptr(energy), _ptr(self.hk), _ptr(self.masses), _ptr(self.sigma), self.dt,
+            self.c1, self.c2, self.seed, _ptr(self.inputs[1]), None if phase in (MD_OPEN, MD_PROJECT) else _ptr(self.forces),
+            _ptr(self.epot[k]), _ptr(self.ekin[k]), atoms.shape[0], ends.shape[0], _ptr(atoms), _ptr(offsets), _ptr(ends), _ptr(d2),
+            con["tol"], con["max_iter"])
+        if rc != _C.OK:
+            raise RuntimeError(f"tmdnet_md_advance_constrained: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
 
     def _barostat_move(self, open_next, forces, virial, k):
         st = self._model._engine
@@ -167,7 +378,10 @@ class DeviceMD:
         evaluation found more neighbours than ``max_num_neighbors`` allows: ``pos`` / ``vel`` / ``forces`` (and ``box``) and the
         counter are then those of the last valid step, and replays change nothing until ``reset``.  Raises a RuntimeError naming
         the barostat when one of its moves was unusable (zero volume, or a NaN from the virial): the state is frozen before that
-        move.  Returns the step counter."""
+        move.  Raises a RuntimeError naming the constraints when a cluster did not converge within ``max_iter`` sweeps (or met a
+        value that is not finite): that cluster is back at its saved state, the whole state is frozen and finite but is not a point
+        of the trajectory - other clusters may be half a step ahead -, and ``reset(pos=, vel=)`` is required.  Returns the step
+        counter."""
         host = (C.c_uint64 * 2)()
         dev = self.pos.device
         with torch.cuda.device(dev):
@@ -179,6 +393,13 @@ class DeviceMD:
         if int(host[1]) == 2:
             raise RuntimeError(f"barostat: the move after step {int(host[0])} was not finite (zero volume, or a NaN in the virial or "
                                "the kinetic energy); the MD state is frozen before that move")
+        if int(host[1]) == 3:
+            bits = int(self._cons_ws.view(torch.int32).max().item()) if self.constraints is not None else 0
+            stage = " and ".join(n for b, n in ((1, "SHAKE (positions)"), (2, "RATTLE (velocities)")) if bits & b) or "an iteration"
+            raise RuntimeError(f"constraints: {stage} did not converge within max_iter={self.constraints['max_iter']} sweeps to "
+                               f"tol={self.constraints['tol']:g} after step {int(host[0])} (or met a value that is not finite); the MD "
+                               "state is frozen and finite but is not a point of the trajectory (other clusters may be half a step "
+                               "ahead): reset(pos=, vel=) is required")
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_md_status failed (code {rc})")
         return int(host[0])
@@ -186,9 +407,21 @@ class DeviceMD:
     def reset(self, pos: Optional[Tensor] = None, vel: Optional[Tensor] = None, step: int = 0, box: Optional[Tensor] = None):
         """New positions and / or velocities (copied into the static buffers), forces evaluated there, status cleared, device step
         counter and ``steps_done`` set to ``step`` (the Langevin noise is a function of (seed, step, atom)).  ``box`` is copied into
-        the static box (a barostat has scaled it since the capture)."""
+        the static box (a barostat has scaled it since the capture).  With constraints: new positions must satisfy them (ValueError
+        naming the worst pair, before anything is changed), and the velocities are projected onto them again.  After a cluster
+        did not converge (``check()`` named the constraints) the state is not a point of the trajectory, so both ``pos`` and ``vel``
+        are required: a reset without one of them raises RuntimeError and changes nothing."""
         self._check_fresh()
         dev = self.pos.device
+        if self.constraints is not None and (pos is None or vel is None):
+            host = (C.c_uint64 * 2)()
+            with torch.cuda.device(dev):
+                _C.lib().tmdnet_md_status(_stream_ptr(dev), _ptr(self._ws), host)
+            if int(host[1]) == 3:
+                raise RuntimeError("constraints: an iteration did not converge, so the MD state is not a point of the trajectory: "
+                                   "reset(pos=, vel=) needs both pos and vel")
+        if self.constraints is not None and pos is not None:
+            _check_positions(pos, self.constraints)
         if box is not None:
             if self.box is None:
                 raise ValueError("reset(box=...): this loop was captured without a box")
@@ -201,6 +434,11 @@ class DeviceMD:
         self.forces.copy_(f)
         with torch.cuda.device(dev):
             _C.lib().tmdnet_md_reset(_stream_ptr(dev), _ptr(self._ws), int(step))
+            if self.constraints is not None:
+                self._cons_ws.zero_()
+                self._advance(MD_PROJECT, None, None, 0)
         self.steps_done = int(step)
         self._check_fresh()  # the evaluation must not have re-created what the graph points into
+        if self.constraints is not None:
+            self.check()
         return self

@@ -1384,8 +1384,25 @@ class TorchMD_Net(nn.Module):
         of that step's evaluation; pressure in E / length^3 (``md.BAR_IN_EV_PER_A3``), compressibility in length^3 / E, ``kT``
         (default: the thermostat's; 0 = weak coupling) in E, ``seed`` default the thermostat's.  Needs a box per molecule ([3,3] for
         one molecule, [B,3,3] otherwise) and an architecture with a virial (not TensorNet2); logs in ``md.volume / pressure /
-        scale`` [K,B]."""
-        from torchmdnet_amd.md import DeviceMD, parse_barostat
+        scale`` [K,B].
+        Distance constraints (X-H bonds, rigid water): ``capture_md_constrained``, the same call with ``constraints=`` after these."""
+        return self.capture_md_constrained(z, pos, vel, masses, dt, batch, box, q, num_systems, steps_per_replay, force_scale,
+                                           thermostat, warmup, atom_weights, halo_exchange, barostat, None)
+
+    def capture_md_constrained(self, z: Tensor, pos: Tensor, vel: Tensor, masses: Tensor, dt: float, batch: Optional[Tensor] = None,
+                               box: Optional[Tensor] = None, q: Optional[Tensor] = None, num_systems: Optional[int] = None,
+                               steps_per_replay: int = 10, force_scale: float = 1.0, thermostat: Optional[dict] = None,
+                               warmup: int = 3, atom_weights=None, halo_exchange=None, barostat: Optional[dict] = None,
+                               constraints: Optional[dict] = None):
+        """``capture_md`` - its parameters in its order, with its meaning - plus ``constraints`` after them (None: ``capture_md``).
+        ``constraints=dict(pairs=, lengths=None, tol=1e-6, max_iter=64)``: holonomic distance constraints |x_i - x_j| = d by RATTLE
+        inside the graph (``tmdnet_md_advance_constrained``) - SHAKE after the drift, the velocity projection after the closing kick,
+        still one integrator launch between two evaluations.  ``pairs`` [C,2] int64 in the caller's atom order (``md.hydrogen_pairs``
+        makes them for X-H bonds and rigid water), ``lengths`` [C] (None: measured from ``pos`` in fp64).  The coupled constraints of
+        one cluster are limited to 8 atoms and 12 constraints; ``pos`` must satisfy the constraints; ``vel`` is projected onto them.
+        Every architecture; not together with ``barostat`` (the constraint forces' virial is not built).  ``md.constraints``,
+        ``md.ndof`` [B]; ``md.check()`` raises when an iteration did not converge."""
+        from torchmdnet_amd.md import DeviceMD, parse_barostat, prepare_constraints
 
         if not getattr(self.representation_model, "static_shapes", False):
             raise RuntimeError("capture_md() needs a model created with static_shapes=True")
@@ -1397,6 +1414,9 @@ class TorchMD_Net(nn.Module):
                                       "without it")
         if atom_weights is not None or halo_exchange is not None:
             raise NotImplementedError("capture_md has no HIP path with atom weights or the halo exchange (domain decomposition)")
+        if constraints is not None and barostat is not None:
+            raise NotImplementedError("capture_md has no HIP path with constraints and a barostat together: the virial of the "
+                                      "constraint forces is not built")
         if int(steps_per_replay) < 1:
             raise ValueError(f"steps_per_replay must be at least 1, got {steps_per_replay}")
         _require_cuda(pos, "capture_md")
@@ -1424,9 +1444,11 @@ class TorchMD_Net(nn.Module):
             staged = box.detach().to(device=dev, dtype=torch.float32).contiguous()
             # no conversion: the caller's own object, so that md.box IS the tensor the caller scales or reads
             box = box if staged.data_ptr() == box.data_ptr() and not box.requires_grad else staged
+        if constraints is not None:  # refused before anything is staged or captured
+            constraints = prepare_constraints(constraints, pos, batch, masses, n_mol)
         q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).contiguous()
         return DeviceMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
-                        barostat)
+                        barostat, constraints)
 
     def capture_minimize(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
                          q: Optional[Tensor] = None, num_systems: Optional[int] = None, steps_per_replay: int = 10,
