@@ -155,7 +155,10 @@ const char* tmdnet_param_name(const tmdnet_model* m, int idx, int64_t* numel);
  * environment disables the tables (direct GEMMs every step).
  * Options: "edge_table_min_pairs"; "pair_rows_bf16" (Equivariant Transformer handle only; 1: the per-pair distance-filter
  * rows silu(dk_proj phi) | silu(dv_proj phi) and their d/dd - reference torchmd_et.py:375-415 - are written by the table
- * interpolation as bf16 and widened when the attention sweeps load them; products and sums stay fp32; default 0).  Info: "edge_table_T" (0 = off), "edge_table_err_value", "edge_table_err_slope"
+ * interpolation as bf16 and widened when the attention sweeps load them; products and sums stay fp32; 2: a developer and test mode - the rows are rounded by the same conversion and widened back into
+ * fp32 rows, so the fp32-row sweeps run on the values the bf16-row sweeps read, and the sweep generation is chosen with the bf16
+ * rows' tile-fill threshold; default 0; tmdnet_get_info returns the value set).  tmdnet_debug_tensor "dkv<l>" / "tkv<l>" copy layer l's
+ * value / tangent rows of the last call: (pairs + 1) * Wd floats, or half as many floats holding the raw bf16 pairs with option 1.  Info: "edge_table_T" (0 = off), "edge_table_err_value", "edge_table_err_slope"
  * (measured at the midpoints), "edge_table_min_pairs".
  * "recompute_pair_rows" (TensorNet handle; default 0): 1 = the message sweeps interpolate a layer's per-pair row from its table
  * themselves (12 table loads per edge instead of 3, or 6 in the reverse sweep) and the rows w^l, d w^l / dd, the distance

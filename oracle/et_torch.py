@@ -27,9 +27,33 @@ def lin(x, sd, key, bias=True):
     return Fn.linear(x, sd[key + ".weight"], sd[key + ".bias"] if bias and (key + ".bias") in sd else None)
 
 
+def bf16_rne(x: Tensor) -> Tensor:
+    """x rounded to the nearest bf16 value (ties to even) by way of fp32, as the engine's row store does; same dtype as x."""
+    return x.float().bfloat16().to(x.dtype)
+
+
+def rounded_filter_rows(sd, key, d, means, betas, lo, up, rnd=None):
+    """The engine's stored pair rows of one projection (``pair_storage="bf16"``): value silu(proj phi(d)) and tangent d/dd of it,
+    each rounded on its own (``rnd``, default ``bf16_rne``), put back together as a function of d whose value is the rounded value
+    and whose derivative is the rounded tangent.  The tangent is a forward-mode derivative (jvp along ones: the rows depend on
+    their own pair's distance only), not autograd's."""
+    rnd = bf16_rne if rnd is None else rnd
+    d0 = d.detach()
+    val, tan = torch.func.jvp(lambda t: Fn.silu(lin(expnorm_rbf(t, means, betas, lo, up), sd, key)), (d0,), (torch.ones_like(d0),))
+    return rnd(val) + rnd(tan) * (d - d0)[:, None]
+
+
 def et_representation(sd: Dict[str, Tensor], hp: dict, z: Tensor, pos: Tensor, batch: Tensor, box: Optional[Tensor] = None,
-                      return_intermediates: bool = False):
-    """TorchMD_ET.forward (torchmdnet/models/torchmd_et.py:188-221) -> x [N,F], vec [N,3,F]."""
+                      return_intermediates: bool = False, pair_rows: str = "fp32"):
+    """TorchMD_ET.forward (torchmdnet/models/torchmd_et.py:188-221) -> x [N,F], vec [N,3,F].
+
+    ``pair_rows="bf16"`` restates the engine's reduced-precision storage of the per-pair filter rows: in every layer and for every
+    pair, self pairs included, the forward pass uses bf16_rne(silu(dk_proj phi(d))) and bf16_rne(silu(dv_proj phi(d))), and the
+    gradient with respect to d uses bf16_rne(d/dd of those rows) (``rounded_filter_rows``).  Value and tangent are rounded
+    independently, so the forces of this mode are NOT the gradient of its (rounded) energy - they are what the engine computes.
+    The neighbour embedding's filter is never stored as bf16 and stays unrounded.  ``"fp32"`` (default): no rounding.  A callable
+    takes the place of ``bf16_rne`` (tests: the identity, a perturbed rounding)."""
+    assert pair_rows in ("fp32", "bf16") or callable(pair_rows), pair_rows
     R = "representation_model."
     F, H = hp["hidden_channels"], hp["num_heads"]
     hd = F // H
@@ -38,7 +62,8 @@ def et_representation(sd: Dict[str, Tensor], hp: dict, z: Tensor, pos: Tensor, b
     x = sd[R + "embedding.weight"][z]  # :195
     # :197 OptimizedDistance(loop=True): self loops, both directions; edge_vec = pos[ei0] - pos[ei1]
     edge_index, d, vec_ij = neighbor_pairs(pos, batch, lo, up, box=box, loop=True)
-    phi = expnorm_rbf(d, sd[R + "distance_expansion.means"], sd[R + "distance_expansion.betas"], lo, up)  # :205
+    means, betas = sd[R + "distance_expansion.means"], sd[R + "distance_expansion.betas"]
+    phi = expnorm_rbf(d, means, betas, lo, up)  # :205
     mask = edge_index[0] != edge_index[1]
     rhat = torch.where(mask[:, None], vec_ij / torch.where(mask, d, torch.ones_like(d))[:, None], torch.zeros_like(vec_ij))  # :206-207
     C = cosine_cutoff(d, lo, up)
@@ -61,8 +86,12 @@ def et_representation(sd: Dict[str, Tensor], hp: dict, z: Tensor, pos: Tensor, b
         v = lin(xt, sd, Lp + "v_proj").reshape(-1, H, 3 * hd)
         vec1, vec2, vec3 = torch.split(lin(vec, sd, Lp + "vec_proj", bias=False), F, dim=-1)
         vec_dot = (vec1 * vec2).sum(dim=1)
-        dk = Fn.silu(lin(phi, sd, Lp + "dk_proj")).reshape(-1, H, hd) if (Lp + "dk_proj.weight") in sd else None
-        dv = Fn.silu(lin(phi, sd, Lp + "dv_proj")).reshape(-1, H, 3 * hd) if (Lp + "dv_proj.weight") in sd else None
+        if pair_rows != "fp32":
+            rows = lambda key: rounded_filter_rows(sd, key, d, means, betas, lo, up, None if pair_rows == "bf16" else pair_rows)
+        else:
+            rows = lambda key: Fn.silu(lin(phi, sd, key))
+        dk = rows(Lp + "dk_proj").reshape(-1, H, hd) if (Lp + "dk_proj.weight") in sd else None
+        dv = rows(Lp + "dv_proj").reshape(-1, H, 3 * hd) if (Lp + "dv_proj.weight") in sd else None
         # message (:376-415)
         qi, kj, vj, vecj = q[tgt], k[src], v[src], vec.reshape(-1, 3, H, hd)[src]
         attn = (qi * kj).sum(-1) if dk is None else (qi * kj * dk).sum(-1)
@@ -111,9 +140,10 @@ def gated_block(sd, pre, x, v, scalar_act):
     return xo, vo
 
 
-def energy(sd, hp, z, pos, batch, box=None, num_systems=None, atomref=None):
-    """TorchMD_Net.forward with EquivariantScalar (model.py:530-631, output_modules.py:120-163)."""
-    x, v = et_representation(sd, hp, z, pos, batch, box)
+def energy(sd, hp, z, pos, batch, box=None, num_systems=None, atomref=None, pair_rows="fp32"):
+    """TorchMD_Net.forward with EquivariantScalar (model.py:530-631, output_modules.py:120-163).  ``pair_rows``: see
+    ``et_representation``."""
+    x, v = et_representation(sd, hp, z, pos, batch, box, pair_rows=pair_rows)
     O = "output_model.output_network."
     x, v = gated_block(sd, O + "0.", x, v, True)
     x, v = gated_block(sd, O + "1.", x, v, False)
@@ -126,9 +156,11 @@ def energy(sd, hp, z, pos, batch, box=None, num_systems=None, atomref=None):
     return y + sd.get("mean", torch.zeros((), dtype=e.dtype))
 
 
-def energy_and_forces(sd, hp, z, pos, batch, box=None, num_systems=None, atomref=None):
+def energy_and_forces(sd, hp, z, pos, batch, box=None, num_systems=None, atomref=None, pair_rows="fp32"):
+    """``pair_rows="bf16"``: the engine's bf16 pair rows (``et_representation``); the forces then use the rounded tangents and are
+    not the gradient of the rounded energy."""
     pos = pos.detach().clone().requires_grad_(True)
-    y = energy(sd, hp, z, pos, batch, box, num_systems, atomref)
+    y = energy(sd, hp, z, pos, batch, box, num_systems, atomref, pair_rows)
     (dy,) = torch.autograd.grad([y], [pos], grad_outputs=[torch.ones_like(y)])
     return y.detach(), -dy
 

@@ -1153,7 +1153,7 @@ int tmdnet_set_option(tmdnet_model* m, const char* name, double value) {
   }
   if (n == "pair_rows_bf16") {
     if (!m->et) return fail(m, TMDNET_ERR_INVALID, "pair_rows_bf16 applies to the Equivariant Transformer handle only");
-    m->pair_bf16 = value != 0.0 ? 1 : 0;
+    m->pair_bf16 = value == 2.0 ? 2 : (value != 0.0 ? 1 : 0);  // 2: bf16 values in fp32 storage (developer / test mode)
     return TMDNET_OK;
   }
   if (n == "recompute_pair_rows") {

@@ -273,10 +273,11 @@ struct InterpArgs {
   float* out[8];        // [P + 1][R]
   float* dout[8];       // [P + 1][R] or null
   int ntab;
-  int out_bf16;         // 1: out / dout are [P + 1][R] bf16 rows (round to nearest even), not fp32
+  int out_bf16;         // 1: out / dout are [P + 1][R] bf16 rows (round to nearest even), not fp32; 2: fp32 rows holding those bf16 values
 };
 
-// one 4-channel piece of an output row: 16 bytes of fp32, or 8 bytes of bf16 (the ET's pair rows in reduced-precision storage)
+// one 4-channel piece of an output row: 16 bytes of fp32, or 8 bytes of bf16 (the ET's pair rows in reduced-precision storage),
+// or (2) 16 bytes of fp32 that hold the bf16 values
 __device__ __forceinline__ void store_piece(float* base, int64_t elem, float x, float y, float z, float w, int bf16) {
   if (bf16) {
     typedef __bf16 b2 __attribute__((ext_vector_type(2)));
@@ -284,7 +285,11 @@ __device__ __forceinline__ void store_piece(float* base, int64_t elem, float x, 
     union { b2 v; uint32_t u; } lo, hi;
     lo.v = __builtin_convertvector((f2){x, y}, b2);
     hi.v = __builtin_convertvector((f2){z, w}, b2);
-    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(base) + elem) = make_uint2(lo.u, hi.u);
+    if (bf16 == 2)  // the same conversion, widened back: what the sweeps read from the bf16 rows, in the fp32 layout
+      *reinterpret_cast<float4*>(base + elem) = make_float4(__uint_as_float(lo.u << 16), __uint_as_float(lo.u & 0xFFFF0000u),
+                                                            __uint_as_float(hi.u << 16), __uint_as_float(hi.u & 0xFFFF0000u));
+    else
+      *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(base) + elem) = make_uint2(lo.u, hi.u);
   } else {
     *reinterpret_cast<float4*>(base + elem) = make_float4(x, y, z, w);
   }

@@ -69,7 +69,9 @@ struct EtModel {
   tmdnet_et_hparams hp;
   EtParams P;
   EtBuffers last{};
-  int64_t lastN = 0;
+  int64_t lastN = 0, lastP = 0;
+  int last_rows = 0;      // 1: the last call stored its pair rows as bf16
+  bool last_tkv = false;  // the last call wrote the tangent rows
   bool has_last = false;
 };
 
@@ -572,8 +574,11 @@ int et_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, s
   // reduced-precision STORAGE of the per-pair filter rows (option "pair_rows_bf16", BASELINE configs[3] "bf16"): dkv / tkv are
   // written by the table interpolation as bf16 and widened to fp32 when the sweeps load them; every product and sum stays fp32.
   // Only with the tables (the value + tangent GEMMs write fp32 rows): otherwise the call silently keeps fp32 storage.
-  const int pbf = (m->pair_bf16 && use_tab) ? 1 : 0;
-  const double pB = pbf ? 2.0 : 4.0;  // bytes per stored pair-row element
+  // 2 (developer / test mode): the same rounding, widened back into fp32 rows - the sweeps run their fp32-row instantiations
+  // on the values the bf16 ones read, and the sweep generation is chosen with the bf16 mode's fill threshold
+  const int pbf = use_tab ? m->pair_bf16 : 0;
+  const int pst = pbf == 1 ? 1 : 0;  // the rows' storage type as the sweeps see it
+  const double pB = pst ? 2.0 : 4.0;  // bytes per stored pair-row element
   if (use_tab) {
     // all per-pair filters from the radial tables: one bucket sort of the pairs, one interpolation launch per row length
     std::vector<const float*> tabs;
@@ -630,7 +635,7 @@ int et_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, s
     EtAttnArgs& a = aa[l];
     a = EtAttnArgs{b.qkv[l], b.vec[l], b.dkv[l], b.tkv[l], b.C, b.dC, F, hd, Wd,
                    (hp.distance_influence & 1) ? 0 : -1, (hp.distance_influence & 2) ? ((hp.distance_influence & 1) ? F : 0) : -1,
-                   hp.vector_cutoff, 2 * (int64_t)P1, pbf, b.tile_open, b.tile_start, et_g16_max_tiles(N, B), b.erec};
+                   hp.vector_cutoff, 2 * (int64_t)P1, pst, b.tile_open, b.tile_start, et_g16_max_tiles(N, B), b.erec};
     // algorithmic bytes (every distinct tensor once): dkv [P+1, Wd], qkv [N,5F], vec [N,3F] in; xagg [N,F],
     // vagg [N,3F] out; edge indices
     float* const xagg_l = tc ? tc->Ch[l] : b.xagg;  // kept per layer when parameter gradients are wanted
@@ -802,6 +807,9 @@ int et_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g, void* ws, s
   }
   m->et->last = b;
   m->et->lastN = N;
+  m->et->lastP = P;
+  m->et->last_rows = pst;
+  m->et->last_tkv = want_forces && Wd > 0 && !tc;
   m->et->has_last = true;
   HIP_TRY(m, hipGetLastError());
   return TMDNET_OK;
@@ -826,6 +834,17 @@ int et_debug_tensor(tmdnet_model* m, hipStream_t s, const char* name, float* out
     if (l < 0 || l >= L) return fail(m, TMDNET_ERR_INVALID, "layer out of range");
     src = isx ? b.x[l + 1] : b.vec[l + 1];
     n = isx ? N * F : N * 3 * F;
+  }
+  else if (nm.rfind("dkv", 0) == 0 || nm.rfind("tkv", 0) == 0) {  // the per-layer pair rows: fp32, or raw bf16 pairs (half the floats)
+    const bool tan = nm[0] == 't';
+    const int64_t Wd = wd_of(m->et->hp);
+    char* end = nullptr;
+    const long l = std::strtol(nm.c_str() + 3, &end, 10);
+    if (end == nm.c_str() + 3 || *end || l < 0 || l >= L) return fail(m, TMDNET_ERR_INVALID, "layer out of range: " + nm);
+    if (Wd == 0) return fail(m, TMDNET_ERR_INVALID, "no pair rows without distance influence: " + nm);
+    if (tan && !m->et->last_tkv) return fail(m, TMDNET_ERR_STATE, "the last call wrote no tangent rows (energies only): " + nm);
+    src = tan ? b.tkv[l] : b.dkv[l];
+    n = (m->et->lastP + 1) * Wd / (m->et->last_rows ? 2 : 1);
   }
   if (!src) return fail(m, TMDNET_ERR_INVALID, "unknown tensor: " + nm);
   if (numel != n) return fail(m, TMDNET_ERR_INVALID, "wrong size for " + nm);

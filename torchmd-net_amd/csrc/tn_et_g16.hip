@@ -794,7 +794,7 @@ void launch_et_tile_prep(const Graph& g, int N, int B, const int64_t* batch, con
   const int max_tiles = et_g16_max_tiles(N, B);
   // directed edges per tile slot (64 x 64) below which the step takes the row sweeps (developer switch, in percent)
   static const int fill_env = getenv("TMDNET_ET_G16_MIN_FILL") ? atoi(getenv("TMDNET_ET_G16_MIN_FILL")) : -1;
-  const float min_fill = fill_env >= 0 ? 0.01f * (float)fill_env : (pair_bf16 ? 0.25f : 0.70f);
+  const float min_fill = fill_env >= 0 ? 0.01f * (float)fill_env : (pair_bf16 ? 0.25f : 0.70f);  // (pair_bf16 = 2, bf16 values in fp32 rows, chooses like the bf16 rows)
   launch_fill(reinterpret_cast<float*>(meta), 0.f, 2, s);
   hipLaunchKernelGGL(k_et_tile_pack, dim3(1), dim3(1024), 0, s, g, batch, N, max_tiles, min_fill, tile_start, meta);
   hipLaunchKernelGGL(k_et_tile_open, dim3((max_tiles + 3) / 4), dim3(256), 0, s, g, N, tile_start, meta);

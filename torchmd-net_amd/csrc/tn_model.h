@@ -220,7 +220,7 @@ struct tmdnet_model {
   int64_t chain_min_atoms = 4096;
   int chain_mask = 7;
   int chain_last = 0;
-  int pair_bf16 = 0;          // option "pair_rows_bf16" (Equivariant Transformer): per-pair filter rows stored as bf16
+  int pair_bf16 = 0;          // option "pair_rows_bf16" (Equivariant Transformer): per-pair filter rows stored as bf16; 2: rounded to bf16, stored as fp32
   bool tabs_pending = false;  // parameters changed since the radial tables were built: rebuilt by the next call that uses them
   int64_t tab_min_pairs = 1;  // developer / test switch (option "edge_table_min_pairs"): fewer pairs take the value + tangent GEMMs
   bool finalized = false;

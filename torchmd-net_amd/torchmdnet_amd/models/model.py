@@ -36,15 +36,15 @@ def create_model(args, prior_model=None, mean=None, std=None):
     key beyond the reference's: ``pair_storage`` = "fp32" (default) | "bf16" - Equivariant Transformer only: the per-pair
     distance-filter rows are STORED as bf16 between the kernels (the sweeps that stream them read half the bytes); all
     arithmetic stays fp32.  That is the "bf16" of BASELINE configs[3]; the reference has no bf16 mode to compare with
-    (models/utils.py:715), so its accuracy is stated against the fp32 oracle (tests/test_gpu_et.py)."""
+    (models/utils.py:715), so its accuracy is stated against the fp32 oracle (tests/test_gpu_et.py).  A third spelling,
+    "bf16-values", is a developer and test mode: the rows are rounded exactly as "bf16" rounds them and stored as fp32, so the
+    fp32-row kernels run on the values the bf16-row kernels read (no bandwidth gain; tests/test_gpu_et.py compares the two)."""
     model = _create_model(args, prior_model=prior_model, mean=mean, std=std)
-    storage = str(args.get("pair_storage", "fp32"))
-    if storage not in ("fp32", "bf16"):
-        raise ValueError(f"pair_storage must be 'fp32' or 'bf16', got {storage!r}")
-    if storage == "bf16" and not model._is_et():
-        raise NotImplementedError("pair_storage='bf16' applies to the Equivariant Transformer only")
-    model.pair_storage = storage
+    model.pair_storage = str(args.get("pair_storage", "fp32"))
     return model
+
+
+PAIR_STORAGE = {"fp32": 0.0, "bf16": 1.0, "bf16-values": 2.0}  # spelling -> engine option "pair_rows_bf16"
 
 
 # property heads (csrc/tn_heads.hip): head class -> engine head kind (tmdnet_set_output_head)
@@ -502,7 +502,7 @@ class TorchMD_Net(nn.Module):
         std = torch.scalar_tensor(1) if std is None else std
         self.register_buffer("std", std.to(dtype=dtype))
         self._engine = _EngineState()
-        self.pair_storage = "fp32"  # "bf16": Equivariant Transformer pair rows in reduced-precision storage (create_model)
+        self._pair_storage = "fp32"  # "bf16": Equivariant Transformer pair rows in reduced-precision storage (create_model)
         self.static_check = True  # static_shapes mode: poll the overflow flag after every non-captured call
         self.cell_list_min_atoms = 1024  # single periodic systems at least this large use the O(N) cell list
         # True: the outputs carry an autograd graph to the PARAMETERS: loss(y, F).backward() fills .grad of every weight - d y / d theta
@@ -641,6 +641,24 @@ class TorchMD_Net(nn.Module):
             fp.append(tuple(p.enable for p in self.prior_model))
         return tuple(fp)
 
+    @property
+    def pair_storage(self) -> str:
+        """ "fp32" | "bf16" | "bf16-values" (see ``create_model``).  Assigning it takes effect from the next call on, also on a model
+        whose engine is already uploaded; replays captured before keep the mode they were captured with."""
+        d = self.__dict__  # (a module pickled before the attribute became a property carries it under its public name)
+        return d.get("_pair_storage", d.get("pair_storage", "fp32"))
+
+    @pair_storage.setter
+    def pair_storage(self, storage):
+        storage = str(storage)
+        if storage not in PAIR_STORAGE:
+            raise ValueError(f"pair_storage must be one of {', '.join(repr(k) for k in PAIR_STORAGE)}, got {storage!r}")
+        if storage != "fp32" and not self._is_et():
+            raise NotImplementedError(f"pair_storage={storage!r} applies to the Equivariant Transformer only")
+        self._pair_storage = storage
+        if self._engine.handle is not None:  # the uploaded parameters stay: only the option changes
+            _C.lib().tmdnet_set_option(self._engine.handle, b"pair_rows_bf16", PAIR_STORAGE[storage])
+
     def _sync_engine(self):
         """(Re)create the library handle and upload the parameters when they changed."""
         st = self._engine
@@ -691,8 +709,8 @@ class TorchMD_Net(nn.Module):
         rc = L.tmdnet_finalize_params(handle)
         if rc != _C.OK:
             raise RuntimeError(L.tmdnet_last_error(handle).decode())
-        if getattr(self, "pair_storage", "fp32") == "bf16":
-            L.tmdnet_set_option(handle, b"pair_rows_bf16", 1.0)
+        if self.pair_storage != "fp32":
+            L.tmdnet_set_option(handle, b"pair_rows_bf16", PAIR_STORAGE[self.pair_storage])
         for name, value in getattr(st, "options", {}).items():
             L.tmdnet_set_option(handle, name.encode(), value)
         st.fingerprint = fp
@@ -1281,6 +1299,11 @@ class TorchMD_Net(nn.Module):
             raise RuntimeError("Found num_pairs > max_num_pairs, please increase max_num_pairs "
                                f"(found {int(counts[1])} edges for max_num_neighbors={self.representation_model.max_num_neighbors})")
         return st.counts
+
+    def graph_counts(self):
+        """(pairs P, directed edges incl. self loops E, 1 if `batch` was not sorted) of the last graph the host read back: every dynamic-shape
+        evaluation and ``check_overflow``; None before the first.  ``debug_tensor("dkv<l>", (P + 1, Wd))`` takes its P from here."""
+        return self._engine.counts
 
     def engine_info(self, name: str) -> float:
         """Library-side facts about the uploaded model, e.g. "edge_table_T" (0: radial tables off), "edge_table_err_value"."""
