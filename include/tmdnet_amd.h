@@ -619,6 +619,55 @@ int tmdnet_min_advance(tmdnet_model* m, void* stream, void* graph_ws, void* min_
  * state is that of step host[0]).  Synchronises the stream.  Returns TMDNET_ERR_OVERFLOW for status 1, TMDNET_ERR_STATE for 2. */
 int tmdnet_min_status(void* stream, void* min_ws, uint64_t host[2]);
 
+/* ---- Cell relaxation in the minimiser (csrc/tn_min.hip; additive exports, the ABI revision stays 10) ---------------------------
+ * ASE's UnitCellFilter scheme on top of the controller above, one per molecule: the box relaxes together with the atoms.  Row
+ * vectors, as for the virial.  State per molecule, fp64: the reference box H0 (the box at the reset), the deformation gradient D
+ * (I at the reset), its FIRE velocity V_D, c = cell_factor.  The box the evaluation reads is H = H0 D^T, its nine entries rounded to
+ * fp32 once; D32 = fp32(D).  State per atom, fp32: xt = x D^-T and its velocity vt; the position handed to the evaluation is
+ *     x_a = (xt_0 D32[a][0] + xt_1 D32[a][1]) + xt_2 D32[a][2]            (each product one rounded product, each sum one rounded sum)
+ * Generalised forces, with the D32 the positions were formed with:
+ *     atoms   Ft_b = (F_0 D32[0][b] + F_1 D32[1][b]) + F_2 D32[2][b]
+ *     cell    W_s = (W + W^T) / 2 from the step's virial;  V = |det box| of the fp32 box the evaluation read;
+ *             G = (W_s - pressure V I) D^-T  (D^-1 by cofactors);  = - d(E + pressure V) / dD at fixed xt
+ *             hydrostatic: G <- (tr G / 3) I;  constant_volume: G <- G - (tr G / 3) I;  then G <- mask o G, entry by entry
+ *     the three rows of G / c count as three more atoms with coordinates c D and velocity V_D.
+ * The sums vf, ff, vv, fmax2 of the atoms (from Ft and vt, reduced as above) get the three rows' fp64 terms added in the controller,
+ * so the convergence test and the max_step clamp see all N + 3 rows.  The controller is the one above; with its three fp32
+ * coefficients, widened, V_D <- c_v V_D + c_f G / c and D <- D + (d V_D) / c in fp64, and per atom vt <- c_v vt + c_f Ft,
+ * xt <- xt + d vt, x from the new D32.  A converged molecule changes neither D nor the box nor its atoms; a fixed atom has vt = 0,
+ * contributes to no sum and keeps xt, so it follows the cell affinely.  With mask = 0, D stays I and every product with D32 is exact:
+ * the run equals tmdnet_min_advance bit for bit.
+ * Status 2 is also latched, before anything of the step is written, for a virial entry that is not finite and for a box whose
+ * volume is zero (now, or after the move about to be made); tmdnet_min_status_cell says which.  The move saves xt, vt and per
+ * molecule D, V_D and the fp32 box; an overflowing evaluation puts all of them, the box and pos back (status 1). */
+/* bytes of `min_ws` for the entries below: tmdnet_min_workspace_bytes plus 540 bytes per molecule (ten arrays, each rounded up to 256 bytes) */
+int tmdnet_min_workspace_bytes_cell(int64_t n_atoms, int64_t n_mol, size_t* bytes);
+/* tmdnet_min_reset, and per molecule H0 = box, D = I, V_D = 0; per atom xt = pos.  box [n_mol, 9] fp32, deform and cell_vel
+ * [n_mol, 9] fp64, pos and xt [n_atoms, 3]. */
+int tmdnet_min_reset_cell(void* stream, void* min_ws, int64_t n_atoms, int64_t n_mol, uint64_t step0, double dt0, double alpha0,
+                          const float* box, double* deform, double* cell_vel, const float* pos, float* xt);
+/* tmdnet_min_advance - its 29 arguments in its order, with its meaning, but `vel` is vt and `pos` is written from xt - plus:
+ *   xt            [n_atoms, 3] the integrated coordinates.
+ *   box           [n_mol, 9] the box the evaluations read: rewritten by every move.
+ *   deform, cell_vel   [n_mol, 9] fp64: D and V_D.
+ *   virial        [n_mol, 9] of the evaluation before this launch (MIDDLE / CLOSE; may be NULL for OPEN).
+ *   cell_factor   [n_mol] fp64, each > 0.
+ *   mask          nine doubles on the HOST, read before the call returns: 0 drops the entry of G.
+ *   flags         bit 0 hydrostatic, bit 1 constant_volume (not both);  pressure in E / length^3.
+ *   log rows      stress [n_mol, 9] fp64 = -W_s / V, volume [n_mol] fp64, cell_force [n_mol, 9] fp64 = G / c; each may be NULL.
+ * The fmax log row includes the cell rows; the sums log row holds the atoms' sums (of Ft and vt), to which the controller adds the
+ * cell rows' terms from cell_force and V_D.  OPEN is two launches (the cell's part of the move, then the atoms). */
+int tmdnet_min_advance_cell(tmdnet_model* m, void* stream, void* graph_ws, void* min_ws, int64_t n_atoms, int64_t n_mol, int32_t phase,
+                            float* pos, float* vel, const float* forces, const float* energy, const uint8_t* fixed, const int64_t* batch,
+                            float* forces_keep, double dt_max, int32_t n_min, double f_inc, double f_dec, double alpha0, double f_alpha,
+                            double max_step, double fmax, float* epot_log_row, float* fmax_log_row, double* sums_log_row,
+                            float* coef_log_row, double* dt_log_row, double* alpha_log_row, int64_t* converged_log_row, float* xt,
+                            float* box, double* deform, double* cell_vel, const float* virial, const double* cell_factor,
+                            const double* mask, int32_t flags, double pressure, double* stress_log_row, double* volume_log_row,
+                            double* cell_force_log_row);
+/* tmdnet_min_status, and host[2] = what was unusable when status is 2: 1 a force sum, 2 the virial, 3 the volume of the box. */
+int tmdnet_min_status_cell(void* stream, void* min_ws, uint64_t host[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,12 @@ for 1 x 64 atoms, 256 x 64 atoms (bench.py's flagship batch) and the 192-atom pe
 Alternating blocks of (a) and (b) in one process, each block at least ``--seconds`` of stepping with the final synchronise inside
 the clock; median and min / max over ``--rounds`` blocks.  The random-weight potential is no force field, so the steps are kept
 tiny (dt, dt_max and max_step scaled down: the atoms must not travel) and fmax is far below what is reached: no molecule freezes
-and both legs do the full work at every step.  Writes profiles/minimize.json."""
+and both legs do the full work at every step.  Writes profiles/minimize.json.
+
+``--cell``: the cell relaxation instead, on the 192-atom water box with TensorNet and the Equivariant Transformer, K = 10, three legs:
+``c_cell_K10`` (``capture_minimize(cell=...)``), ``a_eager_cell`` (the loop a caller builds on ``capture(virial=True)``: FIRE and the
+UnitCellFilter algebra as eager torch ops, nothing read back) and ``b_fixed_K10`` (the fixed-box captured loop).  Writes
+profiles/minimize_cell.json."""
 import argparse
 import json
 import os
@@ -77,12 +82,117 @@ def eager_fire(torch, replay, batch, n_mol, fire, fmax):
     return step, s
 
 
+def eager_fire_cell(torch, replay, box, fire, fmax, pressure):
+    """-> step(): one FIRE step of ONE molecule and its cell (UnitCellFilter, cell_factor = N) as eager torch ops, then one launch of
+    the capture(virial=True) graph; `box` is the tensor that graph reads"""
+    dev = replay.pos.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    n = replay.pos.shape[0]
+    _, forces, virial = replay()
+    xt, vel = replay.pos.clone(), torch.zeros_like(replay.pos)
+    H0, eye = box.double().clone(), torch.eye(3, **f64)
+    s = dict(dt=torch.tensor(fire["dt"], **f64), alpha=torch.tensor(fire["alpha"], **f64), n_pos=torch.zeros((), dtype=torch.int64, device=dev),
+             done=torch.zeros((), dtype=torch.bool, device=dev), D=eye.clone(), VD=torch.zeros(3, 3, **f64))
+    zero = torch.zeros((), **f64)
+    upper = torch.triu(torch.ones(3, 3, **f64))  # the rotation gauge of capture_minimize(cell=...)
+
+    def step():
+        D32 = s["D"].float()
+        ft = forces @ D32
+        W = virial[0].double()
+        V = torch.linalg.det(box.double()).abs()
+        G = (0.5 * (W + W.T) - pressure * V * eye) @ torch.linalg.inv_ex(s["D"], check_errors=False).inverse.T * upper / n
+        vf = (vel * ft).sum().double() + (s["VD"] * G).sum()
+        ff = (ft * ft).sum().double() + (G * G).sum()
+        vv = (vel * vel).sum().double() + (s["VD"] * s["VD"]).sum()
+        fmax2 = torch.maximum((ft * ft).sum(1).max().double(), (G * G).sum(1).max())
+        s["done"] |= fmax2.sqrt() < fmax
+        down = vf > 0
+        c_v = torch.where(down, 1.0 - s["alpha"], zero)
+        mix = torch.where(down & (ff > 0) & (vv > 0), s["alpha"] * torch.sqrt(vv / ff.clamp_min(1e-300)), zero)
+        grow = down & (s["n_pos"] > fire["n_min"])
+        s["dt"] = torch.where(grow, (s["dt"] * fire["f_inc"]).clamp_max(fire["dt_max"]), torch.where(down, s["dt"], s["dt"] * fire["f_dec"]))
+        s["alpha"] = torch.where(grow, s["alpha"] * fire["f_alpha"], torch.where(down, s["alpha"], torch.full_like(zero, fire["alpha"])))
+        s["n_pos"] = torch.where(down, s["n_pos"] + 1, torch.zeros_like(s["n_pos"]))
+        c_f = mix + s["dt"]
+        n2 = c_v * c_v * vv + 2.0 * c_v * c_f * vf + c_f * c_f * ff
+        length = s["dt"] * torch.sqrt(n2.clamp_min(0.0))
+        d = s["dt"] * (fire["max_step"] / length.clamp_min(1e-300)).clamp_max(1.0)
+        moving = (~s["done"]).double()
+        c_v, c_f, d = c_v * moving, c_f * moving, d * moving
+        s["VD"] = c_v * s["VD"] + c_f * G
+        s["D"] = s["D"] + d * s["VD"] / n
+        vel.mul_(c_v.float()).add_(ft * c_f.float())
+        xt.add_(vel * d.float())
+        box.copy_((H0 @ s["D"].T).float())
+        torch.matmul(xt, s["D"].float().T, out=replay.pos)
+        replay()
+
+    return step, s
+
+
+def main_cell(a):
+    import torch
+
+    import __graft_entry__ as ge
+
+    ge.build_hip(verbose=False)
+    from torchmdnet_amd import workloads as W
+    from torchmdnet_amd.models.model import create_model
+
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)
+    K, fmax, pressure = 10, 1e-9, 0.0
+    fire = dict(dt=1e-4, dt_max=1e-3, n_min=5, f_inc=1.1, f_dec=0.5, alpha=0.1, f_alpha=0.99, max_step=1e-4)
+    archs = {"tensornet": dict(W.C2_ARGS, static_shapes=True, max_num_neighbors=128),
+             "equivariant-transformer": dict(W.C4_ARGS, static_shapes=True, max_num_neighbors=128, cutoff_upper=5.0, vector_cutoff=False)}
+    result = {"device": torch.cuda.get_device_name(dev), "system": "192-atom periodic water box", "steps_per_replay": K,
+              "seconds_per_block": a.seconds, "rounds": a.rounds, "fire": fire, "fmax": fmax, "pressure": pressure, "models": {}}
+    z, pos, box0 = W.water_box(n_side=4)
+    z, pos, batch, box0 = z.to(dev), pos.to(dev).float().contiguous(), torch.zeros_like(z).to(dev), box0.to(dev).float().contiguous()
+    for name, args in archs.items():
+        torch.manual_seed(0)
+        model = create_model(dict(args)).to(dev)
+        box_e = box0.clone()
+        replay = model.capture(z, pos, batch, box_e, virial=True)
+        replay(pos)
+        eager, state = eager_fire_cell(torch, replay, box_e, fire, fmax, pressure)
+        cell = model.capture_minimize(z, pos, batch=batch, box=box0.clone(), steps_per_replay=K, fmax=fmax, fire=fire,
+                                      cell=dict(pressure=pressure))
+        fixed = model.capture_minimize(z, pos, batch=batch, box=box0.clone(), steps_per_replay=K, fmax=fmax, fire=fire)
+        legs = {"a_eager_cell": (eager, 1), "c_cell_K10": (cell, K), "b_fixed_K10": (fixed, K)}
+        times = {k: [] for k in legs}
+        for _ in range(a.rounds):  # alternating blocks: every round visits every leg once
+            for k, (fn, spc) in legs.items():
+                times[k].append(_block(fn, spc, a.seconds, sync))
+        cell.check()
+        fixed.check()
+        entry = {k: {"ms_per_step": statistics.median(v), "min": min(v), "max": max(v)} for k, v in times.items()}
+        entry["n_atoms"] = int(z.shape[0])
+        entry["box_change_max"] = {"eager": float((box_e - box0).abs().max()), "capture_minimize": float((cell.box - box0).abs().max())}
+        entry["ratio_cell_over_eager"] = entry["c_cell_K10"]["ms_per_step"] / entry["a_eager_cell"]["ms_per_step"]
+        entry["ratio_cell_over_fixed"] = entry["c_cell_K10"]["ms_per_step"] / entry["b_fixed_K10"]["ms_per_step"]
+        entry["cell_not_slower_than_eager"] = entry["c_cell_K10"]["ms_per_step"] <= entry["a_eager_cell"]["ms_per_step"]
+        result["models"][name] = entry
+        print(name, json.dumps(entry), flush=True)
+        del replay, cell, fixed, legs
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "minimize.json"))
+    ap.add_argument("--cell", action="store_true", help="the cell relaxation on the water box (profiles/minimize_cell.json)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "minimize_cell.json" if a.cell else "minimize.json")
+    if a.cell:
+        return main_cell(a)
 
     import torch
 

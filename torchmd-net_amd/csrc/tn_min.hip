@@ -22,6 +22,13 @@
 // last move saved; when a sum of a molecule that still moves is not finite it latches status 2 before anything of that step is
 // written.  From then on every launch returns at once: positions, velocities, forces_keep, the logs and the step counter stay at
 // the last valid step until tmdnet_min_reset.  Nothing allocates or synchronises; everything is capturable.
+//
+// Cell relaxation (tmdnet_min_*_cell, the second half of this file): the same three launches on N + 3 rows per molecule.  The atoms
+// are integrated in xt = x D^-T, the three rows of the deformation gradient D count as three more atoms with coordinates c D and
+// force (W_s - p V I) D^-T / c from the step's virial, the controller's sums get their terms added, and the move rewrites the box
+// H0 D^T the next evaluation reads.  The scheme is stated with the entries in include/tmdnet_amd.h; the existing kernels are not
+// touched, so the fixed-box path issues the launches and produces the bits it did before.
+#include <cmath>
 #include <string>
 
 #include "tmdnet_amd.h"
@@ -316,6 +323,355 @@ __global__ void k_min_reset(MinState st, uint64_t step0, double dt0, double alph
   }
 }
 
+// ---- cell relaxation: the same three launches with nine more degrees of freedom per molecule ------------------------------------
+// The atoms' integrated state is xt = x D^-T and its velocity (`xt`, `vel`); `pos` is what the evaluation reads, x = xt D32^T.  D
+// and V_D are the caller's fp64 buffers, the box is the buffer the evaluation reads.  The workspace adds, per molecule: H0, what the
+// last move saved (D, V_D, the fp32 box), what the last control prepared (the next D, V_D, box and D32), and two D32: `d32`, which the
+// current positions were formed with, and `d32_prev`, which the positions before the last move were formed with.  A move (the
+// end of the controller in MIDDLE, k_min_cell_commit in OPEN) saves the current values, makes the prepared ones current and moves
+// d32 to d32_prev; the per-atom kernel then forms the generalised force with d32_prev and the new position with d32.
+struct MinCell {
+  double* H0;       // [B, 9] the reference box
+  double* D_keep;   // [B, 9] before the last move
+  double* VD_keep;  // [B, 9]
+  double* D_next;   // [B, 9] what the last control prepared
+  double* VD_next;  // [B, 9]
+  float* box_keep;  // [B, 9]
+  float* box_next;  // [B, 9]
+  float* d32;       // [B, 9]
+  float* d32_prev;  // [B, 9]
+  float* d32_next;  // [B, 9]
+};
+
+size_t min_cell_bytes(int64_t N, int64_t B) {
+  const size_t b = (size_t)(B > 0 ? B : 0);
+  return min_bytes(N, B) + 5 * min_align256(b * 9 * sizeof(double)) + 5 * min_align256(b * 9 * sizeof(float));
+}
+
+MinCell carve_min_cell(void* ws, int64_t N, int64_t B) {
+  char* p = reinterpret_cast<char*>(min_align256(reinterpret_cast<size_t>(ws))) + (min_bytes(N, B) - 256);  // behind MinState
+  const size_t b = (size_t)(B > 0 ? B : 0);
+  MinCell c;
+  double** d64[5] = {&c.H0, &c.D_keep, &c.VD_keep, &c.D_next, &c.VD_next};
+  for (auto q : d64) {
+    *q = reinterpret_cast<double*>(p);
+    p += min_align256(b * 9 * sizeof(double));
+  }
+  float** f32[5] = {&c.box_keep, &c.box_next, &c.d32, &c.d32_prev, &c.d32_next};
+  for (auto q : f32) {
+    *q = reinterpret_cast<float*>(p);
+    p += min_align256(b * 9 * sizeof(float));
+  }
+  return c;
+}
+
+// head[8] (header byte 32): which sum or input was unusable when status 2 was latched (tn_min::CELL_BAD_*)
+
+// grid (B, S) as k_min_reduce, on the generalised forces Ft = F D32 of the D32 the positions were formed with
+__global__ __launch_bounds__(kMinThreads) void k_min_reduce_cell(MinState st, MinCell cs, const int* __restrict__ counts,
+                                                                 const int* __restrict__ mstart, const int* __restrict__ mend, int N, int B,
+                                                                 int S, const int64_t* __restrict__ batch, const float* __restrict__ vel,
+                                                                 const float* __restrict__ forces, const uint8_t* __restrict__ fixed) {
+  __shared__ double sh[4][kMinThreads / 64];
+  if (st.head[2]) return;           // frozen
+  if (counts && counts[2]) return;  // overflowed: stale forces, the controller latches it
+  const int m = blockIdx.x, s = blockIdx.y;
+  const bool filter = counts ? counts[3] != 0 : batch != nullptr;
+  int a = 0, b = N;
+  if (counts && !filter) {
+    a = mstart[m];
+    b = mend[m];
+    a = a < 0 ? 0 : a;
+    b = b > N ? N : b;
+    b = b < a ? a : b;
+  }
+  float d32[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) d32[k] = cs.d32[m * 9 + k];
+  const int64_t len = b - a;
+  const int i0 = a + (int)(len * s / S), i1 = a + (int)(len * (s + 1) / S);
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = i0 + (int)threadIdx.x; i < i1; i += kMinThreads) {
+    if (filter && batch && batch[i] != m) continue;
+    float v[3], f[3], ft[3], t[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      v[d] = vel[i * 3 + d];
+      f[d] = forces[i * 3 + d];
+    }
+    tn_min::cell_atom_force(f, d32, ft);
+    tn_min::atom_terms(v, ft, fixed && fixed[i], t);
+    acc[0] += (double)t[0];
+    acc[1] += (double)t[1];
+    acc[2] += (double)t[2];
+    acc[3] = (double)t[1] > acc[3] ? (double)t[1] : acc[3];
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    acc[0] += __shfl_xor(acc[0], o, 64);
+    acc[1] += __shfl_xor(acc[1], o, 64);
+    acc[2] += __shfl_xor(acc[2], o, 64);
+    const double other = __shfl_xor(acc[3], o, 64);
+    acc[3] = other > acc[3] ? other : acc[3];
+  }
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sh[k][threadIdx.x >> 6] = acc[k];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* out = st.slices + ((int64_t)m * S + s) * 4;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = ((sh[k][0] + sh[k][1]) + sh[k][2]) + sh[k][3];
+    double mx = sh[3][0];
+#pragma unroll
+    for (int w = 1; w < kMinThreads / 64; ++w) mx = sh[3][w] > mx ? sh[3][w] : mx;
+    out[3] = mx;
+  }
+}
+
+struct MinCellCtlArgs {
+  MinCtlArgs base;
+  MinCell cs;
+  tn_min::CellParams cp;
+  int move;                   // 1: MIDDLE, the move follows in this launch
+  const float* virial;        // [B, 9] of the evaluation just made
+  float* box;                 // [B, 9] the box the evaluation reads
+  double* deform;             // [B, 9] D
+  double* cell_vel;           // [B, 9] V_D
+  const double* cell_factor;  // [B]
+  double* stress_row;         // [B, 9] or NULL
+  double* volume_row;         // [B] or NULL
+  double* cell_force_row;     // [B, 9] or NULL: G / c
+};
+
+// the prepared values become the current ones, the current ones the saved ones (one thread per molecule)
+__device__ __forceinline__ void min_cell_commit(const MinCell& cs, float* box, double* deform, double* cell_vel, int m) {
+  for (int k = 0; k < 9; ++k) {
+    const int j = m * 9 + k;
+    cs.D_keep[j] = deform[j];
+    cs.VD_keep[j] = cell_vel[j];
+    cs.box_keep[j] = box[j];
+    cs.d32_prev[j] = cs.d32[j];
+    deform[j] = cs.D_next[j];
+    cell_vel[j] = cs.VD_next[j];
+    box[j] = cs.box_next[j];
+    cs.d32[j] = cs.d32_next[j];
+  }
+}
+
+struct MinCellOut {  // what one control of one molecule produces
+  tn_min::FireState s;
+  double atoms[4], sums[4], Gc[9], V, stress[9], Dn[9], VDn[9];  // atoms: the atoms' sums; sums: with the cell rows
+  float coef[3], boxn[9], d32n[9];
+  int ret, why;
+};
+
+__device__ __forceinline__ void min_cell_eval(const MinCellCtlArgs& a, int m, bool fresh, int64_t step, MinCellOut* o) {
+  min_load(a.base, m, fresh, o->sums, &o->s);
+  for (int k = 0; k < 4; ++k) o->atoms[k] = o->sums[k];
+  float W[9], box[9], d32[9];
+  double H0[9], D[9], VD[9];
+  for (int k = 0; k < 9; ++k) {
+    const int j = m * 9 + k;
+    W[k] = a.virial[j];
+    box[k] = a.box[j];
+    d32[k] = a.cs.d32[j];
+    H0[k] = a.cs.H0[j];
+    D[k] = a.deform[j];
+    VD[k] = a.cell_vel[j];
+  }
+  o->ret = tn_min::cell_control(&o->s, a.base.p, a.cp, a.cell_factor[m], o->sums, W, box, d32, H0, D, VD, step, o->coef, o->Gc, &o->V,
+                                o->stress, o->Dn, o->VDn, o->boxn, o->d32n, &o->why);
+}
+
+// k_min_control with the cell rows: ONE block striding the molecules.  On an overflow it also puts D, V_D, the box and d32 back.
+__global__ __launch_bounds__(kMinThreads) void k_min_control_cell(MinCellCtlArgs a) {
+  __shared__ int bad;
+  const MinState& st = a.base.st;
+  if (st.head[2]) return;  // frozen
+  const bool fresh = st.head[3] != 0;
+  if (a.base.counts && a.base.counts[2]) {
+    if (!fresh)  // nothing was saved before the first control
+      for (int m = threadIdx.x; m < a.base.B; m += kMinThreads)
+        for (int k = 0; k < 9; ++k) {
+          const int j = m * 9 + k;
+          a.deform[j] = a.cs.D_keep[j];
+          a.cell_vel[j] = a.cs.VD_keep[j];
+          a.box[j] = a.cs.box_keep[j];
+          a.cs.d32[j] = a.cs.d32_prev[j];
+        }
+    __syncthreads();  // (every thread has read the status word)
+    if (threadIdx.x == 0) st.head[2] = 1u;
+    return;
+  }
+  const uint64_t step = min_step(st) + (fresh ? 0 : 1);
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  MinCellOut o;
+  int why = 0;
+  for (int m = threadIdx.x; m < a.base.B; m += kMinThreads) {
+    min_cell_eval(a, m, fresh, (int64_t)step, &o);
+    if (o.ret == tn_min::FIRE_UNUSABLE && o.why > why) why = o.why;
+  }
+  if (why) atomicMax(&bad, why);  // (an integer in LDS)
+  __syncthreads();
+  if (bad) {
+    if (threadIdx.x == 0) {
+      st.head[8] = (uint32_t)bad;
+      st.head[2] = 2u;
+    }
+    return;
+  }
+  for (int m = threadIdx.x; m < a.base.B; m += kMinThreads) {
+    min_cell_eval(a, m, fresh, (int64_t)step, &o);
+    st.dt[m] = o.s.dt;
+    st.alpha[m] = o.s.alpha;
+    st.n_pos[m] = o.s.n_pos;
+    st.conv[m] = o.s.converged_at;
+    for (int k = 0; k < 3; ++k) st.coef[m * 3 + k] = o.coef[k];
+    for (int k = 0; k < 9; ++k) {
+      const int j = m * 9 + k;
+      a.cs.D_next[j] = o.Dn[k];
+      a.cs.VD_next[j] = o.VDn[k];
+      a.cs.box_next[j] = o.boxn[k];
+      a.cs.d32_next[j] = o.d32n[k];
+      if (a.stress_row) a.stress_row[j] = o.stress[k];
+      if (a.cell_force_row) a.cell_force_row[j] = o.Gc[k];
+    }
+    if (a.volume_row) a.volume_row[m] = o.V;
+    if (a.base.energy && a.base.epot_row) a.base.epot_row[m] = a.base.energy[m];
+    if (a.base.fmax_row) a.base.fmax_row[m] = (float)sqrt(o.sums[3]);
+    if (a.base.sums_row)
+      for (int k = 0; k < 4; ++k) a.base.sums_row[(int64_t)m * 4 + k] = o.atoms[k];
+    if (a.base.coef_row)
+      for (int k = 0; k < 3; ++k) a.base.coef_row[(int64_t)m * 3 + k] = o.coef[k];
+    if (a.base.dt_row) a.base.dt_row[m] = o.s.dt;
+    if (a.base.alpha_row) a.base.alpha_row[m] = o.s.alpha;
+    if (a.base.conv_row) a.base.conv_row[m] = o.s.converged_at;
+    if (a.move) min_cell_commit(a.cs, a.box, a.deform, a.cell_vel, m);
+  }
+  if (threadIdx.x == 0) {
+    st.head[0] = (uint32_t)step;
+    st.head[1] = (uint32_t)(step >> 32);
+    st.head[3] = 0u;
+  }
+}
+
+// OPEN: the cell's part of the move from what the last control prepared, before the per-atom kernel
+__global__ __launch_bounds__(kMinThreads) void k_min_cell_commit(MinState st, MinCell cs, int B, float* box, double* deform,
+                                                                  double* cell_vel) {
+  const int m = blockIdx.x * kMinThreads + threadIdx.x;
+  if (m >= B || st.head[2] || st.head[3]) return;  // frozen, or straight after a reset: nothing is prepared yet
+  min_cell_commit(cs, box, deform, cell_vel, m);
+}
+
+struct MinCellAtomArgs {
+  MinAtomArgs base;  // vel is the velocity of xt
+  MinCell cs;
+  float* xt;
+};
+
+// k_min_atoms on xt: the generalised force from d32_prev, the update, then the position the evaluation reads from d32.  A fixed atom
+// keeps xt and so follows the cell; an atom of a converged molecule is not touched at all (its D does not change either).
+template <bool ACCEPT, bool MOVE>
+__global__ __launch_bounds__(kMinThreads) void k_min_atoms_cell(MinCellAtomArgs c) {
+  const MinAtomArgs& a = c.base;
+  const int i = blockIdx.x * kMinThreads + threadIdx.x;
+  if (i >= a.N) return;
+  const uint32_t status = a.st.head[2], fresh = a.st.head[3];
+  const int64_t m = a.batch ? a.batch[i] : 0;
+  const bool mol_ok = m >= 0 && m < a.B;
+  if (status) {
+    // the evaluation before this launch overflowed: xt and its velocity as saved, and the position they gave with the D32 of then
+    if (ACCEPT && status == 1u && !fresh && a.counts && a.counts[2] && mol_ok) {
+      float xt[3], x[3], d32[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) d32[k] = c.cs.d32_prev[m * 9 + k];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        xt[d] = a.st.x_keep[i * 3 + d];
+        c.xt[i * 3 + d] = xt[d];
+        a.vel[i * 3 + d] = a.st.v_keep[i * 3 + d];
+      }
+      if (a.st.conv[m] < 0) {  // (an atom of a converged molecule was never moved)
+        tn_min::cell_position(xt, d32, x);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) a.pos[i * 3 + d] = x[d];
+      }
+    }
+    return;
+  }
+  if (fresh) return;
+  float x[3], xt[3], v[3], f[3], ft[3], d32[9];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) f[d] = a.forces[i * 3 + d];
+  if (ACCEPT && a.forces_keep)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) a.forces_keep[i * 3 + d] = f[d];
+  if (MOVE) {
+    if (!mol_ok) return;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      xt[d] = c.xt[i * 3 + d];
+      v[d] = a.vel[i * 3 + d];
+      a.st.x_keep[i * 3 + d] = xt[d];
+      a.st.v_keep[i * 3 + d] = v[d];
+    }
+    if (a.st.conv[m] >= 0) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) a.vel[i * 3 + d] = 0.f;
+      return;
+    }
+    if (a.fixed && a.fixed[i]) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) a.vel[i * 3 + d] = 0.f;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) d32[k] = c.cs.d32_prev[m * 9 + k];
+      tn_min::cell_atom_force(f, d32, ft);
+      tn_min::atom_move(xt, v, ft, a.st.coef[m * 3 + 0], a.st.coef[m * 3 + 1], a.st.coef[m * 3 + 2]);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        c.xt[i * 3 + d] = xt[d];
+        a.vel[i * 3 + d] = v[d];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) d32[k] = c.cs.d32[m * 9 + k];
+    tn_min::cell_position(xt, d32, x);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) a.pos[i * 3 + d] = x[d];
+  }
+}
+
+// the header as k_min_reset; per molecule H0 = the box, D = I, V_D = 0, every saved and prepared value equal to the current one; per
+// atom xt = x
+__global__ __launch_bounds__(kMinThreads) void k_min_reset_cell(MinState st, MinCell cs, int N, int B, uint64_t step0, double dt0,
+                                                                 double alpha0, const float* box, double* deform, double* cell_vel,
+                                                                 const float* pos, float* xt) {
+  const int i = blockIdx.x * kMinThreads + threadIdx.x;
+  if (i == 0) {
+    st.head[0] = (uint32_t)step0;
+    st.head[1] = (uint32_t)(step0 >> 32);
+    st.head[2] = 0u;
+    st.head[3] = 1u;
+    st.head[8] = 0u;
+    st.start[0] = dt0;
+    st.start[1] = alpha0;
+  }
+  if (i < B)
+    for (int k = 0; k < 9; ++k) {
+      const int j = i * 9 + k;
+      const double e = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
+      cs.H0[j] = (double)box[j];
+      deform[j] = cs.D_keep[j] = cs.D_next[j] = e;
+      cell_vel[j] = cs.VD_keep[j] = cs.VD_next[j] = 0.0;
+      cs.box_keep[j] = cs.box_next[j] = box[j];
+      cs.d32[j] = cs.d32_prev[j] = cs.d32_next[j] = (float)e;
+    }
+  if (i < 3 * N) xt[i] = pos[i];
+}
+
 }  // namespace
 
 }  // namespace tn
@@ -420,6 +776,136 @@ int tmdnet_min_status(void* stream, void* min_ws, uint64_t host[2]) {
   if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
   host[0] = (uint64_t)head[0] | ((uint64_t)head[1] << 32);
   host[1] = head[2];
+  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
+}
+
+int tmdnet_min_workspace_bytes_cell(int64_t n_atoms, int64_t n_mol, size_t* bytes) {
+  if (!bytes || n_atoms < 0 || n_mol < 0 || n_atoms > INT32_MAX / 4 || n_mol > INT32_MAX / 16) return TMDNET_ERR_INVALID;
+  *bytes = min_cell_bytes(n_atoms, n_mol);
+  return TMDNET_OK;
+}
+
+int tmdnet_min_reset_cell(void* stream, void* min_ws, int64_t n_atoms, int64_t n_mol, uint64_t step0, double dt0, double alpha0,
+                          const float* box, double* deform, double* cell_vel, const float* pos, float* xt) {
+  if (!min_ws || !(dt0 > 0.0) || !(alpha0 >= 0.0) || !box || !deform || !cell_vel || n_atoms < 0 || n_atoms > INT32_MAX / 4 || n_mol < 1 ||
+      n_mol > INT32_MAX / 16 || (n_atoms > 0 && (!pos || !xt)))
+    return TMDNET_ERR_INVALID;
+  const int64_t threads = 3 * n_atoms > n_mol ? 3 * n_atoms : n_mol;
+  hipLaunchKernelGGL(k_min_reset_cell, dim3((unsigned)((threads + kMinThreads - 1) / kMinThreads)), dim3(kMinThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), carve_min(min_ws, n_atoms, n_mol), carve_min_cell(min_ws, n_atoms, n_mol),
+                     (int)n_atoms, (int)n_mol, step0, dt0, alpha0, box, deform, cell_vel, pos, xt);
+  return hipGetLastError() == hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
+}
+
+int tmdnet_min_advance_cell(tmdnet_model* m, void* stream, void* graph_ws, void* min_ws, int64_t n_atoms, int64_t n_mol, int32_t phase,
+                            float* pos, float* vel, const float* forces, const float* energy, const uint8_t* fixed, const int64_t* batch,
+                            float* forces_keep, double dt_max, int32_t n_min, double f_inc, double f_dec, double alpha0, double f_alpha,
+                            double max_step, double fmax, float* epot_log_row, float* fmax_log_row, double* sums_log_row,
+                            float* coef_log_row, double* dt_log_row, double* alpha_log_row, int64_t* converged_log_row, float* xt,
+                            float* box, double* deform, double* cell_vel, const float* virial, const double* cell_factor,
+                            const double* mask, int32_t flags, double pressure, double* stress_log_row, double* volume_log_row,
+                            double* cell_force_log_row) {
+  if (!min_ws || !pos || !vel || !forces || !xt || !box || !deform || !cell_vel || !cell_factor || !mask || n_atoms < 0 ||
+      n_atoms > INT32_MAX / 4 || n_mol < 1 || n_mol > INT32_MAX / 16)
+    return TMDNET_ERR_INVALID;
+  if (phase != TMDNET_MIN_OPEN && phase != TMDNET_MIN_MIDDLE && phase != TMDNET_MIN_CLOSE) return TMDNET_ERR_INVALID;
+  if (phase != TMDNET_MIN_OPEN && !virial) return TMDNET_ERR_INVALID;
+  if (graph_ws && !m) return TMDNET_ERR_INVALID;
+  if (!(fmax > 0.0) || !(dt_max > 0.0) || !(max_step > 0.0) || !(f_inc > 0.0) || !(f_dec > 0.0) || !(f_alpha > 0.0) || !(alpha0 >= 0.0) ||
+      n_min < 0 || !std::isfinite(pressure) || (flags & ~3) || (flags & 3) == 3)
+    return TMDNET_ERR_INVALID;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int N = (int)n_atoms, B = (int)n_mol;
+  const MinState st = carve_min(min_ws, n_atoms, n_mol);
+  const MinCell cs = carve_min_cell(min_ws, n_atoms, n_mol);
+  const int* counts = nullptr;
+  const int* mstart = nullptr;
+  const int* mend = nullptr;
+  if (graph_ws) {
+    const Graph g = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr);
+    counts = g.counts;
+    mstart = g.mstart;
+    mend = g.mend;
+  }
+  const dim3 block(kMinThreads);
+  if (phase != TMDNET_MIN_OPEN) {
+    const int S = min_slices(n_atoms, n_mol);
+    hipLaunchKernelGGL(k_min_reduce_cell, dim3(B, S), block, 0, s, st, cs, counts, mstart, mend, N, B, S, batch, vel, forces, fixed);
+    MinCellCtlArgs c;
+    c.base.B = B;
+    c.base.S = S;
+    c.base.p.dt_max = dt_max;
+    c.base.p.f_inc = f_inc;
+    c.base.p.f_dec = f_dec;
+    c.base.p.alpha0 = alpha0;
+    c.base.p.f_alpha = f_alpha;
+    c.base.p.max_step = max_step;
+    c.base.p.fmax = fmax;
+    c.base.p.n_min = n_min;
+    c.base.counts = counts;
+    c.base.energy = energy;
+    c.base.epot_row = epot_log_row;
+    c.base.fmax_row = fmax_log_row;
+    c.base.sums_row = sums_log_row;
+    c.base.coef_row = coef_log_row;
+    c.base.dt_row = dt_log_row;
+    c.base.alpha_row = alpha_log_row;
+    c.base.conv_row = converged_log_row;
+    c.base.st = st;
+    c.cs = cs;
+    for (int k = 0; k < 9; ++k) c.cp.mask[k] = mask[k] != 0.0 ? 1.0 : 0.0;
+    c.cp.pressure = pressure;
+    c.cp.hydrostatic = flags & 1;
+    c.cp.constant_volume = (flags >> 1) & 1;
+    c.move = phase == TMDNET_MIN_MIDDLE;
+    c.virial = virial;
+    c.box = box;
+    c.deform = deform;
+    c.cell_vel = cell_vel;
+    c.cell_factor = cell_factor;
+    c.stress_row = stress_log_row;
+    c.volume_row = volume_log_row;
+    c.cell_force_row = cell_force_log_row;
+    hipLaunchKernelGGL(k_min_control_cell, dim3(1), block, 0, s, c);
+  } else {
+    hipLaunchKernelGGL(k_min_cell_commit, dim3((B + kMinThreads - 1) / kMinThreads), block, 0, s, st, cs, B, box, deform, cell_vel);
+  }
+  if (N > 0) {
+    MinCellAtomArgs a;
+    a.base.N = N;
+    a.base.B = B;
+    a.base.pos = pos;
+    a.base.vel = vel;
+    a.base.forces = forces;
+    a.base.forces_keep = forces_keep;
+    a.base.fixed = fixed;
+    a.base.batch = batch;
+    a.base.counts = counts;
+    a.base.st = st;
+    a.cs = cs;
+    a.xt = xt;
+    const dim3 grid((N + kMinThreads - 1) / kMinThreads);
+    if (phase == TMDNET_MIN_OPEN)
+      hipLaunchKernelGGL((k_min_atoms_cell<false, true>), grid, block, 0, s, a);
+    else if (phase == TMDNET_MIN_MIDDLE)
+      hipLaunchKernelGGL((k_min_atoms_cell<true, true>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((k_min_atoms_cell<true, false>), grid, block, 0, s, a);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_min_advance_cell: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
+  return TMDNET_OK;
+}
+
+int tmdnet_min_status_cell(void* stream, void* min_ws, uint64_t host[3]) {
+  if (!min_ws || !host) return TMDNET_ERR_INVALID;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  uint32_t head[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (hipMemcpyAsync(head, carve_min(min_ws, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
+  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
+  host[0] = (uint64_t)head[0] | ((uint64_t)head[1] << 32);
+  host[1] = head[2];
+  host[2] = head[2] == 2 ? head[8] : 0;
   return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
 }
 

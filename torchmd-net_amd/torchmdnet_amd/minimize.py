@@ -4,7 +4,8 @@ FIRE (Bitzek et al., Phys. Rev. Lett. 97, 170201, 2006) in the form ASE ships - 
 to ``max_step`` - with one controller per molecule (replica): every molecule of a batch has its own time step and freezes at its own
 step.  One step is the per-atom update, neighbour list + energy + forces, the per-molecule sums and the controller; all of it runs
 as HIP kernels (csrc/tn_min.hip, ``tmdnet_min_advance``) inside the captured graph, so nothing is issued from the host between two
-steps.  The box is fixed.  The scheme and its rounding are documented with the C entries in include/tmdnet_amd.h and in DESIGN.md
+steps.  The box is fixed unless ``cell=`` is given: then it relaxes with the atoms (ASE's ``UnitCellFilter`` scheme,
+``tmdnet_min_advance_cell``).  The scheme and its rounding are documented with the C entries in include/tmdnet_amd.h and in DESIGN.md
 section 14."""
 import ctypes as C
 from typing import Optional
@@ -36,6 +37,38 @@ def parse_fire(fire):
     return out
 
 
+#: the keys of ``capture_minimize(cell=...)`` and their defaults
+CELL_DEFAULTS = dict(mask=None, hydrostatic=False, constant_volume=False, pressure=0.0, cell_factor=None)
+
+
+def parse_cell(cell):
+    """``cell=dict(...)`` -> every key of ``CELL_DEFAULTS`` present, ``mask`` a 3 x 3 list of 0.0 / 1.0.  Raises ValueError for an
+    unknown key, a mask that is not a symmetric 3 x 3 matrix of 0 / 1, ``hydrostatic`` together with ``constant_volume``, a pressure
+    that is not finite and a ``cell_factor`` that is not positive."""
+    c = dict(cell)
+    unknown = set(c) - set(CELL_DEFAULTS)
+    if unknown:
+        raise ValueError(f"cell: unknown keys {sorted(unknown)} ({', '.join(CELL_DEFAULTS)})")
+    out = dict(CELL_DEFAULTS, **c)
+    mask = torch.ones(3, 3) if out["mask"] is None else torch.as_tensor(out["mask"]).detach().cpu().to(torch.float64)
+    if tuple(mask.shape) != (3, 3) or not bool(((mask == 0) | (mask == 1)).all()):
+        raise ValueError(f"cell: mask must be a [3,3] matrix of 0 / 1, got {mask.tolist()}")
+    if not torch.equal(mask, mask.T):
+        raise ValueError(f"cell: mask must be symmetric, got {mask.tolist()}")
+    out["mask"] = [[float(v) for v in row] for row in mask.tolist()]
+    out["hydrostatic"], out["constant_volume"] = bool(out["hydrostatic"]), bool(out["constant_volume"])
+    if out["hydrostatic"] and out["constant_volume"]:
+        raise ValueError("cell: hydrostatic and constant_volume exclude each other (an isotropic strain changes the volume)")
+    out["pressure"] = float(out["pressure"])
+    if out["pressure"] != out["pressure"] or out["pressure"] in (float("inf"), float("-inf")):
+        raise ValueError(f"cell: pressure must be finite, got {out['pressure']}")
+    if out["cell_factor"] is not None:
+        out["cell_factor"] = float(out["cell_factor"])
+        if not out["cell_factor"] > 0:
+            raise ValueError(f"cell: cell_factor must be positive, got {out['cell_factor']}")
+    return out
+
+
 class DeviceMinimizer:
     """The object ``TorchMD_Net.capture_minimize`` returns.  ``opt(n)`` replays the captured graph n times (``steps_per_replay``
     steps each) and returns ``opt``; nothing is read back.  Static tensors, rewritten by every replay: ``pos`` [N,3]; ``forces``
@@ -43,9 +76,18 @@ class DeviceMinimizer:
     last replay; ``converged_at`` [B] int64, the step at which a molecule's ``fmax`` fell below the bound (-1: not yet; such a
     molecule no longer moves); ``step_size`` [B] fp64, the molecule's current FIRE time step.  ``sums`` [K,B,4] (v.F, F.F, v.v,
     max |F_i|^2), ``coef`` [K,B,3] (c_v, c_f, d of the move that follows) and ``alpha`` [B] are the controller's own logs, and
-    ``epot0 / fmax0 / coef0`` those of the start geometry.  ``steps_done`` counts on the host; ``check()`` reads the device."""
+    ``epot0 / fmax0 / coef0`` those of the start geometry.  ``steps_done`` counts on the host; ``check()`` reads the device.
 
-    def __init__(self, model, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, fire, fixed, warmup):
+    With ``cell=`` the box relaxes too.  ``box`` is the box the graph reads and rewrites ([3,3] for one molecule, [B,3,3] otherwise;
+    the caller's tensor when it needed no conversion); ``deform`` [B,3,3] fp64 is the deformation gradient D since the last reset,
+    ``box = H0 D^T``; ``stress`` [K,B,3,3] fp64 is -W_s / V of each evaluated step, ``volume`` [K,B] fp64 its V, ``cell_force``
+    [K,B,3,3] fp64 the cell rows' force G / cell_factor; ``fmax`` includes the cell rows, ``sums`` are the atoms' alone (the
+    controller adds the cell rows' terms); ``stress0 / volume0 / cell_force0`` belong to the start geometry.  The atoms' integrated state is ``pos D^-T``; ``vel`` is its velocity.  A fixed atom
+    keeps ``pos D^-T``: it follows the cell affinely.  The neighbour search's minimum image needs a lower-triangular box, so the
+    rotation of the cell is not a degree of freedom here: the entries of the cell force below the diagonal are dropped, D stays
+    upper triangular and ``H0 D^T`` lower triangular (a shear allowed by ``mask`` acts through the entry above the diagonal)."""
+
+    def __init__(self, model, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, fire, fixed, warmup, cell=None):
         L = _C.lib()
         dev = pos.device
         n = int(z.shape[0])
@@ -56,6 +98,7 @@ class DeviceMinimizer:
         if not self.fmax_bound > 0:
             raise ValueError(f"fmax must be positive, got {fmax}")
         self.inputs = (z, batch, box, q)  # what the graph reads, kept alive for as long as it can be replayed
+        self.cell = None if cell is None else parse_cell(cell)
         self.pos = pos.detach().to(torch.float32).clone().contiguous()
         self.vel = torch.zeros_like(self.pos)  # FIRE's velocity: the minimiser's own state
         self.fixed = None
@@ -76,14 +119,16 @@ class DeviceMinimizer:
         L.tmdnet_min_workspace_bytes(n, n_mol, C.byref(nbytes))
         self._ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
         self.steps_done = 0
+        if self.cell is not None:
+            self._stage_cell(box, batch)
         with torch.cuda.device(dev):
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
                 for _ in range(max(warmup, 1)):  # uploads parameters, sizes the workspaces, checks overflow
-                    e0, f0 = self._evaluate()
+                    e0, f0, *w0 = self._evaluate()
                 self.forces = f0.clone()
-                self._start(e0, f0)
+                self._start(e0, f0, *w0)
             torch.cuda.current_stream(dev).wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
             self._step_outputs = []  # the evaluations' output buffers live in the graph's pool; kept for the graph's lifetime
@@ -92,22 +137,76 @@ class DeviceMinimizer:
                 for k in range(K):
                     out = self._evaluate()
                     self._step_outputs.append(out)
-                    self._advance(MIN_MIDDLE if k + 1 < K else MIN_CLOSE, out[1], out[0], k)
+                    self._advance(MIN_MIDDLE if k + 1 < K else MIN_CLOSE, out[1], out[0], k, *out[2:])
         self._engine, self._generation = model._engine, model._engine.generation
+
+    def _stage_cell(self, box, batch):
+        """the cell's state and logs, and the workspace with room for it"""
+        dev, B, K = self.pos.device, self.n_mol, self.steps_per_replay
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.box = box
+        self._xt = self.pos.clone()  # pos D^-T: what is integrated
+        self.deform = torch.eye(3, **f64).repeat(B, 1, 1).contiguous()
+        self._cell_vel = torch.zeros((B, 3, 3), **f64)
+        self.stress, self.cell_force = torch.zeros((K, B, 3, 3), **f64), torch.zeros((K, B, 3, 3), **f64)
+        self.volume = torch.zeros((K, B), **f64)
+        self.stress0, self.cell_force0, self.volume0 = torch.zeros((B, 3, 3), **f64), torch.zeros((B, 3, 3), **f64), torch.zeros(B, **f64)
+        c = self.cell["cell_factor"]
+        if c is None:  # ASE's: the number of atoms (of that molecule)
+            self._cell_factor = torch.bincount(batch, minlength=B)[:B].clamp(min=1).to(torch.float64)
+        else:
+            self._cell_factor = torch.full((B,), c, **f64)
+        # the rotation gauge: only the entries on and above the diagonal move D, so that H0 D^T stays lower triangular
+        self._mask = (C.c_double * 9)(*[v if a <= b else 0.0 for a, row in enumerate(self.cell["mask"]) for b, v in enumerate(row)])
+        self._flags = int(self.cell["hydrostatic"]) | (int(self.cell["constant_volume"]) << 1)
+        nbytes = C.c_size_t(0)
+        _C.lib().tmdnet_min_workspace_bytes_cell(self.n_atoms, B, C.byref(nbytes))
+        self._ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
 
     def _evaluate(self):
         z, batch, box, q = self.inputs
+        if self.cell is not None:  # (energy, forces, virial): the gather sibling of the virial replaces the force gather
+            return self._model.energy_and_forces(z, self.pos, batch, box, q, self.n_mol, want_forces=True, want_virial=True)
         return self._model.energy_and_forces(z, self.pos, batch, box, q, self.n_mol, want_forces=True)
 
-    def _start(self, energy, forces):
+    def _start(self, energy, forces, virial=None):
         """reset, then the control of the start geometry: the first coefficients, and molecules that are converged as they stand"""
         dev = self.pos.device
-        rc = _C.lib().tmdnet_min_reset(_stream_ptr(dev), _ptr(self._ws), 0, self.fire["dt"], self.fire["alpha"])
+        if self.cell is not None:
+            rc = _C.lib().tmdnet_min_reset_cell(_stream_ptr(dev), _ptr(self._ws), self.n_atoms, self.n_mol, 0, self.fire["dt"],
+                                                self.fire["alpha"], _ptr(self.box), _ptr(self.deform), _ptr(self._cell_vel),
+                                                _ptr(self.pos), _ptr(self._xt))
+        else:
+            rc = _C.lib().tmdnet_min_reset(_stream_ptr(dev), _ptr(self._ws), 0, self.fire["dt"], self.fire["alpha"])
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_min_reset failed (code {rc})")
-        self._advance(MIN_CLOSE, forces, energy, None)
+        self._advance(MIN_CLOSE, forces, energy, None, virial)
 
-    def _advance(self, phase, forces, energy, k):
+    def _advance_cell(self, phase, forces, energy, k, virial):
+        st = self._model._engine
+        dev = self.pos.device
+        f = self.fire
+        if k is None:  # the start geometry
+            rows = (self.epot0, self.fmax0, self._sums0, self.coef0)
+            cell_rows = (self.stress0, self.volume0, self.cell_force0)
+        else:
+            rows = (self.epot[k], self.fmax[k], self.sums[k], self.coef[k])
+            cell_rows = (self.stress[k], self.volume[k], self.cell_force[k])
+        is_open = phase == MIN_OPEN
+        logs = [None] * 7 if is_open else [_ptr(t) for t in rows + (self.step_size, self.alpha, self.converged_at)]
+        cell_logs = [None] * 3 if is_open else [_ptr(t) for t in cell_rows]
+        rc = _C.lib().tmdnet_min_advance_cell(st.handle, _stream_ptr(dev), _ptr(st.graph_ws), _ptr(self._ws), self.n_atoms, self.n_mol,
+                                              phase, _ptr(self.pos), _ptr(self.vel), _ptr(forces), _ptr(energy), _ptr(self.fixed),
+                                              _ptr(self.inputs[1]), None if is_open else _ptr(self.forces), f["dt_max"], f["n_min"],
+                                              f["f_inc"], f["f_dec"], f["alpha"], f["f_alpha"], f["max_step"], self.fmax_bound, *logs,
+                                              _ptr(self._xt), _ptr(self.box), _ptr(self.deform), _ptr(self._cell_vel), _ptr(virial),
+                                              _ptr(self._cell_factor), self._mask, self._flags, self.cell["pressure"], *cell_logs)
+        if rc != _C.OK:
+            raise RuntimeError(f"tmdnet_min_advance_cell: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
+
+    def _advance(self, phase, forces, energy, k, virial=None):
+        if self.cell is not None:
+            return self._advance_cell(phase, forces, energy, k, virial)
         st = self._model._engine
         dev = self.pos.device
         f = self.fire
@@ -140,15 +239,25 @@ class DeviceMinimizer:
         """Read the device's step counter and status (one synchronisation).  Raises the reference's overflow RuntimeError when an
         evaluation found more neighbours than ``max_num_neighbors`` allows, and a RuntimeError naming the forces when a force sum
         was not finite: ``pos`` / ``forces``, the logs and the counter are then those of the last valid step, and replays change
-        nothing until ``reset``.  Returns the step counter."""
-        host = (C.c_uint64 * 2)()
+        nothing until ``reset``.  With ``cell=`` the error also names a virial that was not finite or a box without volume, and
+        ``box`` / ``deform`` are those of the last valid step as well.  Returns the step counter."""
+        host = (C.c_uint64 * 3)()
         dev = self.pos.device
         with torch.cuda.device(dev):
-            rc = _C.lib().tmdnet_min_status(_stream_ptr(dev), _ptr(self._ws), host)
+            if self.cell is not None:
+                rc = _C.lib().tmdnet_min_status_cell(_stream_ptr(dev), _ptr(self._ws), host)
+            else:
+                rc = _C.lib().tmdnet_min_status(_stream_ptr(dev), _ptr(self._ws), C.cast(host, C.POINTER(C.c_uint64)))
         if rc == _C.ERR_OVERFLOW:
             raise RuntimeError("Found num_pairs > max_num_pairs, please increase max_num_pairs "
                                f"(max_num_neighbors={self._model.representation_model.max_num_neighbors}; the minimiser is frozen at "
                                f"step {int(host[0])})")
+        if int(host[1]) == 2 and int(host[2]) == 2:
+            raise RuntimeError(f"minimiser: the virial after step {int(host[0])} is not finite; the state, the box included, is frozen "
+                               "at that step")
+        if int(host[1]) == 2 and int(host[2]) == 3:
+            raise RuntimeError(f"minimiser: the box after step {int(host[0])} has no volume, or the next move would leave it without "
+                               "one or not finite; the state, the box included, is frozen at that step")
         if int(host[1]) == 2:
             raise RuntimeError(f"minimiser: the forces after step {int(host[0])} are not finite (a NaN or an infinite force sum); the "
                                "state is frozen at that step")
@@ -156,18 +265,26 @@ class DeviceMinimizer:
             raise RuntimeError(f"tmdnet_min_status failed (code {rc})")
         return int(host[0])
 
-    def reset(self, pos: Optional[Tensor] = None):
+    def reset(self, pos: Optional[Tensor] = None, box: Optional[Tensor] = None):
         """New positions (copied into the static buffer), forces evaluated there, velocity zero, every molecule's controller back to
-        its start values, status cleared, step counters zero."""
+        its start values, status cleared, step counters zero.  With ``cell=``: ``box`` (copied into ``self.box``; None: the box as it
+        is) becomes the new reference box and ``deform`` the identity."""
         self._check_fresh()
         dev = self.pos.device
+        if box is not None:
+            if self.cell is None:
+                raise ValueError("reset(box=) needs a minimiser captured with cell=...: the box of this one is fixed")
+            new = box.detach().to(device=dev, dtype=torch.float32).reshape(self.box.shape)
+            if bool((torch.linalg.det(new.double()) == 0).any()):
+                raise ValueError("reset(box=): a box has no volume")
+            self.box.copy_(new)
         if pos is not None:
             self.pos.copy_(pos.detach().to(device=dev, dtype=torch.float32))
         self.vel.zero_()
-        e, f = self._evaluate()  # raises when these positions overflow
+        e, f, *w = self._evaluate()  # raises when these positions overflow
         self.forces.copy_(f)
         with torch.cuda.device(dev):
-            self._start(e, f)
+            self._start(e, f, *w)
         self.steps_done = 0
         self._check_fresh()  # the evaluation must not have re-created what the graph points into
         return self

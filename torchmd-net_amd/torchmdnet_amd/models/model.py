@@ -1476,18 +1476,27 @@ class TorchMD_Net(nn.Module):
     def capture_minimize(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
                          q: Optional[Tensor] = None, num_systems: Optional[int] = None, steps_per_replay: int = 10,
                          fmax: float = 0.05, fire: Optional[dict] = None, fixed: Optional[Tensor] = None, warmup: int = 3,
-                         atom_weights=None, halo_exchange=None):
+                         atom_weights=None, halo_exchange=None, cell: Optional[dict] = None):
         """Capture ``steps_per_replay`` steps of a FIRE geometry minimisation into ONE HIP graph (needs ``static_shapes=True``): per
         step the per-atom update, neighbour list + energy + forces, the per-molecule sums and the controller, all as HIP kernels
         between the evaluations (``tmdnet_min_advance``) - no host work between steps.  FIRE as ASE ships it, unit masses, one
         controller per molecule: every molecule of a batch has its own time step and stops moving at the step where its largest
         atomic force norm falls below ``fmax``.  ``fire`` overrides ASE's defaults ``dict(dt=0.1, dt_max=1.0, n_min=5, f_inc=1.1,
-        f_dec=0.5, alpha=0.1, f_alpha=0.99, max_step=0.2)``; ``fixed`` [N] marks atoms that never move.  The box is fixed (no cell
-        relaxation).  Works for every architecture ``capture`` serves.  Returns a ``torchmdnet_amd.minimize.DeviceMinimizer``:
+        f_dec=0.5, alpha=0.1, f_alpha=0.99, max_step=0.2)``; ``fixed`` [N] marks atoms that never move.  The box is fixed unless
+        ``cell`` is given.  Works for every architecture ``capture`` serves.  Returns a ``torchmdnet_amd.minimize.DeviceMinimizer``:
         ``opt(n)`` replays n times; ``opt.pos / forces``, ``opt.epot / fmax`` [K,B], ``opt.converged_at / step_size`` [B],
         ``opt.check()``, ``opt.reset(pos)``, ``opt.run(max_steps, check_every)``.  Inputs are staged and kept alive as in
-        ``capture``.  ``atom_weights`` / ``halo_exchange`` are accepted only to be refused."""
-        from torchmdnet_amd.minimize import DeviceMinimizer, parse_fire
+        ``capture``.  ``atom_weights`` / ``halo_exchange`` are accepted only to be refused.
+        ``cell=dict(mask=None, hydrostatic=False, constant_volume=False, pressure=0.0, cell_factor=None)`` relaxes the box together
+        with the atoms inside the graph (``tmdnet_min_advance_cell``): ASE's ``UnitCellFilter`` scheme, one deformation gradient per
+        molecule driven by the virial of every step towards ``pressure`` (E / length^3).  ``mask`` [3,3] of 0 / 1, symmetric, selects
+        the entries of the cell force that act (None: all); ``hydrostatic`` keeps the shape, ``constant_volume`` the volume;
+        ``cell_factor`` (None: the molecule's number of atoms) weighs the cell rows against the atoms.  Needs a box per molecule ([3,3]
+        for one molecule, [B,3,3] otherwise) and an architecture with a virial (not TensorNet2).  Then ``opt.box`` (the caller's tensor
+        when it needed no conversion), ``opt.deform`` [B,3,3], ``opt.stress`` [K,B,3,3] = -W_s / V, ``opt.volume`` [K,B],
+        ``opt.reset(pos=, box=)``; ``opt.fmax`` includes the cell rows.  A fixed atom follows the cell affinely.  ``cell=None`` is the
+        fixed-box path, unchanged."""
+        from torchmdnet_amd.minimize import DeviceMinimizer, parse_cell, parse_fire
 
         if not getattr(self.representation_model, "static_shapes", False):
             raise RuntimeError("capture_minimize() needs a model created with static_shapes=True")
@@ -1515,11 +1524,29 @@ class TorchMD_Net(nn.Module):
         if box is None and rm.distance.use_periodic:
             box = rm.distance.box
         dev = pos.device  # staged as in capture(): the graph records raw pointers, conversions must not be temporaries
+        if cell is not None:  # refused before anything is staged or captured
+            parse_cell(cell)
+            self._refuse_virial()
+            if box is None:
+                raise ValueError("capture_minimize(cell=...) needs a box: the cell relaxation moves it")
+            if box.dim() == 2 and n_mol > 1:
+                raise NotImplementedError("capture_minimize(cell=...) relaxes one cell per molecule: give every molecule its own box "
+                                          f"[{n_mol},3,3], not one shared [3,3] box")
+            if bool((torch.linalg.det(box.detach().to(torch.float64)) == 0).any()):
+                raise ValueError("capture_minimize(cell=...): a box has no volume")
+            if box is getattr(rm.distance, "box", None):
+                box = box.clone()  # the model's own box stays as it was created
+            staged = box.detach().to(device=dev, dtype=torch.float32).contiguous()
+            # no conversion: the caller's own object, so that opt.box IS the tensor the caller reads (as md.box)
+            box = box if staged.data_ptr() == box.data_ptr() and not box.requires_grad else staged
         z = z.detach().to(device=dev, dtype=torch.long).contiguous()
         batch = batch.detach().to(device=dev, dtype=torch.long).contiguous()
-        box = None if box is None else box.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if cell is None:
+            box = None if box is None else box.detach().to(device=dev, dtype=torch.float32).contiguous()
         q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).contiguous()
-        return DeviceMinimizer(self, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, fire, fixed, warmup)
+        if cell is None:
+            return DeviceMinimizer(self, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, fire, fixed, warmup)
+        return DeviceMinimizer(self, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, fire, fixed, warmup, cell)
 
     def debug_tensor(self, name: str, shape) -> Tensor:
         L = _C.lib()
