@@ -354,6 +354,68 @@ int tmdnet_debug_gemm_dual(void* stream, const float* A, const float* A2, const 
 int64_t tmdnet_debug_split_weight(const float* W_host, int64_t N, int64_t K, uint16_t* out_host);
 int tmdnet_debug_gemm(void* stream, const float* A, const float* W, const float* bias, float* C, int64_t M, int64_t N,
                       int64_t K, int32_t silu, const uint16_t* Wsb);
+/* (The two entries below are additive: no existing signature or struct changed, the ABI revision stays.)
+ * The single-product GEMM family behind every dense contraction (fp32-MFMA tiles, split-K, split-bf16), with the whole
+ * argument surface the schedules use: epilogue flags, up to nine groups with per-group offsets, leading dimensions and the
+ * device-side row count.  No model handle; for unit tests.
+ *   C[g][m, n] = epilogue( sum_k A[g][m, k] W[g][n, k] + bias[g][n] ),  A[g] = A + a_off[g] (likewise C / pre / aux), g < groups
+ *   flags (TMDNET_GEMM_*), applied in this order: pre[m, n] = value (when pre != NULL); silu; * rowscale[m]; * aux[m, n];
+ *   * silu'(aux[m, n]); + old C[m, n].  Rows: min(M, *m_dev + m_add) when m_dev != NULL (a DEVICE int), else M; rows past that
+ *   count are not written.  Wsbg[g]: DEVICE copy of the split-bf16 tile image of W[g] (tmdnet_debug_split_weight) or NULL; when
+ *   every group has one and the shape qualifies a split-bf16 kernel runs.
+ * *route_out (may be NULL) receives the kernel taken, one of TMDNET_GEMM_ROUTE_*: the value of the selection function the
+ * launchers themselves branch on, not a second copy of their thresholds (those are performance choices and may move).
+ * TMDNET_ERR_INVALID, and no launch, outside the kernels' contract: N < 1, K < 1, M < 0, groups outside 1..9, unknown flag bits,
+ * NULL A / C / W[g], NULL rowscale or aux when a flag reads it, a leading dimension shorter than its row, a negative offset. */
+#define TMDNET_GEMM_MAX_GROUPS 9
+#define TMDNET_GEMM_ACT_SILU 1
+#define TMDNET_GEMM_MUL_AUX 2
+#define TMDNET_GEMM_MUL_DSILU_AUX 4
+#define TMDNET_GEMM_ACCUM 8
+#define TMDNET_GEMM_ROWSCALE 16
+#define TMDNET_GEMM_ROUTE_NONE 0          /* M == 0: nothing launched */
+#define TMDNET_GEMM_ROUTE_SKINNY4 1       /* split-K over 4 waves, 32 x 32 outputs per block (K < 256) */
+#define TMDNET_GEMM_ROUTE_SKINNY8 2       /* split-K over 8 waves (K >= 256) */
+#define TMDNET_GEMM_ROUTE_TILES_128X128 3 /* fp32-MFMA tiles */
+#define TMDNET_GEMM_ROUTE_TILES_128X64 4
+#define TMDNET_GEMM_ROUTE_TILES_128X32 5
+#define TMDNET_GEMM_ROUTE_SB1_128 6       /* split-bf16, persistent 128 x 128 tiles */
+#define TMDNET_GEMM_ROUTE_SB1_64 7        /* split-bf16, 64 x 64 tiles (fewer 128-tiles than compute units) */
+typedef struct tmdnet_gemm_ex_args {
+  const float* A;
+  const float* W[TMDNET_GEMM_MAX_GROUPS];
+  const float* bias[TMDNET_GEMM_MAX_GROUPS]; /* [N] or NULL */
+  float* C;
+  float* pre;            /* optional */
+  const float* aux;      /* operand of MUL_AUX / MUL_DSILU_AUX */
+  const float* rowscale; /* [M], operand of ROWSCALE */
+  int64_t lda, ldw, ldc, ldpre, ldaux;
+  int32_t a_off[TMDNET_GEMM_MAX_GROUPS], c_off[TMDNET_GEMM_MAX_GROUPS], pre_off[TMDNET_GEMM_MAX_GROUPS],
+      aux_off[TMDNET_GEMM_MAX_GROUPS];
+  int32_t M, N, K, groups, flags;
+  const int32_t* m_dev; /* DEVICE row count or NULL */
+  int32_t m_add;
+  const uint16_t* Wsbg[TMDNET_GEMM_MAX_GROUPS];
+} tmdnet_gemm_ex_args;
+int tmdnet_debug_gemm_ex(void* stream, const tmdnet_gemm_ex_args* args, int32_t* route_out);
+/* One launch of the fused nine-component tensor linear (the kernel of every per-atom tensor contraction at batch scale):
+ *   C[atom, c, n] = epilogue( sum_k prologue(A)[atom, c, k] W_type(c)[n, k] ),  type(c) = 0 (c = 0) | 1 (c = 1..3) | 2 (c = 4..8)
+ * pro: 0 plain, 1 A / (quad(A) + 1), 2 update adjoint of (A, A2, kap).  epi: 0 plain, 1 gate multiply (e3 = gates [N, 3, F],
+ * o1 = product before the gates), 2 update (e0 = X; o1 = new X; o2 = its invariants [N, 3, F] when want_feat), 3 normalisation
+ * adjoint (e0 = X, e1 = incoming gradient; C may alias e1), 4 the same followed by the gate adjoint (e2 = UX, e3 = gates,
+ * e4 = gate pre-activations [N, 3, F]; o1 = their gradient [N, 3, F]), 5 embedding atom adjoint (e0 = X, e1 = [N, F];
+ * o1 = [N, 10, F]; C is not written).  The launched pairs are (0,0) (1,0) (2,0) and (0,1..5).  All tensors [N, 9, F] fp32 unless
+ * noted; kap [N] or NULL (= 1); W_I / W_A / W_S are DEVICE fp32 [F, F] matrices.  No model handle; for unit tests.
+ * scratch: DEVICE memory for the three fragment-major split-bf16 weight images, built here on `stream` before the launch.
+ * With scratch == NULL the call only writes the needed number of uint16 elements to *scratch_elems; otherwise *scratch_elems
+ * is the number provided.  The row-count rule of the model's schedule (at least 128 tiles of 32 atoms x 128 channels) is a
+ * performance threshold and is NOT applied here: the kernel clamps the rows of a partial tile itself, so any N >= 1 runs.
+ * TMDNET_ERR_INVALID, and no launch, outside the kernel's contract: F % 128 != 0, N < 1, a (pro, epi) pair that is not
+ * launched, a NULL or misaligned (8 bytes) operand the pair reads or writes, a scratch that is too small. */
+int tmdnet_debug_tlin9(void* stream, int32_t pro, int32_t epi, int64_t N, int64_t F, const float* A, const float* A2, float* C,
+                       const float* e0, const float* e1, const float* e2, const float* e3, const float* e4, float* o1, float* o2,
+                       const float* kap, int32_t want_feat, const float* W_I, const float* W_A, const float* W_S,
+                       uint16_t* scratch, int64_t* scratch_elems);
 
 /* ---- First-order parameter gradients (TensorNet, TensorNet2 and Equivariant Transformer handles; energy-only training).
  * Replaces what autograd does in the reference for `loss(E).backward()` over torchmdnet/models/tensornet.py:543-619, 729-814,

@@ -2275,4 +2275,112 @@ int tmdnet_debug_gemm(void* stream, const float* A, const float* W, const float*
   return hipGetLastError() == hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
 }
 
+static_assert(TMDNET_GEMM_MAX_GROUPS == GEMM_MAX_GROUPS, "group count of the diagnostic struct");
+static_assert(TMDNET_GEMM_ACT_SILU == GEMM_ACT_SILU && TMDNET_GEMM_MUL_AUX == GEMM_MUL_AUX && TMDNET_GEMM_MUL_DSILU_AUX == GEMM_MUL_DSILU_AUX &&
+                  TMDNET_GEMM_ACCUM == GEMM_ACCUM && TMDNET_GEMM_ROWSCALE == GEMM_ROWSCALE, "flag values of the diagnostic struct");
+static_assert(TMDNET_GEMM_ROUTE_NONE == GEMM_ROUTE_NONE && TMDNET_GEMM_ROUTE_SKINNY4 == GEMM_ROUTE_SKINNY4 &&
+                  TMDNET_GEMM_ROUTE_SKINNY8 == GEMM_ROUTE_SKINNY8 && TMDNET_GEMM_ROUTE_TILES_128X128 == GEMM_ROUTE_TILES_128x128 &&
+                  TMDNET_GEMM_ROUTE_TILES_128X64 == GEMM_ROUTE_TILES_128x64 && TMDNET_GEMM_ROUTE_TILES_128X32 == GEMM_ROUTE_TILES_128x32 &&
+                  TMDNET_GEMM_ROUTE_SB1_128 == GEMM_ROUTE_SB1_128 && TMDNET_GEMM_ROUTE_SB1_64 == GEMM_ROUTE_SB1_64, "route values of the header");
+
+int tmdnet_debug_gemm_ex(void* stream, const tmdnet_gemm_ex_args* x, int32_t* route_out) {
+  if (!x) return TMDNET_ERR_INVALID;
+  const int all_flags = GEMM_ACT_SILU | GEMM_MUL_AUX | GEMM_MUL_DSILU_AUX | GEMM_ACCUM | GEMM_ROWSCALE;
+  if (x->N < 1 || x->K < 1 || x->M < 0 || x->groups < 1 || x->groups > GEMM_MAX_GROUPS || (x->flags & ~all_flags)) return TMDNET_ERR_INVALID;
+  if (!x->A || !x->C || x->lda < x->K || x->ldw < x->K || x->ldc < x->N) return TMDNET_ERR_INVALID;
+  if ((x->flags & GEMM_ROWSCALE) && !x->rowscale) return TMDNET_ERR_INVALID;
+  if ((x->flags & (GEMM_MUL_AUX | GEMM_MUL_DSILU_AUX)) && !x->aux) return TMDNET_ERR_INVALID;
+  if (x->pre && x->ldpre < x->N) return TMDNET_ERR_INVALID;
+  if (x->aux && x->ldaux < x->N) return TMDNET_ERR_INVALID;
+  GemmArgs a{};
+  for (int g = 0; g < x->groups; ++g) {
+    if (!x->W[g] || x->a_off[g] < 0 || x->c_off[g] < 0 || (x->pre && x->pre_off[g] < 0) || (x->aux && x->aux_off[g] < 0)) return TMDNET_ERR_INVALID;
+    a.W[g] = x->W[g];
+    a.bias[g] = x->bias[g];
+    a.Wsbg[g] = x->Wsbg[g];
+    a.a_off[g] = x->a_off[g];
+    a.c_off[g] = x->c_off[g];
+    a.pre_off[g] = x->pre_off[g];
+    a.aux_off[g] = x->aux_off[g];
+  }
+  a.A = x->A;
+  a.C = x->C;
+  a.pre = x->pre;
+  a.aux = x->aux;
+  a.rowscale = x->rowscale;
+  a.lda = x->lda;
+  a.ldw = x->ldw;
+  a.ldc = x->ldc;
+  a.ldpre = x->ldpre;
+  a.ldaux = x->ldaux;
+  a.M = x->M;
+  a.N = x->N;
+  a.K = x->K;
+  a.groups = x->groups;
+  a.flags = x->flags;
+  a.m_dev = x->m_dev;
+  a.m_add = x->m_add;
+  if (route_out) *route_out = gemm_route(a);  // the function launch_gemm branches on
+  return launch_gemm(a, reinterpret_cast<hipStream_t>(stream)) == (int)hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
+}
+
+int tmdnet_debug_tlin9(void* stream, int32_t pro, int32_t epi, int64_t N, int64_t F, const float* A, const float* A2, float* C,
+                       const float* e0, const float* e1, const float* e2, const float* e3, const float* e4, float* o1, float* o2,
+                       const float* kap, int32_t want_feat, const float* W_I, const float* W_A, const float* W_S,
+                       uint16_t* scratch, int64_t* scratch_elems) {
+  if (!scratch_elems || F < 128 || F % 128 || F > (1 << 14)) return TMDNET_ERR_INVALID;
+  const int64_t one = (int64_t)split_weight_fm_elems(F, F);
+  if (!scratch) {
+    *scratch_elems = 3 * one;
+    return TMDNET_OK;
+  }
+  if (*scratch_elems < 3 * one || N < 1 || N > (1 << 26)) return TMDNET_ERR_INVALID;
+  auto bad = [](const void* p, uintptr_t al) { return !p || (reinterpret_cast<uintptr_t>(p) & (al - 1)); };
+  bool inv = bad(A, 8) || bad(W_I, 16) || bad(W_A, 16) || bad(W_S, 16) || bad(scratch, 16) || (kap && bad(kap, 4));
+  if (pro == TL9_PRO_PLAIN) {
+    switch (epi) {
+      case TL9_EPI_PLAIN: inv = inv || bad(C, 8); break;
+      case TL9_EPI_MULGATE: inv = inv || bad(C, 8) || bad(e3, 8) || bad(o1, 8); break;
+      case TL9_EPI_UPDATE: inv = inv || bad(C, 8) || bad(e0, 8) || bad(o1, 8) || (want_feat && bad(o2, 8)); break;
+      case TL9_EPI_NORMBWD: inv = inv || bad(C, 8) || bad(e0, 8) || bad(e1, 8); break;
+      case TL9_EPI_NORMBWD_GATE:
+        inv = inv || bad(C, 8) || bad(e0, 8) || bad(e1, 8) || bad(e2, 8) || bad(e3, 8) || bad(e4, 8) || bad(o1, 8);
+        break;
+      case TL9_EPI_EMBBWD: inv = inv || bad(e0, 8) || bad(e1, 8) || bad(o1, 8); break;
+      default: inv = true;
+    }
+  } else if (pro == TL9_PRO_NORM && epi == TL9_EPI_PLAIN) {
+    inv = inv || bad(C, 8);
+  } else if (pro == TL9_PRO_UPDBWD && epi == TL9_EPI_PLAIN) {
+    inv = inv || bad(C, 8) || bad(A2, 8);
+  } else {
+    inv = true;
+  }
+  if (inv) return TMDNET_ERR_INVALID;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const float* W3[3] = {W_I, W_A, W_S};
+  Tl9Args a{};
+  for (int t = 0; t < 3; ++t) {
+    launch_split_weight_fm(W3[t], F, F, scratch + t * one, s);
+    a.Wfm[t] = scratch + t * one;
+  }
+  a.A = A;
+  a.A2 = A2;
+  a.C = C;
+  a.e0 = e0;
+  a.e1 = e1;
+  a.e2 = e2;
+  a.e3 = e3;
+  a.e4 = e4;
+  a.o1 = o1;
+  a.o2 = o2;
+  a.kap = kap;
+  a.N = (int)N;
+  a.F = (int)F;
+  a.want_feat = want_feat ? 1 : 0;
+  // straight to the kernel, not through tlin9_ok: its >= 128-tile rule is a performance threshold of the schedule
+  if (hipGetLastError() != hipSuccess) return TMDNET_ERR_HIP;
+  return launch_tlin9(a, pro, epi, s) == (int)hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
+}
+
 }  // extern "C"

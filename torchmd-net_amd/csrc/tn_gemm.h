@@ -48,6 +48,20 @@ struct GemmArgs {
   const uint16_t* Wsbg[GEMM_MAX_GROUPS];
 };
 
+// which kernel launch_gemm runs for `args`: the one selection function of the family.  launch_gemm, launch_gemm_sb1 and the
+// split-K launcher all branch on its value, so the route it reports is the route taken.
+enum GemmRoute : int {
+  GEMM_ROUTE_NONE = 0,       // nothing to do (M <= 0 or N <= 0): no launch
+  GEMM_ROUTE_SKINNY4,        // k_gemm_skinny, 4 waves split K (K < 256)                      tn_gemm_skinny.hip
+  GEMM_ROUTE_SKINNY8,        // k_gemm_skinny, 8 waves split K (K >= 256)
+  GEMM_ROUTE_TILES_128x128,  // k_gemm_nt<128, 128>                                           tn_gemm.hip
+  GEMM_ROUTE_TILES_128x64,   // k_gemm_nt<128, 64>
+  GEMM_ROUTE_TILES_128x32,   // k_gemm_nt<128, 32>
+  GEMM_ROUTE_SB1_128,        // k_gemm_sb1: split-bf16, persistent 128 x 128 tiles            tn_gemm_sb1.hip
+  GEMM_ROUTE_SB1_64,         // k_gemm_sb1h: split-bf16, 64 x 64 tiles (fewer 128-tiles than compute units)
+};
+int gemm_route(const GemmArgs& args);
+
 // launches on `stream`; returns hipError_t as int
 int launch_gemm(const GemmArgs& args, hipStream_t stream);
 // value + d/dd tangent through one weight tile; kind 0: plain, 1: silu, 2: silu * C(d) (rowscale/rowscale2 = C, C')
@@ -57,7 +71,8 @@ bool gemm_dual_sb_ok(const GemmArgs& args);
 int launch_gemm_dual_sb(const GemmArgs& args, int kind, hipStream_t stream);
 // single-product split-bf16 variant with the node-side epilogues (tn_gemm_sb1.hip): taken by launch_gemm when ok
 bool gemm_sb1_ok(const GemmArgs& args);
-int launch_gemm_sb1(const GemmArgs& args, hipStream_t stream);
+int gemm_sb1_num_cu();                                                      // compute units of the current device (cached)
+int launch_gemm_sb1(const GemmArgs& args, int route, hipStream_t stream);  // route: GEMM_ROUTE_SB1_128 / GEMM_ROUTE_SB1_64
 size_t split_weight_elems(int64_t N, int64_t K);                                   // uint16 elements of the tile image
 void split_weight_tiles(const float* W_host, int64_t N, int64_t K, uint16_t* out_host);
 void launch_split_weight_tiles(const float* W_dev, int64_t N, int64_t K, uint16_t* out_dev, hipStream_t s);  // same image, on the device

@@ -233,20 +233,43 @@ static int launch_variant(const GemmArgs& a, hipStream_t stream) {
   }
 }
 
-int launch_gemm(const GemmArgs& a, hipStream_t stream) {
-  if (a.M <= 0 || a.N <= 0) return 0;
-  if (gemm_sb1_ok(a)) return launch_gemm_sb1(a, stream);  // bf16 matrix pipe, exact 3-way split (tn_gemm_sb1.hip)
+int gemm_route(const GemmArgs& a) {
+  if (a.M <= 0 || a.N <= 0) return GEMM_ROUTE_NONE;
+  if (gemm_sb1_ok(a)) {  // bf16 matrix pipe, exact 3-way split (tn_gemm_sb1.hip)
+    // Developer switch TMDNET_GEMM_HALF_BELOW: 128 x 128 tiles per CU below which the 64 x 64 kernel is taken, 0 = never.
+    static const int half_below = getenv("TMDNET_GEMM_HALF_BELOW") ? atoi(getenv("TMDNET_GEMM_HALF_BELOW")) : 1;
+    const int total = ((a.M + 127) / 128) * ((a.N + 127) / 128) * a.groups;
+    return total < half_below * gemm_sb1_num_cu() ? GEMM_ROUTE_SB1_64 : GEMM_ROUTE_SB1_128;
+  }
   // few tiles: the chip would be mostly idle and every launch would cost K/32 dependent iterations ->
   // latency-oriented split-K kernel (single molecules, small MD systems)
   {
     static const bool no_skinny = getenv("TMDNET_NO_SKINNY") != nullptr;
     const int bn = (a.N % 128 == 0 || a.N > 192) ? 128 : (a.N > 32 ? 64 : 32);
     const int64_t tiles = (int64_t)((a.M + 127) / 128) * ((a.N + bn - 1) / bn) * a.groups;
-    if (!no_skinny && tiles < 256) return launch_gemm_skinny(a, stream);
+    if (!no_skinny && tiles < 256) {
+      if (a.groups <= 0) return GEMM_ROUTE_NONE;
+      return a.K >= 256 ? GEMM_ROUTE_SKINNY8 : GEMM_ROUTE_SKINNY4;
+    }
   }
-  if (a.N % 128 == 0 || a.N > 192) return launch_variant<128, 128, 2, 2>(a, stream);
-  if (a.N > 32) return launch_variant<128, 64, 2, 2>(a, stream);
-  return launch_variant<128, 32, 4, 1>(a, stream);
+  if (a.groups <= 0) return GEMM_ROUTE_NONE;
+  if (a.N % 128 == 0 || a.N > 192) return GEMM_ROUTE_TILES_128x128;
+  if (a.N > 32) return GEMM_ROUTE_TILES_128x64;
+  return GEMM_ROUTE_TILES_128x32;
+}
+
+int launch_gemm(const GemmArgs& a, hipStream_t stream) {
+  const int route = gemm_route(a);
+  switch (route) {
+    case GEMM_ROUTE_NONE: return 0;
+    case GEMM_ROUTE_SB1_128:
+    case GEMM_ROUTE_SB1_64: return launch_gemm_sb1(a, route, stream);
+    case GEMM_ROUTE_SKINNY4:
+    case GEMM_ROUTE_SKINNY8: return launch_gemm_skinny(a, route, stream);
+    case GEMM_ROUTE_TILES_128x128: return launch_variant<128, 128, 2, 2>(a, stream);
+    case GEMM_ROUTE_TILES_128x64: return launch_variant<128, 64, 2, 2>(a, stream);
+    default: return launch_variant<128, 32, 4, 1>(a, stream);
+  }
 }
 
 }  // namespace tn

@@ -67,7 +67,7 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& a, float* __restr
   }
 }
 
-// latency-oriented variant for small row counts (tn_gemm_skinny.hip)
-int launch_gemm_skinny(const GemmArgs& a, hipStream_t stream);
+// latency-oriented variant for small row counts (tn_gemm_skinny.hip); route: GEMM_ROUTE_SKINNY4 / GEMM_ROUTE_SKINNY8
+int launch_gemm_skinny(const GemmArgs& a, int route, hipStream_t stream);
 
 }  // namespace tn

@@ -347,20 +347,24 @@ bool gemm_sb1_ok(const GemmArgs& a) {
   return (int64_t)((a.M + 127) / 128) * ((a.N + 127) / 128) * a.groups >= 128;  // small launches: split-K fp32 kernel
 }
 
-int launch_gemm_sb1(const GemmArgs& a, hipStream_t stream) {
-  const int tiles_m = (a.M + 127) / 128, tiles_n = (a.N + 127) / 128;
+int gemm_sb1_num_cu() {
   static const int n_cu = [] {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n;
   }();
+  return n_cu;
+}
+
+int launch_gemm_sb1(const GemmArgs& a, int route, hipStream_t stream) {
+  const int tiles_m = (a.M + 127) / 128, tiles_n = (a.N + 127) / 128;
+  const int n_cu = gemm_sb1_num_cu();
   const int total = tiles_m * tiles_n * a.groups;
   static const int bpc = getenv("TMDNET_GEMM_BPC") ? atoi(getenv("TMDNET_GEMM_BPC")) : 3;  // developer switch
   // fewer 128 x 128 tiles than CUs (N <= 128 at M = 16 384): 64 x 64 tiles, every CU busy (22.9 -> 19.1 us for 16384 x 128 x 384;
   // from one tile per CU on the two kernels measure the same: these launches are at their streaming floor, ~3.8 TB/s of operands
-  // and both outputs behind a 3 - 4 us launch).  Developer switch TMDNET_GEMM_HALF_BELOW: tiles per CU below which it is taken, 0 = never.
-  static const int half_below = getenv("TMDNET_GEMM_HALF_BELOW") ? atoi(getenv("TMDNET_GEMM_HALF_BELOW")) : 1;
-  if (total < half_below * n_cu) {
+  // and both outputs behind a 3 - 4 us launch).  The threshold itself is in gemm_route (tn_gemm.hip).
+  if (route == GEMM_ROUTE_SB1_64) {
     const int hm = (a.M + 63) / 64, hn = (a.N + 63) / 64;
     const int htotal = hm * hn * a.groups;
     const dim3 hgrid(htotal < 6 * n_cu ? htotal : 6 * n_cu), block(256);

@@ -105,26 +105,26 @@ __global__ __launch_bounds__(64 * NW) void k_gemm_skinny(GemmArgs a, int tiles_m
 }
 
 template <int EPI>
-static int launch_skinny_one(const GemmArgs& a, hipStream_t stream) {
+static int launch_skinny_one(const GemmArgs& a, int route, hipStream_t stream) {
   const int tiles_m = (a.M + 31) / 32, tiles_n = (a.N + 31) / 32;
   const int total = tiles_m * tiles_n * a.groups;
   if (total <= 0) return 0;
-  if (a.K >= 256)
+  if (route == GEMM_ROUTE_SKINNY8)
     hipLaunchKernelGGL((k_gemm_skinny<EPI, 8>), dim3(total), dim3(512), 0, stream, a, tiles_m, tiles_n);
   else
     hipLaunchKernelGGL((k_gemm_skinny<EPI, 4>), dim3(total), dim3(256), 0, stream, a, tiles_m, tiles_n);
   return (int)hipGetLastError();
 }
 
-int launch_gemm_skinny(const GemmArgs& a, hipStream_t stream) {
+int launch_gemm_skinny(const GemmArgs& a, int route, hipStream_t stream) {
   switch (epi_kind(a)) {
-    case EPI_PLAIN: return launch_skinny_one<EPI_PLAIN>(a, stream);
-    case EPI_SILU_PRE: return launch_skinny_one<EPI_SILU_PRE>(a, stream);
-    case EPI_SILU_PRE_ROWSCALE: return launch_skinny_one<EPI_SILU_PRE_ROWSCALE>(a, stream);
-    case EPI_MULAUX_PRE: return launch_skinny_one<EPI_MULAUX_PRE>(a, stream);
-    case EPI_MULDSILU: return launch_skinny_one<EPI_MULDSILU>(a, stream);
-    case EPI_ACCUM: return launch_skinny_one<EPI_ACCUM>(a, stream);
-    default: return launch_skinny_one<EPI_GENERIC>(a, stream);
+    case EPI_PLAIN: return launch_skinny_one<EPI_PLAIN>(a, route, stream);
+    case EPI_SILU_PRE: return launch_skinny_one<EPI_SILU_PRE>(a, route, stream);
+    case EPI_SILU_PRE_ROWSCALE: return launch_skinny_one<EPI_SILU_PRE_ROWSCALE>(a, route, stream);
+    case EPI_MULAUX_PRE: return launch_skinny_one<EPI_MULAUX_PRE>(a, route, stream);
+    case EPI_MULDSILU: return launch_skinny_one<EPI_MULDSILU>(a, route, stream);
+    case EPI_ACCUM: return launch_skinny_one<EPI_ACCUM>(a, route, stream);
+    default: return launch_skinny_one<EPI_GENERIC>(a, route, stream);
   }
 }
 

@@ -45,6 +45,27 @@ class Tn2HParams(C.Structure):
                 ("coulomb_epsilon_solvent", C.c_float)]
 
 
+class GemmExArgs(C.Structure):
+    """tmdnet_gemm_ex_args (include/tmdnet_amd.h): the argument surface of tmdnet_debug_gemm_ex."""
+    _fields_ = [
+        ("A", C.c_void_p), ("W", C.c_void_p * 9), ("bias", C.c_void_p * 9), ("C", C.c_void_p), ("pre", C.c_void_p),
+        ("aux", C.c_void_p), ("rowscale", C.c_void_p),
+        ("lda", C.c_int64), ("ldw", C.c_int64), ("ldc", C.c_int64), ("ldpre", C.c_int64), ("ldaux", C.c_int64),
+        ("a_off", C.c_int32 * 9), ("c_off", C.c_int32 * 9), ("pre_off", C.c_int32 * 9), ("aux_off", C.c_int32 * 9),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("groups", C.c_int32), ("flags", C.c_int32),
+        ("m_dev", C.c_void_p), ("m_add", C.c_int32),
+        ("Wsbg", C.c_void_p * 9),
+    ]
+
+
+# flags and routes of tmdnet_debug_gemm_ex (TMDNET_GEMM_* in the header)
+GEMM_ACT_SILU, GEMM_MUL_AUX, GEMM_MUL_DSILU_AUX, GEMM_ACCUM, GEMM_ROWSCALE = 1, 2, 4, 8, 16
+(GEMM_ROUTE_NONE, GEMM_ROUTE_SKINNY4, GEMM_ROUTE_SKINNY8, GEMM_ROUTE_TILES_128X128, GEMM_ROUTE_TILES_128X64,
+ GEMM_ROUTE_TILES_128X32, GEMM_ROUTE_SB1_128, GEMM_ROUTE_SB1_64) = range(8)
+# prologues and epilogues of tmdnet_debug_tlin9
+TL9_PRO_PLAIN, TL9_PRO_NORM, TL9_PRO_UPDBWD = 0, 1, 2
+TL9_EPI_PLAIN, TL9_EPI_MULGATE, TL9_EPI_UPDATE, TL9_EPI_NORMBWD, TL9_EPI_NORMBWD_GATE, TL9_EPI_EMBBWD = range(6)
+
 _lib = None
 
 
@@ -108,6 +129,8 @@ def lib():
     L.tmdnet_debug_split_weight.argtypes = [vp, i64, i64, vp]
     L.tmdnet_debug_split_weight.restype = i64
     L.tmdnet_debug_gemm.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]
+    L.tmdnet_debug_gemm_ex.argtypes = [vp, C.POINTER(GemmExArgs), C.POINTER(i32)]
+    L.tmdnet_debug_tlin9.argtypes = [vp, i32, i32, i64, i64] + [vp] * 11 + [i32, vp, vp, vp, vp, C.POINTER(i64)]
     L.tmdnet_param_grad_count.argtypes = [vp]
     L.tmdnet_param_grad_entry.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64)]
     L.tmdnet_param_grad_entry.restype = C.c_char_p
