@@ -416,6 +416,66 @@ int tmdnet_debug_tlin9(void* stream, int32_t pro, int32_t epi, int64_t N, int64_
                        const float* e0, const float* e1, const float* e2, const float* e3, const float* e4, float* o1, float* o2,
                        const float* kap, int32_t want_feat, const float* W_I, const float* W_A, const float* W_S,
                        uint16_t* scratch, int64_t* scratch_elems);
+/* One launch of a TensorNet neighbour sweep on a caller-built graph (additive as well: the ABI revision stays).  No model
+ * handle; for unit tests.  The sweeps (type(c) as above, p = epair[e], j = col[e], e over rowptr[i] .. rowptr[i + 1]):
+ *   TMDNET_MSG_OP_FWD   out[i, c, f] = M = sum_e w[p, type(c), f] src[j, c, f];  out2 = dec(C) / (quad(C) + 1) with
+ *                       C = kap (Y M + M Y) (o3 != 0) or 2 Y M, Y = src[i], kap = 1 + 0.1 q[batch[i]] (batch != NULL), q[i]
+ *                       (batch == NULL) or 1 (q == NULL)
+ *   TMDNET_MSG_OP_ADJ   out[i] += sum_e w[p] src[j]
+ *   TMDNET_MSG_OP_GD    the same, and slots[a][2 p + dir] = sum over the channels of group a of w2[p, k, f] sum_{c in k}
+ *                       src[j, c, f] src2[i, c, f]  (w2 = dw, src = gMi, src2 = Pn; dir 0: row i is the pair's first atom, j < i)
+ *   TMDNET_MSG_OP_DUAL  out[i] (+)= sum_e w[p] src[j];  out2[i] (+)= sum_e w[p] src2[j] + sum_e w2[p] src[j]  (w2 = w_t, src2 = src_t)
+ * w, w2: [P + 1, 3, F]; src, src2, out, out2: [N, 9, F]; slots: arrays of slot_stride >= 2 P floats; all fp32, DEVICE memory.
+ * The graph must be in the engine's own form and is NOT validated here: rowptr [N + 1], col / epair / esign per entry, the
+ * adjacency symmetric, the columns of a row ascending, a self edge with pair id P in every row, esign +1 where the row atom is
+ * the pair's first atom (col < row), -1 where it is the second, 0 on the self edge; counts [8] as the engine keeps them
+ * (counts[2] != 0: pair overflow, every kernel returns without writing).  Anything else reads or writes out of bounds.
+ * kernel: TMDNET_MSG_AUTO calls the sweep's launcher with (N, F, small_mols) (and `accumulate` for OP_DUAL); any other value
+ * launches that kernel itself - the launchers' size thresholds are performance choices and are not applied.  *route_out (may be
+ * NULL) receives the kernel taken: the value of the selection function the launcher switches on (a model handle reports the
+ * routes of its last energy / force call the same way: tmdnet_get_info "message_route_last", "message_adjoint_route_last").
+ * Both out-parameters are written only when the call launches (TMDNET_OK, or TMDNET_ERR_HIP from the launch itself).  *slot_arrays_out (may be
+ * NULL) receives the number of slot arrays the kernel writes: F / 64 (row and split kernels), F / 32 (tile kernel), 0 without
+ * slots.  balance (forward tile kernel): 0 every row walked by its own lanes, 1 long rows hand their tails to short ones, < 0 default.
+ * TMDNET_ERR_INVALID, and no launch, outside the selected kernel's contract: N < 1, F < 1, P < 0, a kernel of another sweep or
+ * an unknown one, F % 32 (tile kernels; their operands 16-byte aligned), F % 64 or F > 128 (split kernels), F % 64 or F > 1024
+ * (TMDNET_MSG_GD_ROW), slot_stride < 2 P, a NULL graph array or a NULL operand the kernel reads or writes. */
+#define TMDNET_MSG_OP_FWD 0
+#define TMDNET_MSG_OP_ADJ 1
+#define TMDNET_MSG_OP_GD 2
+#define TMDNET_MSG_OP_DUAL 3
+#define TMDNET_MSG_AUTO 0
+#define TMDNET_MSG_FWD_ROW 1    /* k_message<false> */
+#define TMDNET_MSG_FWD_SPLIT 2  /* k_message_split<0> */
+#define TMDNET_MSG_FWD_TILE 3   /* k_message_rows8<8, 4> */
+#define TMDNET_MSG_ADJ_ROW 4    /* k_message_adjoint */
+#define TMDNET_MSG_ADJ_SPLIT 5  /* k_message_split<1> */
+#define TMDNET_MSG_GD_ROW 6     /* k_message_adjoint_gd<false> */
+#define TMDNET_MSG_GD_SPLIT 7   /* k_message_split<2> */
+#define TMDNET_MSG_GD_TILE 8    /* k_message_adjoint_rows8 */
+#define TMDNET_MSG_DUAL 9       /* k_message_dual<false>: out = ... */
+#define TMDNET_MSG_DUAL_ACC 10  /* k_message_dual<true>: out += ... */
+#define TMDNET_MSG_DUAL_SPLIT3 16 /* route of TMDNET_MSG_AUTO only: three k_message_split<1> launches */
+typedef struct tmdnet_message_args {
+  int32_t op, kernel;
+  int32_t N, F, P, small_mols, o3, balance, accumulate;
+  const int32_t* rowptr; /* [N + 1] */
+  const int32_t* col;
+  const int32_t* epair;
+  const float* esign;
+  const int32_t* counts; /* [8] */
+  const float* w;
+  const float* w2;   /* dw (OP_GD) or w_t (OP_DUAL) */
+  const float* src;  /* src (OP_FWD, OP_DUAL) or gMi (OP_ADJ, OP_GD) */
+  const float* src2; /* Pn (OP_GD) or src_t (OP_DUAL) */
+  const float* q;    /* OP_FWD, optional */
+  const int64_t* batch; /* OP_FWD, optional */
+  float* out;  /* Mi (OP_FWD), gPn (OP_ADJ, OP_GD), out (OP_DUAL) */
+  float* out2; /* Ch (OP_FWD), out_t (OP_DUAL) */
+  float* slots;
+  int64_t slot_stride;
+} tmdnet_message_args;
+int tmdnet_debug_message(void* stream, const tmdnet_message_args* args, int32_t* route_out, int32_t* slot_arrays_out);
 
 /* ---- First-order parameter gradients (TensorNet, TensorNet2 and Equivariant Transformer handles; energy-only training).
  * Replaces what autograd does in the reference for `loss(E).backward()` over torchmdnet/models/tensornet.py:543-619, 729-814,

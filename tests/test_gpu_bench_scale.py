@@ -316,3 +316,94 @@ def test_thousands_of_tiny_molecules_through_the_batch_kernels(hip_lib):
         Eo, Fo = T.energy_and_forces(sd, hp, z[sel], pos[sel], torch.zeros(int(sel.sum()), dtype=torch.long))
         assert abs(E[m].item() - Eo.item()) < 1e-4 * max(1.0, abs(Eo.item())), m
         assert (F[sel.cuda()].cpu() - Fo).abs().max().item() < 1e-4 * max(1.0, Fo.abs().max().item()), m
+
+
+def test_one_large_molecule_in_a_batch_of_small_ones_through_the_tile_sweeps(hip_lib):
+    """`small_mols` looks at the AVERAGE molecule (N <= 96 B), so one dense 648-atom cluster among 120 molecules of 64 atoms
+    (8 328 atoms, C2 model) sends the cluster's tiles through the tile sweeps too, where their column windows (up to 528 rows)
+    are gathered from global memory and the longest adjacency slices (> 4096 entries) are walked from global memory.  Pinned here:
+    the batch really holds such tiles (host census of tests/message_unit_cases.py on the engine's own pair list), the launchers
+    really pick the tile kernel in both directions (for the restated hint through tmdnet_debug_message, and in the engine's own
+    step through tmdnet_get_info "message_route_last" / "message_adjoint_route_last"), and the cluster and two small molecules meet
+    the oracle."""
+    import ctypes as C
+    from oracle import tensornet_torch as T
+    from tests import message_unit_cases as M
+    from torchmdnet_amd import _C
+    from torchmdnet_amd.models.model import create_model
+
+    torch.manual_seed(0)
+    model = create_model(dict(W.C2_ARGS)).cuda()
+    zs, ps, _ = W.synthetic_batch(n_mol=120)
+    zw, pw, _ = W.water_box(n_side=6, spacing=2.6)  # cut out of the lattice, no box: 648 atoms, ~60 neighbours each
+    first = 60 * 64  # the cluster sits in the middle of the batch; the molecules behind it straddle the 64-row tiles
+    z = torch.cat([zs[:first], zw, zs[first:]])
+    pos = torch.cat([ps[:first], pw, ps[first:]])
+    sizes = [64] * 60 + [zw.shape[0]] + [64] * 60
+    batch = torch.repeat_interleave(torch.arange(len(sizes)), torch.tensor(sizes))
+    N, B, Fh = z.shape[0], len(sizes), W.C2_ARGS["embedding_dimension"]
+    assert N >= 8192 and N <= 96 * B
+    zc, pc, bc = z.cuda(), pos.cuda(), batch.cuda()
+
+    # ---- the engine's graph (brute force inside each molecule: the engine's order is the caller's)
+    nb, _, _, npairs = torch.ops.tmdnet.neighbor_pairs(pc, bc, None, 0.0, 5.0, 400_000, False, False, 0, B)
+    P = int(npairs.reshape(-1)[0])
+    pi, pj = torch.maximum(nb[0, :P], nb[1, :P]), torch.minimum(nb[0, :P], nb[1, :P])
+    assert bool((pi > pj).all()) and bool((bc[pi] == bc[pj]).all())
+    ar = torch.arange(N, device="cuda")
+    rows, cols = torch.cat([pi, pj, ar]), torch.cat([pj, pi, ar])
+    pid = torch.cat([torch.arange(P, device="cuda")] * 2 + [torch.full((N,), P, device="cuda")])
+    order = torch.argsort(rows * N + cols)
+    rows, cols, pid = rows[order], cols[order], pid[order]
+    rowptr = torch.zeros(N + 1, dtype=torch.long, device="cuda")
+    rowptr[1:] = torch.bincount(rows, minlength=N).cumsum(0)
+    tiles = M.tile_census(rowptr.cpu(), cols.cpu(), N)
+    assert int(rowptr.diff().max()) <= W.C2_ARGS["max_num_neighbors"]
+    assert sum(not t["staged"] for t in tiles) >= 10 and sum(not t["csr_lds"] for t in tiles) >= 1, "no tile off the LDS path"
+    assert sum(t["staged"] and t["csr_lds"] for t in tiles) >= 60  # and the small molecules in front of the cluster on it
+
+    # ---- the launchers' own choice for this (N, F, small_mols): the tile kernel in both directions
+    g = dict(N=N, P=P)
+    csr = dict(rowptr=rowptr.int(), col=cols.int(), epair=pid.int(), esign=torch.where(rows == cols, 0.0, torch.where(cols < rows, 1.0, -1.0)).float(),
+               counts=torch.tensor([P, rows.numel(), 0, 0, 0, 0, 0, 0], dtype=torch.int32, device="cuda"))
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    rn = lambda *s: torch.randn(*s, generator=gen, device="cuda")
+    d = dict(w=rn(P + 1, 3, Fh) * 0.2, dw=rn(P + 1, 3, Fh) * 0.2, src=rn(N, 9, Fh) * 0.5, gMi=rn(N, 9, Fh), Pn=rn(N, 9, Fh) * 0.5,
+             old=rn(N, 9, Fh), kap_atom=torch.ones(N, device="cuda"))
+    small_mols = int(N <= 96 * B)  # carve_graph's rule RESTATED (the entry takes the hint as an argument); the engine's own routes below
+    for kernel, want, narr in (("fwd_tile", _C.MSG_FWD_TILE, 0), ("gd_tile", _C.MSG_GD_TILE, Fh // 32)):
+        outs = []
+        for sel in (_C.MSG_AUTO, want):
+            x = M.message_args(kernel, g, csr, Fh, small_mols=small_mols)
+            x.kernel = sel
+            out = M.fresh_outputs(kernel, g, d, Fh, "cuda")
+            rc, route, ns = M.launch(hip_lib, kernel, x, d, out, "o3_atom", g)
+            assert (rc, route, ns) == (_C.OK, want, narr), (kernel, sel, rc, route, ns)
+            outs.append(out)
+        assert all(torch.equal(outs[0][k].view(torch.int32), outs[1][k].view(torch.int32)) for k in outs[0])
+        x = M.message_args(kernel, g, csr, Fh, small_mols=0)  # without the hint: the row kernels
+        x.kernel = _C.MSG_AUTO
+        rc, route, ns = M.launch(hip_lib, kernel, x, d, M.fresh_outputs(kernel, g, d, Fh, "cuda"), "o3_atom", g)
+        assert (rc, route, ns) == (_C.OK, _C.MSG_FWD_ROW if kernel == "fwd_tile" else _C.MSG_GD_ROW, narr // 2)
+    del d, outs, out
+
+    # ---- through the engine
+    E, F = model(zc, pc, bc)
+    assert model._engine.counts[0] == P
+    # the routes the engine itself took for this batch (its own hint, its own launchers)
+    assert int(model.engine_info("message_route_last")) == _C.MSG_FWD_TILE
+    assert int(model.engine_info("message_adjoint_route_last")) == _C.MSG_GD_TILE
+    E2, F2 = model(zc, pc.clone(), bc)
+    assert torch.equal(E, E2) and torch.equal(F, F2)
+    sd = {k: v.detach().cpu().double() for k, v in model.state_dict().items()}
+    hp = T.hparams_from_args(W.C2_ARGS)
+    off = [0]
+    for n in sizes:
+        off.append(off[-1] + n)
+    for m in (60, 59, 61):  # the cluster, the molecule in front of it (aligned tiles) and the one behind it (straddles two)
+        sl = slice(off[m], off[m + 1])
+        Er, Fr = T.energy_and_forces(sd, hp, z[sl], pos[sl].double(), torch.zeros(sizes[m], dtype=torch.long))
+        assert abs(E[m].item() - Er.item()) / max(abs(Er.item()), 1e-12) < REL, m
+        assert rel_err(F[sl].cpu().double(), Fr) < REL, m
+    net = torch.zeros(B, 3, device="cuda").index_add_(0, bc, F)
+    assert net.abs().max().item() < 1e-3 * F.abs().max().item()

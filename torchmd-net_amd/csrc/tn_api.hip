@@ -1183,6 +1183,8 @@ int tmdnet_get_info(const tmdnet_model* m, const char* name, double* value) {
   else if (n == "species_last_build") *value = (double)m->last_nt;
   else if (n == "halo_active_first") *value = (double)m->halo_active[0];  // rows the per-atom kernels of the last step ran on
   else if (n == "halo_active_rows") *value = (double)m->halo_active[1];
+  else if (n == "message_route_last") *value = (double)m->msg_route_last[0];  // TMDNET_MSG_* of the last TensorNet step's sweeps
+  else if (n == "message_adjoint_route_last") *value = (double)m->msg_route_last[1];
   else return TMDNET_ERR_INVALID;
   return TMDNET_OK;
 }
@@ -1698,6 +1700,7 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
         ta.A = b.X[l] + o9F; ta.C = b.Pn[l] + o9F; ta.N = Na; ta.F = F;
         tlin9(s, TL9_PRO_NORM, TL9_EPI_PLAIN, q_.V, ta, 2.0, "norm");
         HALO_TRY(l, b.Pn[l], 9 * F);
+        m->msg_route_last[0] = message_route(g, N, F, recompute, a0, rng ? Na : -1);
         KR(CAT_MESSAGE, wB + idxB + nodeB * (1.0 + 2.0 * Na / Nd),  // P of every local atom is gathered; Mi, C_hat of the swept rows are written
            launch_message(g, N, F, b.w[l], b.Pn[l], q, batch_k, o3, b.Mi[l], Ch_l, s, recompute ? &rts[l] : nullptr, a0, rng ? Na : -1));
         // dX = linear(C_hat), then X_new = X_hat + dX + kappa dX.dX (and the readout invariants after the last layer) in the epilogue
@@ -1711,6 +1714,7 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
       if (l == 0) KR(CAT_ELEMENTWISE, 2 * nodeB, launch_norm_x(b.X[l], Xh_l, N, F, s));
       tensor_linear(s, Xh_l, q_.V, b.Pn[l], N, F);
       HALO_TRY(l, b.Pn[l], 9 * F);
+      m->msg_route_last[0] = message_route(g, N, F, recompute);
       KR(CAT_MESSAGE, wB + idxB + 3 * nodeB, launch_message(g, N, F, b.w[l], b.Pn[l], q, batch_k, o3, b.Mi[l], Ch_l, s, recompute ? &rts[l] : nullptr));
       tensor_linear(s, Ch_l, q_.V + 3, b.D[l], N, F);
       // update fused with the next consumer of the new X: the next layer's normalisation, or the readout invariants
@@ -1872,6 +1876,8 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
         launch_colsum(s, tc->g1, rF, nullptr, rF, nullptr, nullptr, P1, F, tc->at(t_ + "b0"), false, tc->part);
         NODE();
       }
+      m->msg_route_last[1] = merged_gd ? message_adjoint_gd_route(g, N, F, recompute, a0, rng ? a0 + Na : -1, !m->graph_no_ghost_pairs)
+                                       : message_adjoint_route(N, F);
       if (merged_gd) {
         KR(CAT_MESSAGE, 2 * wB + idxB + nodeB * (2.0 + 2.0 * Na / Nd) + 8 * (Pd + 1) * gd_nw,  // w, dw, gMi, Pn, gPn (read + write: swept rows), g_d slots
            launch_message_adjoint_gd(g, N, F, b.w[l], b.dw[l], b.gMi, b.Pn[l], b.gPn, b.gd_slots + (int64_t)l * gd_nw * gd_stride,
@@ -2381,6 +2387,85 @@ int tmdnet_debug_tlin9(void* stream, int32_t pro, int32_t epi, int64_t N, int64_
   // straight to the kernel, not through tlin9_ok: its >= 128-tile rule is a performance threshold of the schedule
   if (hipGetLastError() != hipSuccess) return TMDNET_ERR_HIP;
   return launch_tlin9(a, pro, epi, s) == (int)hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
+}
+
+static_assert(TMDNET_MSG_FWD_ROW == MSG_FWD_ROW && TMDNET_MSG_FWD_SPLIT == MSG_FWD_SPLIT && TMDNET_MSG_FWD_TILE == MSG_FWD_TILE &&
+                  TMDNET_MSG_ADJ_ROW == MSG_ADJ_ROW && TMDNET_MSG_ADJ_SPLIT == MSG_ADJ_SPLIT && TMDNET_MSG_GD_ROW == MSG_GD_ROW &&
+                  TMDNET_MSG_GD_SPLIT == MSG_GD_SPLIT && TMDNET_MSG_GD_TILE == MSG_GD_TILE && TMDNET_MSG_DUAL == MSG_DUAL &&
+                  TMDNET_MSG_DUAL_ACC == MSG_DUAL_ACC && TMDNET_MSG_DUAL_SPLIT3 == MSG_DUAL_SPLIT3 && TMDNET_MSG_AUTO == MSG_NONE,
+              "route values of the header");
+
+int tmdnet_debug_message(void* stream, const tmdnet_message_args* x, int32_t* route_out, int32_t* slot_arrays_out) {
+  if (!x) return TMDNET_ERR_INVALID;
+  const int N = x->N, F = x->F;
+  if (N < 1 || F < 1 || x->P < 0 || x->op < TMDNET_MSG_OP_FWD || x->op > TMDNET_MSG_OP_DUAL) return TMDNET_ERR_INVALID;
+  if (!x->rowptr || !x->col || !x->epair || !x->esign || !x->counts) return TMDNET_ERR_INVALID;
+  Graph g{};
+  g.rowptr = const_cast<int*>(x->rowptr);
+  g.col = const_cast<int*>(x->col);
+  g.epair = const_cast<int*>(x->epair);
+  g.esign = const_cast<float*>(x->esign);
+  g.counts = const_cast<int*>(x->counts);
+  g.small_mols = x->small_mols ? 1 : 0;
+  MsgRoute r = static_cast<MsgRoute>(x->kernel);
+  const bool automatic = x->kernel == TMDNET_MSG_AUTO;
+  if (automatic) {  // the launcher's own choice for (N, F, small_mols)
+    switch (x->op) {
+      case TMDNET_MSG_OP_FWD: r = message_route(g, N, F); break;
+      case TMDNET_MSG_OP_ADJ: r = message_adjoint_route(N, F); break;
+      case TMDNET_MSG_OP_GD: r = message_adjoint_gd_route(g, N, F); break;
+      default: r = message_dual_route(N, F, x->accumulate != 0);
+    }
+  }
+  // the selected kernel's own contract
+  int op_of = -1, slot_arrays = 0;
+  bool ok = true;
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  switch (r) {
+    case MSG_FWD_ROW: op_of = TMDNET_MSG_OP_FWD; break;
+    case MSG_FWD_SPLIT: op_of = TMDNET_MSG_OP_FWD; ok = F % 64 == 0 && F <= 128; break;
+    case MSG_FWD_TILE: op_of = TMDNET_MSG_OP_FWD; ok = F % 32 == 0 && al16(x->w) && al16(x->src) && al16(x->out) && al16(x->out2); break;
+    case MSG_ADJ_ROW: op_of = TMDNET_MSG_OP_ADJ; break;
+    case MSG_ADJ_SPLIT: op_of = TMDNET_MSG_OP_ADJ; ok = F % 64 == 0 && F <= 128; break;
+    case MSG_GD_ROW: op_of = TMDNET_MSG_OP_GD; ok = F % 64 == 0 && F <= 1024; slot_arrays = F / 64; break;
+    case MSG_GD_SPLIT: op_of = TMDNET_MSG_OP_GD; ok = F % 64 == 0 && F <= 128; slot_arrays = F / 64; break;
+    case MSG_GD_TILE:
+      op_of = TMDNET_MSG_OP_GD;
+      ok = F % 32 == 0 && al16(x->w) && al16(x->w2) && al16(x->src) && al16(x->src2) && al16(x->out);
+      slot_arrays = F / 32;
+      break;
+    case MSG_DUAL: case MSG_DUAL_ACC: op_of = TMDNET_MSG_OP_DUAL; break;
+    case MSG_DUAL_SPLIT3: op_of = automatic ? TMDNET_MSG_OP_DUAL : -1; break;  // a route of the launcher, not a kernel to select
+    default: break;
+  }
+  if (op_of != x->op || !ok || !x->w || !x->src || !x->out) return TMDNET_ERR_INVALID;
+  if ((x->op == TMDNET_MSG_OP_FWD || x->op == TMDNET_MSG_OP_DUAL) && !x->out2) return TMDNET_ERR_INVALID;
+  if ((x->op == TMDNET_MSG_OP_GD || x->op == TMDNET_MSG_OP_DUAL) && (!x->w2 || !x->src2)) return TMDNET_ERR_INVALID;
+  if (x->op == TMDNET_MSG_OP_GD && (!x->slots || x->slot_stride < 2 * (int64_t)x->P)) return TMDNET_ERR_INVALID;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (hipGetLastError() != hipSuccess) return TMDNET_ERR_HIP;  // an earlier error: nothing launched, the out-parameters untouched
+  if (route_out) *route_out = r;
+  if (slot_arrays_out) *slot_arrays_out = slot_arrays;
+  bool launched = true;
+  switch (x->op) {
+    case TMDNET_MSG_OP_FWD:
+      if (automatic) launch_message(g, N, F, x->w, x->src, x->q, x->batch, x->o3, x->out, x->out2, s);
+      else launched = launch_message_as(r, g, N, F, x->w, x->src, x->q, x->batch, x->o3, x->out, x->out2, s, nullptr, 0, -1, x->balance);
+      break;
+    case TMDNET_MSG_OP_ADJ:
+      if (automatic) launch_message_adjoint(g, N, F, x->w, x->src, x->out, s);
+      else launched = launch_message_adjoint_as(r, g, N, F, x->w, x->src, x->out, s);
+      break;
+    case TMDNET_MSG_OP_GD:
+      if (automatic) launch_message_adjoint_gd(g, N, F, x->w, x->w2, x->src, x->src2, x->out, x->slots, x->slot_stride, s);
+      else launched = launch_message_adjoint_gd_as(r, g, N, F, x->w, x->w2, x->src, x->src2, x->out, x->slots, x->slot_stride, s);
+      break;
+    default:
+      if (automatic) launch_message_dual(g, N, F, x->w, x->w2, x->src, x->src2, x->out, x->out2, x->accumulate != 0, s);
+      else launched = launch_message_dual_as(r, g, N, F, x->w, x->w2, x->src, x->src2, x->out, x->out2, s);
+  }
+  if (!launched) return TMDNET_ERR_INVALID;
+  return hipGetLastError() == hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
 }
 
 }  // extern "C"

@@ -44,7 +44,9 @@ struct Graph {  // device pointers into the graph workspace
   int use_cell;          // 0: brute force, 1: cell list / one molecule, 2: cell list / several molecules
   const float* ghost_w;  // halo exchange (cell list): the caller's atom weights; pairs of two weight-0 atoms (ghosts) are left out
   int max_z;
-  int small_mols;        // host hint: on average <= 96 atoms per molecule, i.e. the column window of a 64-row tile fits LDS
+  int small_mols;        // host hint: on AVERAGE <= 96 atoms per molecule (N <= 96 B), i.e. the column window of most 64-row tiles
+                         // fits LDS.  It routes the whole batch to the tile sweeps; a tile of a larger molecule in such a batch
+                         // gathers from global memory inside them (block-uniform branches, tests/test_gpu_message.py)
 };
 
 struct RadialParams {
@@ -84,6 +86,43 @@ void launch_layernorm_bwd(const float* g, const float* xhat, const float* rstd, 
 void launch_norm_x(const float* X, float* Xh, int N, int F, hipStream_t s);
 // mode 0: forward message + O(3)/SO(3) product + normalisation -> Mi, Ch ; mode 1: dst[i] += sum_e w * src[j] (adjoint)
 struct PairRowTable;  // tn_interp.h: a layer's radial table for sweeps that evaluate the per-pair rows themselves
+// The kernel a neighbour sweep runs: the value of the selection functions below, which the launchers switch on (and which
+// tmdnet_debug_message reports).  The values are those of TMDNET_MSG_* in include/tmdnet_amd.h.
+enum MsgRoute {
+  MSG_NONE = 0,          // N <= 0: nothing launched
+  MSG_FWD_ROW = 1,       // k_message<false>
+  MSG_FWD_SPLIT = 2,     // k_message_split<0>
+  MSG_FWD_TILE = 3,      // k_message_rows8<8, 4> (tn_message_pair.hip)
+  MSG_ADJ_ROW = 4,       // k_message_adjoint
+  MSG_ADJ_SPLIT = 5,     // k_message_split<1>
+  MSG_GD_ROW = 6,        // k_message_adjoint_gd<false>
+  MSG_GD_SPLIT = 7,      // k_message_split<2>
+  MSG_GD_TILE = 8,       // k_message_adjoint_rows8 (tn_message_pair.hip)
+  MSG_DUAL = 9,          // k_message_dual<false>
+  MSG_DUAL_ACC = 10,     // k_message_dual<true>
+  MSG_FWD_ROW_TABLE = 11,  // k_message<true>: rows evaluated from the radial table inside the sweep
+  MSG_FWD_ROW_RANGE = 12,  // k_message<false> over the rows [row0, row0 + nrows)
+  MSG_GD_ROW_TABLE = 13,   // k_message_adjoint_gd<true>
+  MSG_GD_ROW_OWNED = 14,   // k_message_adjoint_gd<false> with an owned range (ghost rows write slots only)
+  MSG_GD_ROW_TWO = 15,     // k_message_adjoint_gd<false, true>: the owned rows serve both halves
+  MSG_DUAL_SPLIT3 = 16,    // three k_message_split<1> launches (after a zero fill unless accumulating)
+};
+MsgRoute message_route(const Graph& g, int N, int F, bool rows_from_table = false, int row0 = 0, int nrows = -1);
+MsgRoute message_adjoint_route(int N, int F);
+MsgRoute message_adjoint_gd_route(const Graph& g, int N, int F, bool rows_from_table = false, int own0 = 0, int own1 = -1,
+                                  bool narrow = true);
+MsgRoute message_dual_route(int N, int F, bool accumulate);
+// One kernel of the table above on the caller's operands, without the launchers' size thresholds (tmdnet_debug_message; the
+// launchers themselves end here).  false: `r` is not a route of that sweep.  balance < 0: the forward tile kernel's default.
+bool launch_message_as(MsgRoute r, const Graph& g, int N, int F, const float* w, const float* src, const float* q,
+                       const int64_t* batch, int o3, float* Mi, float* Ch, hipStream_t s, const PairRowTable* rt = nullptr,
+                       int row0 = 0, int nrows = -1, int balance = -1);
+bool launch_message_adjoint_as(MsgRoute r, const Graph& g, int N, int F, const float* w, const float* gMi, float* gPn, hipStream_t s);
+bool launch_message_adjoint_gd_as(MsgRoute r, const Graph& g, int N, int F, const float* w, const float* dw, const float* gMi,
+                                  const float* Pn, float* gPn, float* slots, int64_t slot_stride, hipStream_t s,
+                                  const PairRowTable* rt = nullptr, int own0 = 0, int own1 = -1, bool narrow = true);
+bool launch_message_dual_as(MsgRoute r, const Graph& g, int N, int F, const float* w, const float* w_t, const float* src,
+                            const float* src_t, float* out, float* out_t, hipStream_t s);
 void launch_message_dual(const Graph& g, int N, int F, const float* w, const float* w_t, const float* src, const float* src_t,
                          float* out, float* out_t, bool accumulate, hipStream_t s);  // value + tangent sweep (second-order pass)
 void launch_message(const Graph& g, int N, int F, const float* w, const float* src, const float* q, const int64_t* batch, int o3,
@@ -209,7 +248,7 @@ void launch_interp_list(const float* tab, const double* dist, int M, int R, int 
 // ---- LDS-staged forward sweep (tn_message_pair.hip): 8 lanes per row x 16 bytes per lane, the tile's source window in LDS
 bool message_pair_ok(int N, int F);
 void launch_message_pair(const Graph& g, int N, int F, const float* w, const float* src, const float* q, const int64_t* batch,
-                         int o3, float* Mi, float* Ch, hipStream_t s);
+                         int o3, float* Mi, float* Ch, hipStream_t s, int balance = -1);  // balance < 0: on, unless TMDNET_MSG_NOBALANCE
 
 // 16-byte-per-lane form of the per-pair kernels (tn_pairgrad.hip)
 bool gather_v4_ok(int F);

@@ -812,31 +812,45 @@ __global__ __launch_bounds__(1024) void k_message_split(Graph g, int N, int F, c
 }
 static bool split_rows_ok(int N, int F) { return N <= kSplitRows && F <= 128 && F % 64 == 0; }
 
+// The kernel of the forward sweep.  A row range keeps the row kernel (one large system; the other kernels take all rows)
+// unless the shape belongs to the split or the tile sweep.  The tile kernels pay off when a tile's column window fits LDS
+// (batches of small molecules); one large system in cell order has windows of hundreds of rows: there the row kernel with four
+// edges in flight is faster (10 k-atom box: 0.36 -> 0.26 ms per sweep).
+MsgRoute message_route(const Graph& g, int N, int F, bool rows_from_table, int row0, int nrows) {
+  (void)row0;
+  if (N <= 0) return MSG_NONE;
+  if (rows_from_table) return MSG_FWD_ROW_TABLE;
+  const bool tile = g.small_mols && message_pair_ok(N, F);
+  if (nrows >= 0 && nrows != N && !split_rows_ok(N, F) && !tile) return MSG_FWD_ROW_RANGE;
+  if (split_rows_ok(N, F)) return MSG_FWD_SPLIT;
+  return tile ? MSG_FWD_TILE : MSG_FWD_ROW;
+}
+bool launch_message_as(MsgRoute r, const Graph& g, int N, int F, const float* w, const float* src, const float* q,
+                       const int64_t* batch, int o3, float* Mi, float* Ch, hipStream_t s, const PairRowTable* rt, int row0, int nrows,
+                       int balance) {
+  switch (r) {
+    case MSG_NONE: return true;
+    case MSG_FWD_ROW_TABLE:  // rows evaluated from the table inside the sweep
+      if (!rt) return false;
+      if (nrows < 0) row0 = 0, nrows = N;
+      hipLaunchKernelGGL((k_message<true>), dim3(nrows), dim3(fthreads(F)), 0, s, g, N, F, w, src, q, batch, o3, Mi, Ch, *rt, row0);
+      return true;
+    case MSG_FWD_ROW_RANGE:
+      hipLaunchKernelGGL((k_message<false>), dim3(nrows), dim3(fthreads(F)), 0, s, g, N, F, w, src, q, batch, o3, Mi, Ch, PairRowTable{}, row0);
+      return true;
+    case MSG_FWD_SPLIT:
+      hipLaunchKernelGGL((k_message_split<0>), dim3(N), dim3(kEG * F), 0, s, g, N, F, w, src, q, batch, o3, Mi, Ch);
+      return true;
+    case MSG_FWD_TILE: launch_message_pair(g, N, F, w, src, q, batch, o3, Mi, Ch, s, balance); return true;
+    case MSG_FWD_ROW:
+      hipLaunchKernelGGL((k_message<false>), dim3(N), dim3(fthreads(F)), 0, s, g, N, F, w, src, q, batch, o3, Mi, Ch, PairRowTable{}, 0);
+      return true;
+    default: return false;
+  }
+}
 void launch_message(const Graph& g, int N, int F, const float* w, const float* src, const float* q, const int64_t* batch, int o3,
                     float* Mi, float* Ch, hipStream_t s, const PairRowTable* rt, int row0, int nrows) {
-  if (N <= 0) return;
-  if (nrows < 0) {
-    row0 = 0;
-    nrows = N;
-  }
-  if (rt) {  // rows evaluated from the table inside the sweep
-    hipLaunchKernelGGL((k_message<true>), dim3(nrows), dim3(fthreads(F)), 0, s, g, N, F, w, src, q, batch, o3, Mi, Ch, *rt, row0);
-    return;
-  }
-  if (nrows != N && !split_rows_ok(N, F) && !(g.small_mols && message_pair_ok(N, F))) {  // a row range: the row kernel (one large
-                                                                                            // system; the other kernels take all rows)
-    hipLaunchKernelGGL((k_message<false>), dim3(nrows), dim3(fthreads(F)), 0, s, g, N, F, w, src, q, batch, o3, Mi, Ch, PairRowTable{}, row0);
-    return;
-  }
-  if (split_rows_ok(N, F)) {
-    hipLaunchKernelGGL((k_message_split<0>), dim3(N), dim3(kEG * F), 0, s, g, N, F, w, src, q, batch, o3, Mi, Ch);
-    return;
-  }
-  // the tile kernels pay off when a tile's column window fits LDS (batches of small molecules); one large system in cell
-  // order has windows of hundreds of rows: there the row kernel with four edges in flight is faster (10 k-atom box:
-  // 0.36 -> 0.26 ms per sweep)
-  if (g.small_mols && message_pair_ok(N, F)) return launch_message_pair(g, N, F, w, src, q, batch, o3, Mi, Ch, s);
-  hipLaunchKernelGGL((k_message<false>), dim3(N), dim3(fthreads(F)), 0, s, g, N, F, w, src, q, batch, o3, Mi, Ch, PairRowTable{}, 0);
+  launch_message_as(message_route(g, N, F, rt != nullptr, row0, nrows), g, N, F, w, src, q, batch, o3, Mi, Ch, s, rt, row0, nrows);
 }
 
 // adjoint of the message sum: the graph and the edge weights are symmetric, so the transpose sweep is the
@@ -969,41 +983,59 @@ __global__ void k_message_adjoint_gd(Graph g, int N, int F, const float* __restr
   for (int c = 0; c < 9; ++c) o[c * F] += acc[c];
 }
 bool message_adjoint_gd_ok(int N, int F) { return F % 64 == 0 && (split_rows_ok(N, F) || (N > kSplitRows && F <= 1024)); }
+// The kernel of the adjoint sweep with the distance-gradient halves.  An owned range (halo exchange) keeps the row kernel - the
+// others treat every row alike - unless the shape belongs to the split or the tile sweep; `two`: the graph holds no ghost-ghost
+// pairs, so the owned rows serve both halves.  Batches of small molecules: the tile kernel (tn_message_pair.hip).
+MsgRoute message_adjoint_gd_route(const Graph& g, int N, int F, bool rows_from_table, int own0, int own1, bool narrow) {
+  if (N <= 0) return MSG_NONE;
+  if (rows_from_table) return MSG_GD_ROW_TABLE;
+  const bool owned = own1 >= 0 && (own0 != 0 || own1 != N);
+  const bool tile = message_adjoint_pair_ok(g, N, F);
+  if (owned && !split_rows_ok(N, F) && !tile) return !narrow ? MSG_GD_ROW_TWO : MSG_GD_ROW_OWNED;
+  if (split_rows_ok(N, F)) return MSG_GD_SPLIT;
+  return tile ? MSG_GD_TILE : MSG_GD_ROW;
+}
 // slot arrays per layer: one per wave of the row kernel's block (F / 64), or one per 32-channel chunk of the tile kernel
 int message_adjoint_gd_waves(const Graph& g, int N, int F, bool rows_from_table) {
-  return (!rows_from_table && !split_rows_ok(N, F) && message_adjoint_pair_ok(g, N, F)) ? F / 32 : F / 64;
+  return message_adjoint_gd_route(g, N, F, rows_from_table) == MSG_GD_TILE ? F / 32 : F / 64;
 }
-void launch_message_adjoint_gd(const Graph& g, int N, int F, const float* w, const float* dw, const float* gMi, const float* Pn,
-                               float* gPn, float* slots, int64_t slot_stride, hipStream_t s, const PairRowTable* rt, int own0, int own1, bool narrow) {
-  const bool two = !narrow && own1 >= 0 && (own0 != 0 || own1 != N);  // no ghost-ghost pairs in the graph: the owned rows serve both halves
-  if (N <= 0) return;
+bool launch_message_adjoint_gd_as(MsgRoute r, const Graph& g, int N, int F, const float* w, const float* dw, const float* gMi,
+                                  const float* Pn, float* gPn, float* slots, int64_t slot_stride, hipStream_t s, const PairRowTable* rt,
+                                  int own0, int own1, bool narrow) {
   if (own1 < 0) {
     own0 = 0;
     own1 = N;
   }
-  if (rt) {
-    hipLaunchKernelGGL((k_message_adjoint_gd<true>), dim3(N), dim3(F), 0, s, g, N, F, w, dw, gMi, Pn, gPn, slots, slot_stride, *rt, own0, own1, narrow ? 1 : 0);
-    return;
-  }
-  if ((own0 != 0 || own1 != N) && !split_rows_ok(N, F) && !message_adjoint_pair_ok(g, N, F)) {  // an owned range: the row kernel
-                                                                                                   // (the others treat every row alike)
-    if (two)
+  switch (r) {
+    case MSG_NONE: return true;
+    case MSG_GD_ROW_TABLE:
+      if (!rt) return false;
+      hipLaunchKernelGGL((k_message_adjoint_gd<true>), dim3(N), dim3(F), 0, s, g, N, F, w, dw, gMi, Pn, gPn, slots, slot_stride, *rt, own0, own1, narrow ? 1 : 0);
+      return true;
+    case MSG_GD_ROW_TWO:
       hipLaunchKernelGGL((k_message_adjoint_gd<false, true>), dim3(own1 - own0), dim3(F), 0, s, g, N, F, w, dw, gMi, Pn, gPn, slots,
                          slot_stride, PairRowTable{}, own0, own1, 0);
-    else
+      return true;
+    case MSG_GD_ROW_OWNED:
       hipLaunchKernelGGL((k_message_adjoint_gd<false>), dim3(N), dim3(F), 0, s, g, N, F, w, dw, gMi, Pn, gPn, slots, slot_stride,
                          PairRowTable{}, own0, own1, narrow ? 1 : 0);
-    return;
+      return true;
+    case MSG_GD_SPLIT:
+      hipLaunchKernelGGL((k_message_split<2>), dim3(N), dim3(kEG * F), 0, s, g, N, F, w, gMi, dw, nullptr, 0, const_cast<float*>(Pn), gPn,
+                         slots, slot_stride);
+      return true;
+    case MSG_GD_TILE: launch_message_adjoint_pair(g, N, F, w, dw, gMi, Pn, gPn, slots, slot_stride, s); return true;
+    case MSG_GD_ROW:
+      hipLaunchKernelGGL((k_message_adjoint_gd<false>), dim3(N), dim3(F), 0, s, g, N, F, w, dw, gMi, Pn, gPn, slots, slot_stride,
+                         PairRowTable{}, 0, N, 0);
+      return true;
+    default: return false;
   }
-  if (split_rows_ok(N, F)) {
-    hipLaunchKernelGGL((k_message_split<2>), dim3(N), dim3(kEG * F), 0, s, g, N, F, w, gMi, dw, nullptr, 0, const_cast<float*>(Pn), gPn,
-                       slots, slot_stride);
-    return;
-  }
-  // batches of small molecules: the tile kernel (tn_message_pair.hip: gMi window and adjacency slice in LDS, balanced rows)
-  if (message_adjoint_pair_ok(g, N, F)) return launch_message_adjoint_pair(g, N, F, w, dw, gMi, Pn, gPn, slots, slot_stride, s);
-  hipLaunchKernelGGL((k_message_adjoint_gd<false>), dim3(N), dim3(F), 0, s, g, N, F, w, dw, gMi, Pn, gPn, slots, slot_stride,
-                     PairRowTable{}, 0, N, 0);
+}
+void launch_message_adjoint_gd(const Graph& g, int N, int F, const float* w, const float* dw, const float* gMi, const float* Pn,
+                               float* gPn, float* slots, int64_t slot_stride, hipStream_t s, const PairRowTable* rt, int own0, int own1, bool narrow) {
+  launch_message_adjoint_gd_as(message_adjoint_gd_route(g, N, F, rt != nullptr, own0, own1, narrow), g, N, F, w, dw, gMi, Pn, gPn, slots,
+                               slot_stride, s, rt, own0, own1, narrow);
 }
 
 // Value + tangent of a neighbour sum in ONE sweep (second-order pass, tn_hvp_api.hip):
@@ -1078,10 +1110,29 @@ __global__ void k_message_dual(Graph g, int N, int F, const float* __restrict__ 
     }
   }
 }
+// small systems: the split-row sweeps (the chip is mostly idle there: three launches are fine)
+MsgRoute message_dual_route(int N, int F, bool accumulate) {
+  if (N <= 0) return MSG_NONE;
+  if (split_rows_ok(N, F)) return MSG_DUAL_SPLIT3;
+  return accumulate ? MSG_DUAL_ACC : MSG_DUAL;
+}
+bool launch_message_dual_as(MsgRoute r, const Graph& g, int N, int F, const float* w, const float* w_t, const float* src,
+                            const float* src_t, float* out, float* out_t, hipStream_t s) {
+  switch (r) {
+    case MSG_NONE: return true;
+    case MSG_DUAL_ACC:
+      hipLaunchKernelGGL((k_message_dual<true>), dim3(N), dim3(fthreads(F)), 0, s, g, N, F, w, w_t, src, src_t, out, out_t);
+      return true;
+    case MSG_DUAL:
+      hipLaunchKernelGGL((k_message_dual<false>), dim3(N), dim3(fthreads(F)), 0, s, g, N, F, w, w_t, src, src_t, out, out_t);
+      return true;
+    default: return false;
+  }
+}
 void launch_message_dual(const Graph& g, int N, int F, const float* w, const float* w_t, const float* src, const float* src_t,
                          float* out, float* out_t, bool accumulate, hipStream_t s) {
-  if (N <= 0) return;
-  if (split_rows_ok(N, F)) {  // small systems: the split-row sweeps (the chip is mostly idle there: three launches are fine)
+  const MsgRoute r = message_dual_route(N, F, accumulate);
+  if (r == MSG_DUAL_SPLIT3) {
     if (!accumulate) {
       launch_fill(out, 0.f, (int64_t)N * 9 * F, s);
       launch_fill(out_t, 0.f, (int64_t)N * 9 * F, s);
@@ -1091,17 +1142,25 @@ void launch_message_dual(const Graph& g, int N, int F, const float* w, const flo
     launch_message_adjoint(g, N, F, w_t, src, out_t, s);
     return;
   }
-  if (accumulate) hipLaunchKernelGGL((k_message_dual<true>), dim3(N), dim3(fthreads(F)), 0, s, g, N, F, w, w_t, src, src_t, out, out_t);
-  else hipLaunchKernelGGL((k_message_dual<false>), dim3(N), dim3(fthreads(F)), 0, s, g, N, F, w, w_t, src, src_t, out, out_t);
+  launch_message_dual_as(r, g, N, F, w, w_t, src, src_t, out, out_t, s);
 }
 
-void launch_message_adjoint(const Graph& g, int N, int F, const float* w, const float* gMi, float* gPn, hipStream_t s) {
-  if (N <= 0) return;
-  if (split_rows_ok(N, F)) {
-    hipLaunchKernelGGL((k_message_split<1>), dim3(N), dim3(kEG * F), 0, s, g, N, F, w, gMi, nullptr, nullptr, 0, nullptr, gPn);
-    return;
+MsgRoute message_adjoint_route(int N, int F) {
+  if (N <= 0) return MSG_NONE;
+  return split_rows_ok(N, F) ? MSG_ADJ_SPLIT : MSG_ADJ_ROW;
+}
+bool launch_message_adjoint_as(MsgRoute r, const Graph& g, int N, int F, const float* w, const float* gMi, float* gPn, hipStream_t s) {
+  switch (r) {
+    case MSG_NONE: return true;
+    case MSG_ADJ_SPLIT:
+      hipLaunchKernelGGL((k_message_split<1>), dim3(N), dim3(kEG * F), 0, s, g, N, F, w, gMi, nullptr, nullptr, 0, nullptr, gPn);
+      return true;
+    case MSG_ADJ_ROW: hipLaunchKernelGGL(k_message_adjoint, dim3(N), dim3(fthreads(F)), 0, s, g, N, F, w, gMi, gPn); return true;
+    default: return false;
   }
-  hipLaunchKernelGGL(k_message_adjoint, dim3(N), dim3(fthreads(F)), 0, s, g, N, F, w, gMi, gPn);
+}
+void launch_message_adjoint(const Graph& g, int N, int F, const float* w, const float* gMi, float* gPn, hipStream_t s) {
+  launch_message_adjoint_as(message_adjoint_route(N, F), g, N, F, w, gMi, gPn, s);
 }
 
 // X_new = X_hat + dX + kappa * dX.dX    (reference tensornet.py:811-812; residual on the normalised X)

@@ -412,8 +412,11 @@ __global__ __launch_bounds__(64 * LPR) void k_message_rows8(Graph g, int N, int 
 // the tile's column window sit in LDS, the Pn row of the row being walked in registers (a helper group holds the LONG row's Pn
 // while it walks that row's tail, then its own); per edge a lane loads six 16-byte pieces (w, dw) and reads nine from LDS; the 8
 // lanes of a row reduce their channel products and lane 0 writes the slot (channel chunk, pair, direction): one writer per slot,
-// summed in fixed order by the embedding's pair kernel.  Tiles whose window or adjacency slice does not fit LDS are not taken by
-// this kernel at all (message_adjoint_pair_ok looks at the batch; the row kernel serves them).
+// summed in fixed order by the embedding's pair kernel.  message_adjoint_pair_ok looks at the batch as a whole (g.small_mols: the
+// AVERAGE molecule has at most 96 atoms), so a large molecule in a batch of small ones does come here: a tile whose window is
+// wider than MP_W rows gathers gMi from global memory, one whose slice exceeds MP_E entries reads its records from global memory
+// and walks every row with its own group only (no helpers); both block-uniform, both compared with fp64 in
+// tests/test_gpu_message.py and, through the engine, in tests/test_gpu_bench_scale.py.
 __global__ __launch_bounds__(512) void k_message_adjoint_rows8(Graph g, int N, int F, const float* __restrict__ w,
                                                                const float* __restrict__ dw, const float* __restrict__ gMi,
                                                                const float* __restrict__ Pn, float* __restrict__ gPn,
@@ -686,9 +689,10 @@ bool message_pair_ok(int N, int F) {
   return (int64_t)((N + MP_TA - 1) / MP_TA) * (F / MP_FC) >= 512;
 }
 void launch_message_pair(const Graph& g, int N, int F, const float* w, const float* src, const float* q, const int64_t* batch,
-                         int o3, float* Mi, float* Ch, hipStream_t s) {
+                         int o3, float* Mi, float* Ch, hipStream_t s, int balance_arg) {
   const int nchunks = F / MP_FC, tiles = (N + MP_TA - 1) / MP_TA;
-  static const int balance = getenv("TMDNET_MSG_NOBALANCE") ? 0 : 1;  // developer switch: every row walked by its own group only
+  static const int balance_env = getenv("TMDNET_MSG_NOBALANCE") ? 0 : 1;  // developer switch: every row walked by its own group only
+  const int balance = balance_arg < 0 ? balance_env : (balance_arg ? 1 : 0);
   hipLaunchKernelGGL((k_message_rows8<8, 4>), dim3(tiles * nchunks), dim3(512), 0, s, g, N, F, w, src, q, batch, o3, Mi, Ch, nchunks, balance);
 }
 

@@ -161,6 +161,7 @@ struct tmdnet_model {
   int* halo_rng = nullptr;          // device scratch: first / last / count of the owned rows in the engine's order
   bool graph_no_ghost_pairs = false;  // the last graph was built with the exchange set: no pairs of two ghosts in it
   int halo_active[2] = {0, 0};      // [first row, rows] the per-atom kernels of the last step ran on ("halo_active_rows")
+  int msg_route_last[2] = {0, 0};   // MsgRoute of the last step's forward and reverse neighbour sweeps ("message_route_last", "message_adjoint_route_last")
   tmdnet_hparams hp;
   int head_kind = 0;  // tmdnet_set_output_head: 0 scalar, 1 dipole moment, 2 electronic spatial extent (tn_heads.hip)
   TrainCtx* train = nullptr;  // non-null while tmdnet_energy_param_grads drives tmdnet_energy_forces

@@ -58,6 +58,18 @@ class GemmExArgs(C.Structure):
     ]
 
 
+class MessageArgs(C.Structure):
+    """tmdnet_message_args (include/tmdnet_amd.h): one neighbour sweep on a caller-built graph, tmdnet_debug_message."""
+    _fields_ = [(n, C.c_int32) for n in ("op", "kernel", "N", "F", "P", "small_mols", "o3", "balance", "accumulate")] + \
+               [(n, C.c_void_p) for n in ("rowptr", "col", "epair", "esign", "counts", "w", "w2", "src", "src2", "q", "batch", "out",
+                                          "out2", "slots")] + [("slot_stride", C.c_int64)]
+
+
+# sweeps and kernels of tmdnet_debug_message (TMDNET_MSG_* in the header)
+MSG_OP_FWD, MSG_OP_ADJ, MSG_OP_GD, MSG_OP_DUAL = range(4)
+(MSG_AUTO, MSG_FWD_ROW, MSG_FWD_SPLIT, MSG_FWD_TILE, MSG_ADJ_ROW, MSG_ADJ_SPLIT, MSG_GD_ROW, MSG_GD_SPLIT, MSG_GD_TILE, MSG_DUAL,
+ MSG_DUAL_ACC) = range(11)
+MSG_DUAL_SPLIT3 = 16
 # flags and routes of tmdnet_debug_gemm_ex (TMDNET_GEMM_* in the header)
 GEMM_ACT_SILU, GEMM_MUL_AUX, GEMM_MUL_DSILU_AUX, GEMM_ACCUM, GEMM_ROWSCALE = 1, 2, 4, 8, 16
 (GEMM_ROUTE_NONE, GEMM_ROUTE_SKINNY4, GEMM_ROUTE_SKINNY8, GEMM_ROUTE_TILES_128X128, GEMM_ROUTE_TILES_128X64,
@@ -131,6 +143,7 @@ def lib():
     L.tmdnet_debug_gemm.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, vp]
     L.tmdnet_debug_gemm_ex.argtypes = [vp, C.POINTER(GemmExArgs), C.POINTER(i32)]
     L.tmdnet_debug_tlin9.argtypes = [vp, i32, i32, i64, i64] + [vp] * 11 + [i32, vp, vp, vp, vp, C.POINTER(i64)]
+    L.tmdnet_debug_message.argtypes = [vp, C.POINTER(MessageArgs), C.POINTER(i32), C.POINTER(i32)]
     L.tmdnet_param_grad_count.argtypes = [vp]
     L.tmdnet_param_grad_entry.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64)]
     L.tmdnet_param_grad_entry.restype = C.c_char_p
