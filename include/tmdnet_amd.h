@@ -790,6 +790,68 @@ int tmdnet_min_advance_cell(tmdnet_model* m, void* stream, void* graph_ws, void*
 /* tmdnet_min_status, and host[2] = what was unusable when status is 2: 1 a force sum, 2 the virial, 3 the volume of the box. */
 int tmdnet_min_status_cell(void* stream, void* min_ws, uint64_t host[3]);
 
+/* ---- Device-resident nudged elastic band (csrc/tn_neb.hip; additive exports, the ABI revision stays 10) ------------------------
+ * A minimum-energy path and its saddle point: NEB with the improved tangent (Henkelman and Jonsson, J. Chem. Phys. 113, 9978, 2000)
+ * and a climbing image, driven by the FIRE controller above with ONE controller per band.  The launches sit between two
+ * tmdnet_energy_forces calls of a captured step: K band steps replay as one HIP graph.
+ * Storage: a band has M >= 3 images of the same n atoms, a call has G >= 1 bands; rows are image-major, atom a of image i of band g
+ * is row (g M + i) n + a, and the evaluation sees G M molecules of n atoms.  Images 0 and M - 1 of every band never move (a branch:
+ * their positions keep their bits); they are evaluated with the rest and their energies feed the tangents.  No minimum image is
+ * applied between images: the caller supplies an unwrapped path.
+ * Per step, for every interior image i, from the energies E and forces F at the current positions:
+ *   per atom, fp32 under the rounding contract of the MD loop:  d+ = R_{i+1} - R_i,  d- = R_i - R_{i-1}  (one rounded sum per
+ *     component), and the terms  d+.d+, d-.d-, d+.d-, F.d+, F.d-  each as (x + y) + z of three rounded products; an atom with
+ *     fixed[a] != 0 contributes nothing
+ *   per image, the terms widened and added in fp64 in the fixed order of the minimiser's sums:  a, b, c, p, q
+ *   per image, fp64, from the fp32 energies widened - the improved tangent tau = w+ d+ + w- d-:
+ *     E_{i+1} > E_i > E_{i-1}: (w+, w-) = (1, 0);   E_{i+1} < E_i < E_{i-1}: (0, 1);   otherwise hi / lo = the larger / smaller of
+ *     |E_{i+1} - E_i| and |E_{i-1} - E_i|, and (w+, w-) = (hi, lo) when E_{i+1} > E_{i-1}, else (lo, hi)
+ *     |tau|^2 = ((w+ w+) a + ((2 w+) w-) c) + (w- w-) b;   F.tau = w+ p + w- q
+ *     g = (-(F.tau / |tau|) + k (sqrt a - sqrt b)) / |tau|       (F - (F.tau^) tau^ + k (|d+| - |d-|) tau^; k = spring_k, E / length^2)
+ *     the climber, when climbing is on: g = (-2 F.tau) / |tau|^2  (F - 2 (F.tau^) tau^, no spring).  The climber of a band is the
+ *     lowest interior index with the largest energy, chosen anew at every step from that step's energies.
+ *     s+ = fp32(g w+), s- = fp32(g w-), each rounded once
+ *   per atom, fp32 under the contract:  F_neb = (F + s+ d+) + s- d-;  a fixed atom keeps F, an endpoint image has F_neb = 0
+ *   per band: vf, ff, vv, fmax2 of the minimiser over all interior images on F_neb (per image in the minimiser's order, the images
+ *     added in image order), then the minimiser's controller, unchanged: the band converges when sqrt(fmax2) < fmax and freezes then,
+ *     and the max_step clamp acts on the whole band's move
+ *   per atom the minimiser's update with the band's three coefficients; fixed atoms, endpoint images and frozen bands: v <- 0, x
+ *     is not touched.
+ * A band that still moves is unusable - status 2, nothing of that step is written - when an energy of the band is not finite
+ * (cause 3), when |tau|^2 of an image is zero or not finite (cause 2: coincident images), or when F.tau or a FIRE sum is not
+ * finite (cause 1).  When every atom is fixed no image has a degree of freedom: no tangent is formed, nothing is unusable and the
+ * band converges as it stands.  Overflow is the minimiser's protocol: the move saves x and v, an overflowed evaluation latches status 1 and
+ * puts them back.  Only the single-block controller writes the status word; every later launch returns at once until a reset. */
+/* Bytes of the band state `neb_ws`: a 256-byte header (step counter, status, the start values, the climb flag, the cause), per band
+ * the controller's state and coefficients, per image its path sums, weights, coefficients and the slice sums, per row the position
+ * and velocity before the last move and F_neb (36 bytes).  n_images >= 3, n_bands >= 1. */
+int tmdnet_neb_workspace_bytes(int64_t n_atoms_per_image, int64_t n_images, int64_t n_bands, size_t* bytes);
+/* tmdnet_min_reset, and climb = 1 / 0 switches the climbing image on / off for every band: one captured graph serves the plain phase
+ * and the climbing phase.  The first launch after it must be tmdnet_neb_advance(TMDNET_MIN_CLOSE) on the start path (vel = 0). */
+int tmdnet_neb_reset(void* stream, void* neb_ws, uint64_t step0, double dt0, double alpha0, int32_t climb);
+/* Enqueues one phase (TMDNET_MIN_OPEN / MIDDLE / CLOSE with the minimiser's meaning).  MIDDLE and CLOSE are four launches - the path
+ * sums on a grid (image, slice); the projection on the same grid, every block deriving its image's coefficients from the slice sums;
+ * the controller as one block; one thread per row - and OPEN is one.  The arguments of tmdnet_min_advance with its meaning, except:
+ *   n_atoms_per_image, n_images, n_bands   replace n_atoms, n_mol and batch (the evaluation had n_images n_bands molecules).
+ *   forces        MIDDLE / CLOSE: the evaluation's F;  OPEN: the kept F_neb.
+ *   energy        [n_bands, n_images], required for MIDDLE / CLOSE.
+ *   fixed         [n_atoms_per_image] bytes or NULL: the same atoms in every image.
+ *   forces_keep   receives F_neb once the step is accepted.
+ *   spring_k      > 0, after fmax.
+ *   log rows      epot [n_bands, n_images]; fmax, sums, coef, dt, alpha, converged_at per BAND as for the minimiser; then per image
+ *                 path_sums [n_bands, n_images, 5] fp64 (a, b, c, p, q), weights [.., 2] fp64 (w+, w-), tangent_coef [.., 2] fp32
+ *                 (s+, s-), zero on endpoints; and climber [n_bands] int32, the interior image with the largest energy (the image
+ *                 that climbs when climbing is on).  Each may be NULL. */
+int tmdnet_neb_advance(tmdnet_model* m, void* stream, void* graph_ws, void* neb_ws, int64_t n_atoms_per_image, int64_t n_images,
+                       int64_t n_bands, int32_t phase, float* pos, float* vel, const float* forces, const float* energy,
+                       const uint8_t* fixed, float* forces_keep, double dt_max, int32_t n_min, double f_inc, double f_dec, double alpha0,
+                       double f_alpha, double max_step, double fmax, double spring_k, float* epot_log_row, float* fmax_log_row,
+                       double* sums_log_row, float* coef_log_row, double* dt_log_row, double* alpha_log_row,
+                       int64_t* converged_log_row, double* path_sums_log_row, double* weights_log_row, float* tangent_coef_log_row,
+                       int32_t* climber_log_row);
+/* tmdnet_min_status, and host[2] = what was unusable when status is 2: 1 a force sum, 2 the path (coincident images), 3 an energy. */
+int tmdnet_neb_status(void* stream, void* neb_ws, uint64_t host[3]);
+
 #ifdef __cplusplus
 }
 #endif

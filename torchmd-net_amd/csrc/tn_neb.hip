@@ -1,0 +1,599 @@
+// Device-resident nudged elastic band: the kernels that sit between two energy+force evaluations of a captured step, so that K band
+// steps replay as one HIP graph with no host work in between.  A band is M images of the same n atoms, a call has G bands; rows are
+// image-major, atom a of image i of band g is row (g M + i) n + a, and the evaluation sees G M molecules of n atoms.  Images 0 and
+// M - 1 of every band never move.  The arithmetic is tn_neb_math.h (tangents, band force) and tn_min_math.h (FIRE, one controller per
+// band).  The scheme is stated with the entries in include/tmdnet_amd.h.
+//
+// One step, after the energies E and forces F at the current positions are known - four launches:
+//   path      grid (image, slice): the five path sums a, b, c, p, q of every interior image   (fp32 terms, fp64 sums, fixed order),
+//             and the number of atoms that are not fixed (none: the image has no degree of freedom and needs no tangent)
+//   project   grid (image, slice): every block derives its image's weights and its two coefficients from the slice sums and the band's
+//             energies itself (every block of an image computes the same bits), writes F_neb into the workspace and reduces the
+//             FIRE terms v.F_neb, F_neb.F_neb, v.v, max |F_neb|^2 per image
+//   control   ONE block, bands strided: the images' sums added in image order, tn_min::fire_control, the status word, the logs
+//   atoms     per atom: accept (F_neb -> forces_keep, or the saved state back after an overflow) and, in MIDDLE, the move
+// CLOSE omits the move, OPEN is the move alone from the coefficients the workspace holds and the kept F_neb.
+//
+// Reductions follow k_min_reduce: threads stride the atoms of a slice, lanes add by the wave's xor tree, waves in turn, slices in
+// slice order.  No floating-point atomics: repeats are bit-identical.
+//
+// Overflow, non-finite sums and unusable tangents follow the minimiser's protocol: the controller is the only kernel that writes
+// the status word; an overflowed evaluation latches status 1 and the per-atom kernel puts x and v back; a band that still moves
+// and has an energy that is not finite, a tangent of length zero or a sum that is not finite latches status 2 (the cause in header
+// word 5) before anything of that step is written.  From then on every launch returns at once until tmdnet_neb_reset.
+#include <cmath>
+#include <string>
+
+#include "tmdnet_amd.h"
+#include "tn_common.h"
+#include "tn_model.h"
+#include "tn_neb_math.h"
+
+namespace tn {
+
+namespace {
+
+constexpr int kNebThreads = 256;
+constexpr size_t kNebHeaderBytes = 256;
+// The header: six uint32 words, then two doubles.  Words 0 / 1 the step counter (lo / hi), 2 the status, 3 "reset, not yet controlled",
+constexpr int kNebClimbWord = 4;       // 1: the climbing image is on
+constexpr int kNebCauseWord = 5;       // which input was unusable when status 2 was latched (tn_neb::NEB_*)
+constexpr int kNebHeadWords = 6;       // words the status entry reads back
+constexpr size_t kNebStartByte = 32;   // dt0, alpha0 (fp64)
+static_assert(kNebClimbWord > 3 && kNebCauseWord != kNebClimbWord && kNebCauseWord < kNebHeadWords, "header words must not overlap");
+static_assert(kNebHeadWords * sizeof(uint32_t) <= kNebStartByte && kNebStartByte % sizeof(double) == 0 &&
+                  kNebStartByte + 2 * sizeof(double) <= kNebHeaderBytes,
+              "the start values lie behind the header words, aligned, inside the header");
+
+struct NebState {  // views into the caller's workspace
+  uint32_t* head;       // [0] step lo, [1] step hi, [2] status, [3] 1 = reset, not yet controlled, [4] climb, [5] cause of status 2
+  double* start;        // [0] dt0, [1] alpha0 (header bytes 32..47, behind the six words)
+  double* dt;           // [G]
+  double* alpha;        // [G]
+  int64_t* conv;        // [G] converged_at
+  int32_t* n_pos;       // [G]
+  float* coef;          // [G, 3] c_v, c_f, d of the next move
+  double* img_sums;     // [G M, 5] a, b, c, p, q
+  double* img_w;        // [G M, 2] w+, w-
+  float* img_s;         // [G M, 2] s+, s-
+  int32_t* img_why;     // [G M] tn_neb::NEB_*
+  double* path_slices;  // [G M, S, 6] a, b, c, p, q and the number of atoms that are not fixed
+  double* fire_slices;  // [G M, S, 4]
+  float* x_keep;        // [N, 3] positions before the last move
+  float* v_keep;        // [N, 3]
+  float* f_neb;         // [N, 3] F_neb of the evaluation being controlled
+};
+
+inline size_t neb_align256(size_t n) { return (n + 255) & ~size_t(255); }
+
+// slices per image: tn_min.hip's min_slices with one image as the molecule
+int neb_slices(int64_t n) {
+  if (n <= 1024) return 1;
+  const int64_t s = (n + 1023) / 1024;
+  return (int)(s > 256 ? 256 : s);
+}
+
+struct NebSizes {
+  size_t g, gm, N, S;
+};
+
+NebSizes neb_sizes(int64_t n, int64_t M, int64_t G) {
+  NebSizes z;
+  z.g = (size_t)(G > 0 ? G : 0);
+  z.gm = z.g * (size_t)(M > 0 ? M : 0);
+  z.N = z.gm * (size_t)(n > 0 ? n : 0);
+  z.S = (size_t)neb_slices(n);
+  return z;
+}
+
+size_t neb_bytes(int64_t n, int64_t M, int64_t G) {
+  const NebSizes z = neb_sizes(n, M, G);
+  return kNebHeaderBytes + 3 * neb_align256(z.g * 8) + neb_align256(z.g * 4) + neb_align256(z.g * 3 * sizeof(float)) +
+         neb_align256(z.gm * 5 * 8) + neb_align256(z.gm * 2 * 8) + neb_align256(z.gm * 2 * sizeof(float)) + neb_align256(z.gm * 4) +
+         neb_align256(z.gm * z.S * 6 * 8) + neb_align256(z.gm * z.S * 4 * 8) + 3 * neb_align256(z.N * 3 * sizeof(float)) +
+         256;  // + room to align the pointer
+}
+
+NebState carve_neb(void* ws, int64_t n, int64_t M, int64_t G) {
+  char* p = reinterpret_cast<char*>(neb_align256(reinterpret_cast<size_t>(ws)));
+  const NebSizes z = neb_sizes(n, M, G);
+  NebState st;
+  st.head = reinterpret_cast<uint32_t*>(p);
+  st.start = reinterpret_cast<double*>(p + kNebStartByte);
+  p += kNebHeaderBytes;
+  auto take = [&p](size_t bytes) {
+    char* q = p;
+    p += neb_align256(bytes);
+    return q;
+  };
+  st.dt = reinterpret_cast<double*>(take(z.g * 8));
+  st.alpha = reinterpret_cast<double*>(take(z.g * 8));
+  st.conv = reinterpret_cast<int64_t*>(take(z.g * 8));
+  st.n_pos = reinterpret_cast<int32_t*>(take(z.g * 4));
+  st.coef = reinterpret_cast<float*>(take(z.g * 3 * sizeof(float)));
+  st.img_sums = reinterpret_cast<double*>(take(z.gm * 5 * 8));
+  st.img_w = reinterpret_cast<double*>(take(z.gm * 2 * 8));
+  st.img_s = reinterpret_cast<float*>(take(z.gm * 2 * sizeof(float)));
+  st.img_why = reinterpret_cast<int32_t*>(take(z.gm * 4));
+  st.path_slices = reinterpret_cast<double*>(take(z.gm * z.S * 6 * 8));
+  st.fire_slices = reinterpret_cast<double*>(take(z.gm * z.S * 4 * 8));
+  st.x_keep = reinterpret_cast<float*>(take(z.N * 3 * sizeof(float)));
+  st.v_keep = reinterpret_cast<float*>(take(z.N * 3 * sizeof(float)));
+  st.f_neb = reinterpret_cast<float*>(take(z.N * 3 * sizeof(float)));
+  return st;
+}
+
+__device__ __forceinline__ uint64_t neb_step(const NebState& st) { return (uint64_t)st.head[0] | ((uint64_t)st.head[1] << 32); }
+
+// K sums of one block in the order of k_min_reduce (lanes by the xor tree, waves in turn); entry MAXK (-1: none) takes the maximum
+// instead.  Thread 0 holds the result in acc.
+template <int K, int MAXK>
+__device__ __forceinline__ void neb_block_reduce(double acc[K], double (*sh)[kNebThreads / 64]) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const double other = __shfl_xor(acc[k], o, 64);
+      if (k == MAXK)
+        acc[k] = other > acc[k] ? other : acc[k];
+      else
+        acc[k] += other;
+    }
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < K; ++k) sh[k][threadIdx.x >> 6] = acc[k];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (k == MAXK) {
+        double mx = sh[k][0];
+#pragma unroll
+        for (int w = 1; w < kNebThreads / 64; ++w) mx = sh[k][w] > mx ? sh[k][w] : mx;
+        acc[k] = mx;
+      } else {
+        acc[k] = ((sh[k][0] + sh[k][1]) + sh[k][2]) + sh[k][3];
+      }
+    }
+  }
+}
+
+struct NebGeom {
+  int n, M, G, S;
+};
+
+// d+ and d- of atom a of interior image `img` (rows img n + a and its two neighbours' n rows away)
+__device__ __forceinline__ void neb_load_diff(const float* __restrict__ pos, int64_t row, int n, float dp[3], float dm[3]) {
+  float xp[3], x[3], xn[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    xp[d] = pos[(row - n) * 3 + d];
+    x[d] = pos[row * 3 + d];
+    xn[d] = pos[(row + n) * 3 + d];
+  }
+  tn_neb::path_diff(xp, x, xn, dp, dm);
+}
+
+// grid (G M, S): slice s of interior image img -> path_slices[img, s, 0..5]
+__global__ __launch_bounds__(kNebThreads) void k_neb_path(NebState st, NebGeom g, const int* __restrict__ counts,
+                                                          const float* __restrict__ pos, const float* __restrict__ forces,
+                                                          const uint8_t* __restrict__ fixed) {
+  __shared__ double sh[6][kNebThreads / 64];
+  if (st.head[2]) return;           // frozen
+  if (counts && counts[2]) return;  // overflowed: stale forces, the controller latches it
+  const int img = blockIdx.x, s = blockIdx.y, i = img % g.M;
+  if (i == 0 || i == g.M - 1) return;  // an endpoint has no tangent
+  const int a0 = (int)((int64_t)g.n * s / g.S), a1 = (int)((int64_t)g.n * (s + 1) / g.S);
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int a = a0 + (int)threadIdx.x; a < a1; a += kNebThreads) {
+    const int64_t row = (int64_t)img * g.n + a;
+    const int fx = fixed && fixed[a];
+    float dp[3], dm[3], f[3], t[5];
+    neb_load_diff(pos, row, g.n, dp, dm);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) f[d] = forces[row * 3 + d];
+    tn_neb::path_terms(dp, dm, f, fx, t);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) acc[k] += (double)t[k];
+    acc[5] += fx ? 0.0 : 1.0;  // (a count: exact)
+  }
+  neb_block_reduce<6, -1>(acc, sh);
+  if (threadIdx.x == 0) {
+    double* out = st.path_slices + ((int64_t)img * g.S + s) * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) out[k] = acc[k];
+  }
+}
+
+// grid (G M, S), after k_neb_path: the image's coefficients (every block of the image computes the same bits; the block of slice 0
+// records them), F_neb of the slice's atoms into the workspace, fire_slices[img, s, 0..3] = v.F_neb, F_neb.F_neb, v.v, max |F_neb|^2
+__global__ __launch_bounds__(kNebThreads) void k_neb_project(NebState st, NebGeom g, const int* __restrict__ counts,
+                                                             const float* __restrict__ pos, const float* __restrict__ vel,
+                                                             const float* __restrict__ forces, const float* __restrict__ energy,
+                                                             const uint8_t* __restrict__ fixed, double spring_k) {
+  __shared__ double sh[4][kNebThreads / 64];
+  if (st.head[2]) return;
+  if (counts && counts[2]) return;
+  const int img = blockIdx.x, s = blockIdx.y, i = img % g.M;
+  const int a0 = (int)((int64_t)g.n * s / g.S), a1 = (int)((int64_t)g.n * (s + 1) / g.S);
+  if (i == 0 || i == g.M - 1) {  // an endpoint feels no band force
+    for (int a = a0 + (int)threadIdx.x; a < a1; a += kNebThreads) {
+      const int64_t row = (int64_t)img * g.n + a;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) st.f_neb[row * 3 + d] = 0.f;
+    }
+    return;
+  }
+  double S5[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, w[2];  // [5]: the number of atoms that are not fixed
+  float sc[2];
+  const double* sl = st.path_slices + (int64_t)img * g.S * 6;
+  for (int k = 0; k < g.S; ++k)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) S5[j] += sl[k * 6 + j];
+  const int why = tn_neb::image_control(energy + (int64_t)(img - i), g.M, i, S5, spring_k, st.head[kNebClimbWord] != 0, S5[5] > 0.0, w, sc);
+  if (s == 0 && threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) st.img_sums[(int64_t)img * 5 + j] = S5[j];
+    st.img_w[img * 2 + 0] = w[0];
+    st.img_w[img * 2 + 1] = w[1];
+    st.img_s[img * 2 + 0] = sc[0];
+    st.img_s[img * 2 + 1] = sc[1];
+    st.img_why[img] = why;
+  }
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int a = a0 + (int)threadIdx.x; a < a1; a += kNebThreads) {
+    const int64_t row = (int64_t)img * g.n + a;
+    const int fx = fixed && fixed[a];
+    float dp[3], dm[3], f[3], v[3], fn[3], t[3];
+    neb_load_diff(pos, row, g.n, dp, dm);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      f[d] = forces[row * 3 + d];
+      v[d] = vel[row * 3 + d];
+    }
+    if (fx) {  // a fixed atom is outside the band: it keeps the force of the evaluation
+#pragma unroll
+      for (int d = 0; d < 3; ++d) fn[d] = f[d];
+    } else {
+      tn_neb::project(f, dp, dm, sc[0], sc[1], fn);
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) st.f_neb[row * 3 + d] = fn[d];
+    tn_min::atom_terms(v, fn, fx, t);
+    acc[0] += (double)t[0];
+    acc[1] += (double)t[1];
+    acc[2] += (double)t[2];
+    acc[3] = (double)t[1] > acc[3] ? (double)t[1] : acc[3];
+  }
+  neb_block_reduce<4, 3>(acc, sh);
+  if (threadIdx.x == 0) {
+    double* out = st.fire_slices + ((int64_t)img * g.S + s) * 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[k] = acc[k];
+  }
+}
+
+struct NebCtlArgs {
+  NebGeom g;
+  tn_min::FireParams p;
+  const int* counts;  // the graph's counters, or NULL
+  const float* energy;
+  float* epot_row;      // [G, M]
+  float* fmax_row;      // [G]
+  double* sums_row;     // [G, 4]
+  float* coef_row;      // [G, 3]
+  double* dt_row;       // [G]
+  double* alpha_row;    // [G]
+  int64_t* conv_row;    // [G]
+  double* path_row;     // [G, M, 5]
+  double* weights_row;  // [G, M, 2]
+  float* tcoef_row;     // [G, M, 2]
+  int32_t* climber_row; // [G]
+  NebState st;
+};
+
+// the FIRE sums of band b (per image the slices in slice order, then the images in image order), its state (after a reset: the
+// start values of the header) and the largest cause among its interior images
+__device__ __forceinline__ int neb_load(const NebCtlArgs& a, int b, bool fresh, double sums[4], tn_min::FireState* s) {
+  sums[0] = sums[1] = sums[2] = sums[3] = 0.0;
+  int why = 0;
+  for (int i = 1; i < a.g.M - 1; ++i) {
+    const int img = b * a.g.M + i;
+    const double* sl = a.st.fire_slices + (int64_t)img * a.g.S * 4;
+    double t[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < a.g.S; ++k) {
+      t[0] += sl[k * 4 + 0];
+      t[1] += sl[k * 4 + 1];
+      t[2] += sl[k * 4 + 2];
+      t[3] = sl[k * 4 + 3] > t[3] ? sl[k * 4 + 3] : t[3];
+    }
+    sums[0] += t[0];
+    sums[1] += t[1];
+    sums[2] += t[2];
+    sums[3] = t[3] > sums[3] ? t[3] : sums[3];
+    why = a.st.img_why[img] > why ? a.st.img_why[img] : why;
+  }
+  if (fresh) {
+    s->dt = a.st.start[0];
+    s->alpha = a.st.start[1];
+    s->n_pos = 0;
+    s->converged_at = -1;
+  } else {
+    s->dt = a.st.dt[b];
+    s->alpha = a.st.alpha[b];
+    s->n_pos = a.st.n_pos[b];
+    s->converged_at = a.st.conv[b];
+  }
+  return why;
+}
+
+// ONE block striding the bands, after k_neb_project: k_min_control with the tangents' causes.  Pass 1: is any band that still moves
+// unusable?  Pass 2, only when none is: every band's state, coefficients and log rows; then thread 0 advances the step counter.
+__global__ __launch_bounds__(kNebThreads) void k_neb_control(NebCtlArgs a) {
+  __shared__ int bad;
+  if (a.st.head[2]) return;  // frozen
+  if (a.counts && a.counts[2]) {
+    if (threadIdx.x == 0) a.st.head[2] = 1u;
+    return;
+  }
+  const bool fresh = a.st.head[3] != 0;
+  const uint64_t step = neb_step(a.st) + (fresh ? 0 : 1);
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();  // (every thread has read the header by now: thread 0 rewrites it at the end)
+  int cause = 0;
+  double sums[4];
+  float coef[3];
+  tn_min::FireState s;
+  for (int b = threadIdx.x; b < a.g.G; b += kNebThreads) {
+    const int why = neb_load(a, b, fresh, sums, &s);
+    if (s.converged_at >= 0) continue;  // a band that has converged looks at nothing
+    int c = why;
+    if (!c && tn_min::fire_control(&s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef) == tn_min::FIRE_UNUSABLE)
+      c = tn_neb::NEB_BAD_SUMS;
+    cause = c > cause ? c : cause;
+  }
+  if (cause) atomicMax(&bad, cause);  // (an integer in LDS)
+  __syncthreads();
+  if (bad) {
+    if (threadIdx.x == 0) {
+      a.st.head[kNebCauseWord] = (uint32_t)bad;
+      a.st.head[2] = 2u;
+    }
+    return;
+  }
+  const int M = a.g.M;
+  for (int b = threadIdx.x; b < a.g.G; b += kNebThreads) {
+    neb_load(a, b, fresh, sums, &s);
+    tn_min::fire_control(&s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef);
+    a.st.dt[b] = s.dt;
+    a.st.alpha[b] = s.alpha;
+    a.st.n_pos[b] = s.n_pos;
+    a.st.conv[b] = s.converged_at;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.st.coef[b * 3 + k] = coef[k];
+    if (a.epot_row)
+      for (int i = 0; i < M; ++i) a.epot_row[b * M + i] = a.energy[b * M + i];
+    if (a.fmax_row) a.fmax_row[b] = (float)sqrt(sums[3]);
+    if (a.sums_row)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a.sums_row[(int64_t)b * 4 + k] = sums[k];
+    if (a.coef_row)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) a.coef_row[(int64_t)b * 3 + k] = coef[k];
+    if (a.dt_row) a.dt_row[b] = s.dt;
+    if (a.alpha_row) a.alpha_row[b] = s.alpha;
+    if (a.conv_row) a.conv_row[b] = s.converged_at;
+    if (a.climber_row) a.climber_row[b] = tn_neb::climber(a.energy + (int64_t)b * M, M);
+    for (int i = 0; i < M; ++i) {  // an endpoint's rows are zero
+      const int64_t img = (int64_t)b * M + i;
+      const bool inner = i > 0 && i < M - 1;
+      if (a.path_row)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) a.path_row[img * 5 + k] = inner ? a.st.img_sums[img * 5 + k] : 0.0;
+      if (a.weights_row)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) a.weights_row[img * 2 + k] = inner ? a.st.img_w[img * 2 + k] : 0.0;
+      if (a.tcoef_row)
+#pragma unroll
+        for (int k = 0; k < 2; ++k) a.tcoef_row[img * 2 + k] = inner ? a.st.img_s[img * 2 + k] : 0.f;
+    }
+  }
+  if (threadIdx.x == 0) {
+    a.st.head[0] = (uint32_t)step;
+    a.st.head[1] = (uint32_t)(step >> 32);
+    a.st.head[3] = 0u;
+  }
+}
+
+struct NebAtomArgs {
+  NebGeom g;
+  int64_t N;
+  float* pos;
+  float* vel;
+  const float* forces;  // OPEN: the kept F_neb
+  float* forces_keep;
+  const uint8_t* fixed;
+  const int* counts;  // the graph's counters, or NULL
+  NebState st;
+};
+
+// one thread per row.  ACCEPT (after k_neb_control): keep F_neb of the evaluation, or, when it overflowed, go back to the state the
+// last move saved.  MOVE: save x and v, then the update with the band's coefficients (ACCEPT: on the F_neb just made, else on `forces`).
+template <bool ACCEPT, bool MOVE>
+__global__ __launch_bounds__(kNebThreads) void k_neb_atoms(NebAtomArgs a) {
+  const int64_t r = (int64_t)blockIdx.x * kNebThreads + threadIdx.x;
+  if (r >= a.N) return;
+  const uint32_t status = a.st.head[2], fresh = a.st.head[3];
+  if (status) {
+    if (ACCEPT && status == 1u && !fresh && a.counts && a.counts[2]) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        a.pos[r * 3 + d] = a.st.x_keep[r * 3 + d];
+        a.vel[r * 3 + d] = a.st.v_keep[r * 3 + d];
+      }
+    }
+    return;
+  }
+  if (fresh) return;  // (OPEN straight after a reset: there are no coefficients yet)
+  float x[3], v[3], f[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) f[d] = ACCEPT ? a.st.f_neb[r * 3 + d] : a.forces[r * 3 + d];
+  if (ACCEPT && a.forces_keep)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) a.forces_keep[r * 3 + d] = f[d];
+  if (MOVE) {
+    const int img = (int)(r / a.g.n), atom = (int)(r - (int64_t)img * a.g.n);
+    const int b = img / a.g.M, i = img - b * a.g.M;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      x[d] = a.pos[r * 3 + d];
+      v[d] = a.vel[r * 3 + d];
+      a.st.x_keep[r * 3 + d] = x[d];
+      a.st.v_keep[r * 3 + d] = v[d];
+    }
+    if (i == 0 || i == a.g.M - 1 || a.st.conv[b] >= 0 || (a.fixed && a.fixed[atom])) {  // a branch: x keeps its bits
+#pragma unroll
+      for (int d = 0; d < 3; ++d) a.vel[r * 3 + d] = 0.f;
+      return;
+    }
+    tn_min::atom_move(x, v, f, a.st.coef[b * 3 + 0], a.st.coef[b * 3 + 1], a.st.coef[b * 3 + 2]);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      a.pos[r * 3 + d] = x[d];
+      a.vel[r * 3 + d] = v[d];
+    }
+  }
+}
+
+__global__ void k_neb_reset(NebState st, uint64_t step0, double dt0, double alpha0, uint32_t climb) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    st.head[0] = (uint32_t)step0;
+    st.head[1] = (uint32_t)(step0 >> 32);
+    st.head[2] = 0u;
+    st.head[3] = 1u;
+    st.head[kNebClimbWord] = climb;
+    st.head[kNebCauseWord] = 0u;
+    st.start[0] = dt0;
+    st.start[1] = alpha0;
+  }
+}
+
+bool neb_shape_ok(int64_t n, int64_t M, int64_t G) {
+  if (n < 0 || M < 3 || G < 1 || M > INT32_MAX / 16 || G > INT32_MAX / 16) return false;
+  if (G * M > INT32_MAX / 16) return false;
+  return n == 0 || G * M <= (INT32_MAX / 4) / n;
+}
+
+}  // namespace
+
+}  // namespace tn
+
+using namespace tn;
+
+extern "C" {
+
+int tmdnet_neb_workspace_bytes(int64_t n_atoms_per_image, int64_t n_images, int64_t n_bands, size_t* bytes) {
+  if (!bytes || !neb_shape_ok(n_atoms_per_image, n_images, n_bands)) return TMDNET_ERR_INVALID;
+  *bytes = neb_bytes(n_atoms_per_image, n_images, n_bands);
+  return TMDNET_OK;
+}
+
+int tmdnet_neb_reset(void* stream, void* neb_ws, uint64_t step0, double dt0, double alpha0, int32_t climb) {
+  if (!neb_ws || !(dt0 > 0.0) || !(alpha0 >= 0.0) || (climb != 0 && climb != 1)) return TMDNET_ERR_INVALID;
+  hipLaunchKernelGGL(k_neb_reset, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), carve_neb(neb_ws, 0, 0, 0), step0, dt0,
+                     alpha0, (uint32_t)climb);
+  return hipGetLastError() == hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
+}
+
+int tmdnet_neb_advance(tmdnet_model* m, void* stream, void* graph_ws, void* neb_ws, int64_t n_atoms_per_image, int64_t n_images,
+                       int64_t n_bands, int32_t phase, float* pos, float* vel, const float* forces, const float* energy,
+                       const uint8_t* fixed, float* forces_keep, double dt_max, int32_t n_min, double f_inc, double f_dec, double alpha0,
+                       double f_alpha, double max_step, double fmax, double spring_k, float* epot_log_row, float* fmax_log_row,
+                       double* sums_log_row, float* coef_log_row, double* dt_log_row, double* alpha_log_row,
+                       int64_t* converged_log_row, double* path_sums_log_row, double* weights_log_row, float* tangent_coef_log_row,
+                       int32_t* climber_log_row) {
+  if (!neb_ws || !pos || !vel || !forces || !neb_shape_ok(n_atoms_per_image, n_images, n_bands)) return TMDNET_ERR_INVALID;
+  if (phase != TMDNET_MIN_OPEN && phase != TMDNET_MIN_MIDDLE && phase != TMDNET_MIN_CLOSE) return TMDNET_ERR_INVALID;
+  if (phase != TMDNET_MIN_OPEN && !energy) return TMDNET_ERR_INVALID;  // the tangents need the energies
+  if (graph_ws && !m) return TMDNET_ERR_INVALID;
+  if (!(fmax > 0.0) || !(dt_max > 0.0) || !(max_step > 0.0) || !(f_inc > 0.0) || !(f_dec > 0.0) || !(f_alpha > 0.0) || !(alpha0 >= 0.0) ||
+      n_min < 0 || !(spring_k > 0.0) || !std::isfinite(spring_k))
+    return TMDNET_ERR_INVALID;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  NebGeom g;
+  g.n = (int)n_atoms_per_image;
+  g.M = (int)n_images;
+  g.G = (int)n_bands;
+  g.S = neb_slices(n_atoms_per_image);
+  const int64_t n_img = n_images * n_bands, N = n_img * n_atoms_per_image;
+  const NebState st = carve_neb(neb_ws, n_atoms_per_image, n_images, n_bands);
+  const int* counts = nullptr;
+  if (graph_ws) counts = carve_graph(graph_ws, N, n_img, (int64_t)m->hp.max_num_neighbors * N, nullptr).counts;
+  const dim3 block(kNebThreads);
+  if (phase != TMDNET_MIN_OPEN) {
+    const dim3 grid((unsigned)n_img, (unsigned)g.S);
+    hipLaunchKernelGGL(k_neb_path, grid, block, 0, s, st, g, counts, pos, forces, fixed);
+    hipLaunchKernelGGL(k_neb_project, grid, block, 0, s, st, g, counts, pos, vel, forces, energy, fixed, spring_k);
+    NebCtlArgs c;
+    c.g = g;
+    c.p.dt_max = dt_max;
+    c.p.f_inc = f_inc;
+    c.p.f_dec = f_dec;
+    c.p.alpha0 = alpha0;
+    c.p.f_alpha = f_alpha;
+    c.p.max_step = max_step;
+    c.p.fmax = fmax;
+    c.p.n_min = n_min;
+    c.counts = counts;
+    c.energy = energy;
+    c.epot_row = epot_log_row;
+    c.fmax_row = fmax_log_row;
+    c.sums_row = sums_log_row;
+    c.coef_row = coef_log_row;
+    c.dt_row = dt_log_row;
+    c.alpha_row = alpha_log_row;
+    c.conv_row = converged_log_row;
+    c.path_row = path_sums_log_row;
+    c.weights_row = weights_log_row;
+    c.tcoef_row = tangent_coef_log_row;
+    c.climber_row = climber_log_row;
+    c.st = st;
+    hipLaunchKernelGGL(k_neb_control, dim3(1), block, 0, s, c);
+  }
+  if (N > 0) {
+    NebAtomArgs a;
+    a.g = g;
+    a.N = N;
+    a.pos = pos;
+    a.vel = vel;
+    a.forces = forces;
+    a.forces_keep = forces_keep;
+    a.fixed = fixed;
+    a.counts = counts;
+    a.st = st;
+    const dim3 grid((unsigned)((N + kNebThreads - 1) / kNebThreads));
+    if (phase == TMDNET_MIN_OPEN)
+      hipLaunchKernelGGL((k_neb_atoms<false, true>), grid, block, 0, s, a);
+    else if (phase == TMDNET_MIN_MIDDLE)
+      hipLaunchKernelGGL((k_neb_atoms<true, true>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((k_neb_atoms<true, false>), grid, block, 0, s, a);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_neb_advance: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
+  return TMDNET_OK;
+}
+
+int tmdnet_neb_status(void* stream, void* neb_ws, uint64_t host[3]) {
+  if (!neb_ws || !host) return TMDNET_ERR_INVALID;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  uint32_t head[kNebHeadWords] = {0, 0, 0, 0, 0, 0};
+  if (hipMemcpyAsync(head, carve_neb(neb_ws, 0, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
+  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
+  host[0] = (uint64_t)head[0] | ((uint64_t)head[1] << 32);
+  host[1] = head[2];
+  host[2] = head[2] == 2 ? head[kNebCauseWord] : 0;
+  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
+}
+
+}  // extern "C"

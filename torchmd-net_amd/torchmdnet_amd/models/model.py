@@ -1548,6 +1548,68 @@ class TorchMD_Net(nn.Module):
             return DeviceMinimizer(self, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, fire, fixed, warmup)
         return DeviceMinimizer(self, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, fire, fixed, warmup, cell)
 
+    def capture_neb(self, z: Tensor, images: Tensor, box: Optional[Tensor] = None, q: Optional[Tensor] = None,
+                    steps_per_replay: int = 10, fmax: float = 0.05, spring: float = 0.1, climb: bool = False,
+                    fire: Optional[dict] = None, fixed: Optional[Tensor] = None, warmup: int = 3):
+        """Capture ``steps_per_replay`` steps of a nudged-elastic-band path optimisation into ONE HIP graph (needs
+        ``static_shapes=True``): a minimum-energy path between two minima and, with ``climb=True``, its saddle point.  ``z`` [n];
+        ``images`` [M,n,3] (one band) or [G,M,n,3] (G bands), M >= 3, an unwrapped path whose first and last image never move
+        (``torchmdnet_amd.neb.interpolate`` makes a linear one).  The G M images are evaluated as one batch; per step the per-atom
+        update, neighbour list + energies + forces, the improved tangent of every interior image, the band force F_neb =
+        F - (F.t)t + spring (|d+| - |d-|) t (the climber: F - 2 (F.t)t) and FIRE with one controller per band, all as HIP kernels
+        between the evaluations (``tmdnet_neb_advance``) - no host work between steps.  A band stops moving at the step where its
+        largest atomic |F_neb| falls below ``fmax``.  ``spring`` in E / length^2; ``fire`` as for ``capture_minimize``; ``fixed`` [n]
+        marks atoms that never move in any image; a [3,3] ``box`` is shared by all images; ``q``, if given, is one value per band.
+        Works for every architecture ``capture_minimize`` serves.  Returns a ``torchmdnet_amd.neb.DeviceNEB``: ``neb(n)`` replays n
+        times; ``neb.images / forces`` [G,M,n,3], ``neb.epot`` [K,G,M], ``neb.fmax / climber`` [K,G], ``neb.converged_at /
+        step_size`` [G], ``neb.barrier()``, ``neb.check()``, ``neb.reset(images=None, climb=None)``, ``neb.run(max_steps,
+        check_every)``.  The same graph serves the plain and the climbing phase: ``neb.reset(climb=True)``."""
+        from torchmdnet_amd.minimize import parse_fire
+        from torchmdnet_amd.neb import DeviceNEB, parse_neb
+
+        if not getattr(self.representation_model, "static_shapes", False):
+            raise RuntimeError("capture_neb() needs a model created with static_shapes=True")
+        if self._head_kind() != _C.HEAD_SCALAR:
+            raise NotImplementedError(f"capture_neb has no HIP path with output_model {type(self.output_model).__name__}: a band "
+                                      "needs energies and their forces (scalar head)")
+        if self.parameter_gradients:
+            raise NotImplementedError("capture_neb has no HIP path with parameter_gradients=True (a training model); create the "
+                                      "model without it")
+        if int(steps_per_replay) < 1:
+            raise ValueError(f"steps_per_replay must be at least 1, got {steps_per_replay}")
+        if not float(fmax) > 0:
+            raise ValueError(f"fmax must be positive, got {fmax}")
+        parse_fire(fire)  # refused before anything is staged or captured
+        parse_neb(dict(spring=spring, climb=climb))
+        if z.dim() != 1:
+            raise ValueError(f"z must be [n], the atoms of ONE image, got {tuple(z.shape)}")
+        n = int(z.shape[0])
+        if images.dim() not in (3, 4) or tuple(images.shape[-2:]) != (n, 3):
+            raise ValueError(f"images must be [M,{n},3] or [G,M,{n},3] for {n} atoms, got {tuple(images.shape)}")
+        if images.shape[-3] < 3:
+            raise ValueError(f"a band needs at least 3 images, got {images.shape[-3]}")
+        if images.dim() == 4 and images.shape[0] < 1:
+            raise ValueError("images holds no band")
+        n_bands = 1 if images.dim() == 3 else int(images.shape[0])
+        if fixed is not None and fixed.numel() != n:
+            raise ValueError(f"fixed must have one entry per atom of an image ({n}), got {fixed.numel()}")
+        if q is not None and q.numel() != n_bands:
+            raise ValueError(f"q must have one entry per band ({n_bands}), got {q.numel()}")
+        _require_cuda(images, "capture_neb")
+        if images.dtype != torch.float32:
+            raise NotImplementedError("torchmdnet_amd computes in fp32; cast the images to float32")
+        rm = self.representation_model
+        if box is None and rm.distance.use_periodic:
+            box = rm.distance.box
+        if box is not None and box.dim() != 2:
+            raise ValueError(f"capture_neb takes one [3,3] box shared by all images, got {tuple(box.shape)}")
+        dev = images.device  # staged as in capture(): the graph records raw pointers, conversions must not be temporaries
+        z = z.detach().to(device=dev, dtype=torch.long).contiguous()
+        box = None if box is None else box.detach().to(device=dev, dtype=torch.float32).contiguous()
+        q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        images = images if images.dim() == 4 else images[None]
+        return DeviceNEB(self, z, images, box, q, steps_per_replay, fmax, spring, climb, fire, fixed, warmup)
+
     def debug_tensor(self, name: str, shape) -> Tensor:
         L = _C.lib()
         st = self._engine
