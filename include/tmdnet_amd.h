@@ -852,6 +852,65 @@ int tmdnet_neb_advance(tmdnet_model* m, void* stream, void* graph_ws, void* neb_
 /* tmdnet_min_status, and host[2] = what was unusable when status is 2: 1 a force sum, 2 the path (coincident images), 3 an energy. */
 int tmdnet_neb_status(void* stream, void* neb_ws, uint64_t host[3]);
 
+/* ---- Hessians and normal-mode preparation assembled on the device (csrc/tn_vib.hip; additive exports, the ABI revision stays 10) ----
+ * The molecules of a batch are independent, so R replicas of a batch of B molecules and N atoms, each carrying ONE coordinate of
+ * every molecule, give R Hessian columns of every molecule from one evaluation of the replicated batch: analytically, hv = H v of
+ * tmdnet_loss_param_grads with a unit seed, or as a central difference of the forces of two tmdnet_energy_forces calls on displaced
+ * copies.  These entries seed / displace the replicated batch, gather the columns into per-molecule matrices, and turn those into
+ * the mass-weighted, projected matrices whose eigenvalues are the squared angular frequencies (Wilson, Decius and Cross, Molecular
+ * Vibrations, 1955, ch. 2).  Everything is device memory; nothing is read back.
+ * Numbering: the atoms of a molecule are contiguous, `batch` [N] is non-decreasing.  free_idx [n_free] lists the atoms that are not
+ * fixed, in the caller's order; fstart [B + 1] holds the molecules' offsets into it.  Molecule b has D_b = 3 (fstart[b+1] - fstart[b])
+ * coordinates, coordinate i = component i % 3 of its free atom i / 3, and dim = D >= max_b D_b (a multiple of 3) is the padded size.
+ * Replica r of a pass that starts at column col0 carries column k = col0 + r of every molecule with k < D_b; a molecule with fewer
+ * columns is neither seeded nor displaced in that replica.  Row r N + a of a replicated buffer is atom a of replica r (its molecule
+ * index in the evaluation is r B + b); z, batch, q and the boxes are replicated by the caller. */
+#define TMDNET_VIB_SEED 0
+#define TMDNET_VIB_PLUS 1
+#define TMDNET_VIB_MINUS 2
+#define TMDNET_VIB_ANALYTIC 0
+#define TMDNET_VIB_CENTRAL 1
+#define TMDNET_VIB_PROJECT_NONE 0
+#define TMDNET_VIB_PROJECT_TRANS 1
+#define TMDNET_VIB_PROJECT_TRANS_ROT 2
+#define TMDNET_VIB_INFO 8
+/* Bytes tmdnet_vib_finish needs beyond the caller's buffers: per molecule the projection basis U [6, dim], U^T A [6, dim] and
+ * U^T A U [6, 6] in fp64.  tmdnet_vib_seed and tmdnet_vib_gather need none. */
+int tmdnet_vib_workspace_bytes(int64_t n_mol, int64_t dim, size_t* bytes);
+/* One thread per replicated atom; out [replicas n_atoms, 3].  TMDNET_VIB_SEED: the seed vector, zero except 1.0 at the component a
+ * replica carries (pos and delta are not read).  TMDNET_VIB_PLUS / MINUS: the replicated positions with that one component moved by
+ * +delta / -delta in ONE rounded fp32 addition (the rounding contract of the MD loop); every other entry keeps the caller's bits.
+ * A replica whose column is beyond every molecule's D_b (the padding of the last pass) is all zero / undisplaced. */
+int tmdnet_vib_seed(void* stream, int32_t mode, int64_t n_atoms, int64_t n_mol, int64_t replicas, int64_t col0, const float* pos,
+                    const int64_t* batch, const int64_t* free_idx, const int64_t* fstart, float delta, float* out);
+/* The columns col0 .. col0 + replicas - 1 of every molecule into the padded row-major fp32 H [n_mol, dim, dim], which the caller zeroes
+ * once before the first pass:
+ *   TMDNET_VIB_ANALYTIC   H[b][i, k] = hv[r N + atom(b, i / 3)][i % 3]         (hv_or_f_plus = hv of the pass; the other three NULL)
+ *   TMDNET_VIB_CENTRAL    H[b][i, k] = - (F+ - F-) / den, den = x+ - x- of the moved coordinate read from the two displaced position
+ *                         buffers (the actual difference of the rounded positions, NOT 2 delta); difference and quotient in fp64,
+ *                         rounded to fp32 once.  hv_or_f_plus / f_minus = the forces at pos_plus / pos_minus.
+ * One thread per (replica, free coordinate).  Every (b, i, k) with i, k < D_b is written exactly once over the passes col0 = 0, R,
+ * 2 R, ...; nothing outside those entries is written; no atomics.  replicas <= 65535. */
+int tmdnet_vib_gather(void* stream, int32_t mode, int64_t n_atoms, int64_t n_mol, int64_t n_free, int64_t dim, int64_t replicas,
+                      int64_t col0, const int64_t* batch, const int64_t* free_idx, const int64_t* fstart, const float* hv_or_f_plus,
+                      const float* f_minus, const float* pos_plus, const float* pos_minus, float* H);
+/* One block per molecule, fp64 throughout, every entry computed by one thread in a fixed order, no floating-point atomics: repeats
+ * are bit-identical.  Writes A [n_mol, dim, dim] (fp64, zero in its padding) and info [n_mol, TMDNET_VIB_INFO] (fp64):
+ *   info[0] hmax = max |H_ij|;  info[1] asym = max |H_ij - H_ji|;  info[2] drift = max_{i, beta} | sum_j H[i, 3 j + beta] |, the
+ *     acoustic sum (meaningful only when no atom of the molecule is fixed);  info[3] the rank of the projection;  info[4] its mode;
+ *     info[5] D_b;  info[6..7] zero
+ *   S = (H + H^T) / 2;   A_ij = S_ij / sqrt(m_i m_j), masses [n_atoms] fp32 widened
+ *   projection, per molecule: mode 0 (none) when mol_atoms [n_mol] (the molecules' atom counts, or NULL: no atom is fixed) says an
+ *     atom of the molecule is fixed, else `project`: TMDNET_VIB_PROJECT_NONE, _TRANS (translations: a periodic system) or _TRANS_ROT.
+ *     Candidates in mass-weighted coordinates, t_alpha[3 j + beta] = sqrt(m_j) delta_alpha,beta and r_alpha[3 j ..] = sqrt(m_j) (e_alpha x
+ *     (x_j - c)), c the centre of mass from the fp32 positions widened, orthonormalised in the order t_x t_y t_z r_x r_y r_z by
+ *     modified Gram-Schmidt applied twice; a candidate is kept when |w|^2 > 1e-12 |w0|^2 (rank 6 in general, 5 for a linear
+ *     molecule, 3 for one atom).  With U the kept vectors:  A <- A - U (U^T A) - (U^T A)^T U^T + U (U^T A U) U^T.
+ * info[3] = -1 and nothing else written: fstart does not fit dim. */
+int tmdnet_vib_finish(void* stream, void* vib_ws, size_t ws_bytes, int64_t n_atoms, int64_t n_mol, int64_t dim, int32_t project,
+                      const float* H, const float* pos, const float* masses, const int64_t* free_idx, const int64_t* fstart,
+                      const int64_t* mol_atoms, double* A, double* info);
+
 #ifdef __cplusplus
 }
 #endif

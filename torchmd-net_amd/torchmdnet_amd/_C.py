@@ -77,6 +77,11 @@ GEMM_ACT_SILU, GEMM_MUL_AUX, GEMM_MUL_DSILU_AUX, GEMM_ACCUM, GEMM_ROWSCALE = 1, 
 # prologues and epilogues of tmdnet_debug_tlin9
 TL9_PRO_PLAIN, TL9_PRO_NORM, TL9_PRO_UPDBWD = 0, 1, 2
 TL9_EPI_PLAIN, TL9_EPI_MULGATE, TL9_EPI_UPDATE, TL9_EPI_NORMBWD, TL9_EPI_NORMBWD_GATE, TL9_EPI_EMBBWD = range(6)
+# modes of tmdnet_vib_seed / tmdnet_vib_gather / tmdnet_vib_finish (TMDNET_VIB_* in the header)
+VIB_SEED, VIB_PLUS, VIB_MINUS = range(3)
+VIB_ANALYTIC, VIB_CENTRAL = range(2)
+VIB_PROJECT_NONE, VIB_PROJECT_TRANS, VIB_PROJECT_TRANS_ROT = range(3)
+VIB_INFO = 8
 
 _lib = None
 
@@ -179,6 +184,10 @@ def lib():
     L.tmdnet_neb_advance.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, f64, i32, f64, f64, f64, f64, f64, f64,
                                      f64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tmdnet_neb_status.argtypes = [vp, vp, C.POINTER(u64)]
+    L.tmdnet_vib_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
+    L.tmdnet_vib_seed.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, vp, vp, f32, vp]
+    L.tmdnet_vib_gather.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tmdnet_vib_finish.argtypes = [vp, vp, sz, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in declared_symbols():
         fn = getattr(L, name)
         if fn.restype is C.c_int:

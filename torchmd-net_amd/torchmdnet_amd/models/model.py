@@ -1610,6 +1610,37 @@ class TorchMD_Net(nn.Module):
         images = images if images.dim() == 4 else images[None]
         return DeviceNEB(self, z, images, box, q, steps_per_replay, fmax, spring, climb, fire, fixed, warmup)
 
+    def hessian(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None, q: Optional[Tensor] = None,
+                method: str = "analytic", delta: float = 0.01, fixed: Optional[Tensor] = None, replicas: Optional[int] = None,
+                max_workspace_bytes: int = 8 << 30, atom_weights=None):
+        """The Hessian d^2 E_b / d x d x of every molecule of a batch, assembled on the device: ``(H, info)`` with ``H`` [B,D,D] fp32
+        (padded, row-major; molecule b fills its leading D_b = 3 nfree_b rows and columns, coordinate i = component i % 3 of its free
+        atom i / 3) and ``info`` a dict (``dims``, ``replicas``, ``passes``, ``engine_calls``, ``graph_builds``, ``free_idx``,
+        ``fstart``, ...).  R replicas of the batch, each carrying one coordinate of every molecule, give R columns of every molecule
+        per pass (``tmdnet_vib_seed`` / ``tmdnet_vib_gather``).  ``method="analytic"``: one second-order pass per R columns
+        (``tmdnet_loss_param_grads`` with a unit seed; the neighbour graph of the replicated batch is built once).
+        ``method="central"``: two ``energy_and_forces`` evaluations per R columns at ``pos +- delta``; the quotient divides by the
+        actual difference of the rounded positions.  ``batch`` must be non-decreasing; ``fixed`` [N] removes atoms from the Hessian
+        (a partial Hessian); ``replicas=None`` picks the largest R <= D whose workspace fits ``max_workspace_bytes``.  ``atom_weights``
+        is served by the central route only.  Works for TensorNet, the Equivariant Transformer and TensorNet2 with the scalar head."""
+        from torchmdnet_amd.vibrations import compute_hessian
+
+        return compute_hessian(self, z, pos, batch, box, q, method, delta, fixed, replicas, max_workspace_bytes, atom_weights)
+
+    def vibrations(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None, q: Optional[Tensor] = None,
+                   masses: Optional[Tensor] = None, project: bool = True, force_scale: float = 9.648533e-3, **hessian_kw):
+        """Normal-mode analysis at ``pos``: ``hessian(...)``, then on the device and in fp64 the symmetrisation, the mass weighting and
+        the projection of translations and rotations (``tmdnet_vib_finish``: translations only with a box, nothing for a molecule
+        with a fixed atom or with ``project=False``), then ``torch.linalg.eigh`` per molecule on the host.  ``masses`` [N] (default:
+        ``torchmdnet_amd.atomic_masses.atomic_masses[z]``); ``force_scale`` converts E / (length^2 mass) into the squared angular
+        frequency of ``omega2`` (default: eV, Angstrom, amu -> fs^-2); ``hessian_kw``: ``method``, ``delta``, ``fixed``,
+        ``replicas``, ``max_workspace_bytes``.  Returns a ``torchmdnet_amd.vibrations.Vibrations``: ``eigenvalues``, ``modes``,
+        ``omega2``, ``wavenumbers()``, ``n_negative()``, ``zero_point_energy()``, ``n_projected``, ``asymmetry``, ``drift``,
+        ``hmax``, ``hessian``."""
+        from torchmdnet_amd.vibrations import compute_vibrations
+
+        return compute_vibrations(self, z, pos, batch, box, q, masses, project, force_scale, **hessian_kw)
+
     def debug_tensor(self, name: str, shape) -> Tensor:
         L = _C.lib()
         st = self._engine
