@@ -626,6 +626,47 @@ int tmdnet_md_barostat(tmdnet_model* m, void* stream, void* graph_ws, void* md_w
                        double compressibility, double tau, double force_scale, uint64_t seed, float* volume_log_row,
                        float* pressure_log_row, float* scale_log_row);
 
+/* ---- Temperature replica exchange of the device-resident MD loop (csrc/tn_remd.hip; additive exports, the ABI revision stays 10) -
+ * Parallel tempering inside the captured graph.  n_mol = G * ladder replicas of ONE system (n = n_atoms / n_mol atoms each, replica
+ * b owns atoms b n .. b n + n - 1 in the caller's order): G independent ladders of R = ladder temperature slots, replica
+ * b = g R + r starts in slot r.  Replicas swap TEMPERATURES, not coordinates, so nothing of size n_atoms moves: `slot[b]` (int32)
+ * is the slot replica b holds and `holder[g][s]` (int32, 0..R-1 within the ladder) its inverse, both permutations at all times.
+ * The ladder need not be monotonic; neighbours are neighbours in the given order.
+ * When: a captured step that ends with an attempt is
+ *     evaluation;  tmdnet_md_advance(TMDNET_MD_CLOSE);  tmdnet_md_exchange;  tmdnet_md_advance(TMDNET_MD_OPEN, forces = forces_keep)
+ * in place of TMDNET_MD_MIDDLE - by the rounding contract CLOSE then OPEN is bit-identical to MIDDLE, so the steps themselves do not
+ * change.  The CLOSE reduction has advanced the step counter, which therefore reads n, the number of completed steps.
+ * Which pairs: attempt a = n / exchange_every (integer division) tries the slot pairs (s, s + 1) for s = (a & 1), (a & 1) + 2, ...
+ * while s + 1 < R.
+ * Decision, per pair, with i = holder[g][s], j = holder[g][s + 1] and E = epot_row, in fp64 in the order written:
+ *     D = (beta[s] - beta[s + 1]) * ((double)E_i - (double)E_j)          accept iff D >= 0 || (double)u < exp(D)
+ * A NaN on the way makes both comparisons false: a rejection, never a status.
+ * Noise: u = ((word 0 >> 8) + 0.5) 2^-24 of one Philox4x32-10 call, key = `seed`, counter = (n low, n high, g (R - 1) + s, 2);
+ * counter word 3 keeps the stream apart from the atoms' (0) and the barostat's (1).
+ * On acceptance: slot[i] <-> slot[j], holder updated; every velocity component of the atoms of i is multiplied by scale_up[s] =
+ * fp32(sqrt(kT[s + 1] / kT[s])) and of j by scale_down[s] = fp32(sqrt(kT[s] / kT[s + 1])) (the caller computes both in fp64 and
+ * rounds once; each scaling is ONE rounded fp32 product), and sigma[b n + a] <- sigma_table[new slot][a], the caller's table of
+ * fp32(sqrt(kT[s] force_scale / m_a)).  An atom of infinite mass has sigma_table = 0 and its zero velocity keeps its bits.
+ * Frozen state: when the status word is set, or the evaluation of this step overflowed (graph_ws), the exchange writes nothing - no
+ * slot, no velocity, no sigma, no log row and no counter.
+ * Enqueues two launches: one lane per slot of every ladder (the lane of a tried pair's lower slot decides and keeps the books),
+ * then one thread per atom (velocities and sigma).  No atomics: the result is a function of (seed, n, energies).
+ *   m, graph_ws   as in tmdnet_md_barostat.  graph_ws == NULL (m may be NULL): no overflow test.
+ *   ex_ws         tmdnet_md_exchange_workspace_bytes(n_mol, ladder) bytes of scratch: one accept flag per pair.
+ *   vel [n_atoms, 3], sigma [n_atoms]   updated in place;   epot_row [n_mol]   the epot_log_row of the CLOSE launch.
+ *   beta [ladder] double = 1 / kT;  sigma_table [ladder, n];  scale_up, scale_down [ladder - 1].
+ *   slot [n_mol], holder [G, ladder]   int32, updated in place.
+ *   slot_log_row [n_mol] int32 or NULL: slot of every replica after the attempt.   accept_log_row [G, ladder - 1] uint8 or NULL:
+ *                 1 for an accepted pair, 0 for a rejected one and for the pairs not tried in this parity.
+ *   counters      [2, G, ladder - 1] int64 or NULL: attempts, then accepts, cumulative (plain adds by the pair's one lane).
+ * TMDNET_ERR_INVALID: ladder < 2, n_mol % ladder != 0, n_atoms % n_mol != 0, exchange_every < 1, or a NULL md_ws / ex_ws / vel /
+ * sigma / epot_row / beta / sigma_table / scale_up / scale_down / slot / holder. */
+int tmdnet_md_exchange_workspace_bytes(int64_t n_mol, int32_t ladder, size_t* bytes);
+int tmdnet_md_exchange(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, void* ex_ws, int64_t n_atoms, int64_t n_mol,
+                       int32_t ladder, int64_t exchange_every, float* vel, float* sigma, const float* epot_row, const double* beta,
+                       const float* sigma_table, const float* scale_up, const float* scale_down, uint64_t seed, int32_t* slot,
+                       int32_t* holder, int32_t* slot_log_row, uint8_t* accept_log_row, int64_t* counters);
+
 /* ---- Distance constraints of the device-resident MD loop (csrc/tn_md_cons.hip; additive exports, the ABI revision stays 10) ------
  * Holonomic constraints |x_i - x_j| = d_c by RATTLE (Andersen, J. Comput. Phys. 52, 24, 1983) in the splitting above:
  *     B  v <- v + hk F

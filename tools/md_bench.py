@@ -36,7 +36,16 @@ A block is ``--block-steps`` steps from the same start (the atoms must not trave
 alternating blocks, median and min / max over ``--rounds`` blocks after one that warms up.  ``iteration`` records what SHAKE and
 RATTLE had to do at the middle step of a block - the residual before SHAKE over its bound, and the correcting sweeps per cluster,
 counted by the same Gauss-Seidel iteration in fp64 on the host from the device's state -, and ``residual_over_bound_end`` what the
-unconstrained leg's positions have become.  Writes profiles/md_constraints.json."""
+unconstrained leg's positions have become.  Writes profiles/md_constraints.json.
+
+``--remd``: temperature replica exchange, G = 8 ladders of R = 32 slots of the 64-atom molecule above (B = 256 replicas, 16 384
+atoms), Langevin, K = 100 steps per replay:
+
+  (a) ``capture_md``: the 256 replicas as plain ``capture_md`` at one temperature - the loop as it was before the exchange existed;
+  (b) ``remd_X0`` / ``remd_X10`` / ``remd_X100``: ``capture_remd`` on a geometric ladder with ``exchange_every`` = 0, 10, 100.
+
+Same alternating blocks, median and min / max; prints the acceptance matrix [G,R-1] of every leg with exchanges and records the
+ratios to (a).  Writes the key ``timing`` of profiles/md_remd.json (the other keys of that file are kept)."""
 import argparse
 import json
 import os
@@ -346,6 +355,71 @@ def constraints_main(a):
     print("wrote", out)
 
 
+def remd_main(a):
+    import torch
+
+    import __graft_entry__ as ge
+
+    ge.build_hip(verbose=False)
+    from torchmdnet_amd import md as MD
+    from torchmdnet_amd import workloads as W
+    from torchmdnet_amd.models.model import create_model
+
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)
+    dt, mass_amu, fs, friction, K, G, R, n = 1e-3, 12.0, MD.FORCE_SCALE_EV_A_AMU_FS, 0.01, 100, 8, 32, 64
+    kT = MD.geometric_ladder(0.0259, 2.0 * 0.0259, R)
+    torch.manual_seed(0)
+    model = create_model(dict(W.C2_ARGS, static_shapes=True, max_num_neighbors=64)).to(dev)
+    z, pos, _ = W.synthetic_batch(n_mol=1, n_atoms=n)
+    z, pos = z.to(dev), pos.to(dev).float().contiguous()
+    B = G * R
+    masses = torch.full((n,), mass_amu, device=dev)
+    pos_all = pos[None, None].repeat(G, R, 1, 1).contiguous()
+    vel0 = torch.zeros_like(pos_all)
+    batch = torch.repeat_interleave(torch.arange(B, device=dev), n)
+    legs, mds = {}, {}
+    mds["capture_md"] = model.capture_md(z.repeat(B), pos_all.reshape(-1, 3), vel0.reshape(-1, 3), masses.repeat(B), dt, batch=batch,
+                                         steps_per_replay=K, force_scale=fs, thermostat=dict(friction=friction, kT=float(kT[0]), seed=1))
+    for X in (0, 10, 100):
+        mds[f"remd_X{X}"] = model.capture_remd(z, pos_all, vel0, masses, dt, temperatures=kT, exchange_every=X, steps_per_replay=K,
+                                               force_scale=fs, thermostat=dict(friction=friction, seed=1))
+    for k, md in mds.items():
+        legs[k] = (md, K)
+    times = {k: [] for k in legs}
+    for _ in range(a.rounds):  # alternating blocks: every round visits every leg once
+        for k, (fn, spc) in legs.items():
+            times[k].append(_block(fn, spc, a.seconds, sync))
+    for md in mds.values():
+        md.check()  # raises if a trajectory overflowed: its timings would be of a frozen loop
+    entry = _summary(times)
+    base = entry["capture_md"]["ms_per_step"]
+    entry["ratio_over_capture_md"] = {k: entry[k]["ms_per_step"] / base for k in entry if k.startswith("remd_")}
+    entry["acceptance"] = {}
+    for X in (10, 100):
+        acc = mds[f"remd_X{X}"].acceptance()
+        entry["acceptance"][f"remd_X{X}"] = {"attempts_per_pair": int(mds[f"remd_X{X}"].attempts.max()), "mean": float(acc.mean()),
+                                             "min": float(acc.min()), "max": float(acc.max()), "matrix": acc.tolist()}
+        print(f"acceptance [G,R-1], exchange_every = {X}:")
+        for row in acc.tolist():
+            print("  " + " ".join(f"{v:.2f}" for v in row))
+    for k in legs:
+        print(f"{k:12s} {entry[k]['ms_per_step']:.4f} ms/step  (min {entry[k]['min']:.4f}, max {entry[k]['max']:.4f})", flush=True)
+    entry.update({"device": torch.cuda.get_device_name(dev), "model": "TensorNet F=128 L=2 (C2_ARGS), static_shapes", "ladders": G,
+                  "slots": R, "atoms_per_replica": n, "steps_per_replay": K, "seconds_per_block": a.seconds, "rounds": a.rounds,
+                  "kT": kT.tolist()})
+    out = a.out if a.out else os.path.join(ROOT, "profiles", "md_remd.json")
+    result = {}
+    if os.path.exists(out):
+        with open(out) as fh:
+            result = json.load(fh)
+    result["timing"] = entry
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=2.0)
@@ -353,6 +427,7 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[64, 256, 1024])
     ap.add_argument("--npt", action="store_true", help="time the constant-pressure loop instead (profiles/md_npt.json)")
     ap.add_argument("--constraints", action="store_true", help="time the constrained loop instead (profiles/md_constraints.json)")
+    ap.add_argument("--remd", action="store_true", help="time temperature replica exchange instead (key 'timing' of profiles/md_remd.json)")
     ap.add_argument("--block-steps", type=int, default=100, help="--constraints: steps of one timed block (a multiple of 10)")
     ap.add_argument("--out", default=None, help="default: profiles/md_loop.json, with --npt profiles/md_npt.json, with --constraints "
                                                 "profiles/md_constraints.json")
@@ -361,6 +436,8 @@ def main():
         return npt_main(a)
     if a.constraints:
         return constraints_main(a)
+    if a.remd:
+        return remd_main(a)
     a.out = a.out or os.path.join(ROOT, "profiles", "md_loop.json")
 
     import torch

@@ -7,7 +7,8 @@ move per molecule (``tmdnet_md_barostat``): box, positions and velocities are sc
 rounding contract and the noise generator are documented with the C entries in include/tmdnet_amd.h and in DESIGN.md section 13.
 With ``constraints=`` (``TorchMD_Net.capture_md_constrained``) the integrator launches are those of csrc/tn_md_cons.hip
 (``tmdnet_md_advance_constrained``): SHAKE after the drift and RATTLE after the closing kick, one group of lanes per cluster of
-coupled constraints, still one launch between two evaluations."""
+coupled constraints, still one launch between two evaluations.  ``TorchMD_Net.capture_remd`` (``DeviceREMD``) runs G ladders of R
+replicas of one system and exchanges their temperatures inside the graph (csrc/tn_remd.hip, ``tmdnet_md_exchange``)."""
 import ctypes as C
 import math
 from typing import Optional
@@ -263,7 +264,7 @@ class DeviceMD:
             self.c1 = math.exp(-float(self.thermostat["friction"]) * self.dt)
             self.c2 = math.sqrt(1.0 - self.c1 * self.c1)
             self.seed = int(self.thermostat.get("seed", 0)) & (2 ** 64 - 1)
-            self.sigma = torch.sqrt(float(self.thermostat["kT"]) * self.force_scale / m64).to(torch.float32).contiguous()
+            self.sigma = self._stage_sigma(m64)
         self.epot = torch.zeros((K, n_mol), dtype=torch.float32, device=dev)
         self.ekin = torch.zeros((K, n_mol), dtype=torch.float32, device=dev)
         self.barostat = None if barostat is None else parse_barostat(barostat, self.thermostat)
@@ -303,12 +304,20 @@ class DeviceMD:
                 for k in range(K):
                     out = self._evaluate()
                     self._step_outputs.append(out)
-                    if self.barostat is None:
-                        self._advance(MD_MIDDLE if k + 1 < K else MD_CLOSE, out[1], out[0], k)
-                    else:  # the kinetic energy of the closing half is reduced before the move: CLOSE, then scale (and open)
-                        self._advance(MD_CLOSE, out[1], out[0], k)
-                        self._barostat_move(k + 1 < K, out[1], out[2], k)
+                    self._capture_step(k, K, out)
         self._engine, self._generation = model._engine, model._engine.generation
+
+    def _stage_sigma(self, m64):
+        """[N] fp32 thermal velocities sqrt(kT force_scale / m) the O step reads, from fp64, rounded once"""
+        return torch.sqrt(float(self.thermostat["kT"]) * self.force_scale / m64).to(torch.float32).contiguous()
+
+    def _capture_step(self, k, K, out):
+        """The launches that follow evaluation k of a replay (inside the capture): close step k, open step k + 1"""
+        if self.barostat is None:
+            self._advance(MD_MIDDLE if k + 1 < K else MD_CLOSE, out[1], out[0], k)
+        else:  # the kinetic energy of the closing half is reduced before the move: CLOSE, then scale (and open)
+            self._advance(MD_CLOSE, out[1], out[0], k)
+            self._barostat_move(k + 1 < K, out[1], out[2], k)
 
     @property
     def ndof(self) -> Tensor:
@@ -442,3 +451,118 @@ class DeviceMD:
         if self.constraints is not None:
             self.check()
         return self
+
+
+def geometric_ladder(kT_min, kT_max, R):
+    """R temperatures kT_min (kT_max / kT_min)^(i / (R - 1)), i = 0..R-1: equal ratios between neighbours, which gives equal
+    acceptance along the ladder when the heat capacity does not depend on the temperature.  -> [R] float64 (host)"""
+    R = int(R)
+    if R < 2 or not kT_min > 0 or not kT_max > 0:
+        raise ValueError(f"geometric_ladder: needs R >= 2 and positive temperatures, got {kT_min}, {kT_max}, {R}")
+    i = torch.arange(R, dtype=torch.float64) / (R - 1)
+    return float(kT_min) * (float(kT_max) / float(kT_min)) ** i
+
+
+class DeviceREMD(DeviceMD):
+    """The object ``TorchMD_Net.capture_remd`` returns: ``DeviceMD`` for B = G R replicas of one system in G independent ladders of
+    R temperature slots, with a temperature-exchange attempt inside the graph after every ``exchange_every`` steps
+    (``tmdnet_md_exchange``; the scheme is documented in include/tmdnet_amd.h and DESIGN.md section 13).  Replicas swap
+    temperatures, not coordinates: row b of ``pos`` / ``vel`` stays replica b, and ``slot`` [B] int32 says which temperature it
+    has now (``holder`` [G,R] int32 is the inverse); both are the live device tensors.  ``slot_log`` [K/X,B] int32 and ``accepted``
+    [K/X,G,R-1] uint8 (pairs not tried in that parity read 0) are the logs of the last replay's attempts; ``attempts`` /
+    ``accepts`` [G,R-1] int64 count on the device since the capture or the last ``reset``.  ``temperatures`` [R] float64 (host)."""
+
+    def __init__(self, model, z, pos, vel, masses, dt, temperatures, exchange_every, n_ladders, box, q, steps_per_replay, force_scale,
+                 thermostat, warmup):
+        kT = torch.as_tensor(temperatures, dtype=torch.float64).detach().cpu().reshape(-1)
+        self.temperatures = kT
+        self.n_slots, self.n_ladders = R, G = int(kT.numel()), int(n_ladders)
+        self.exchange_every = X = int(exchange_every)
+        n1 = int(z.shape[0]) // (G * R)
+        self._m1 = masses.detach().to(device=pos.device, dtype=torch.float64).reshape(-1)[:n1]
+        batch = torch.repeat_interleave(torch.arange(G * R, device=pos.device), n1)
+        self._n_attempts = int(steps_per_replay) // X if X else 0
+        super().__init__(model, z, pos, vel, masses, dt, batch, box, q, G * R, steps_per_replay, force_scale, thermostat, warmup)
+
+    def _stage_sigma(self, m64):
+        # everything the exchange launches read, before the capture: tables per slot in fp64, rounded once
+        dev, R, G, kT = m64.device, self.n_slots, self.n_ladders, self.temperatures
+        B, n1 = G * R, self._m1.numel()
+        self.sigma_table = torch.stack([torch.sqrt(float(t) * self.force_scale / self._m1) for t in kT]).to(torch.float32).contiguous()
+        self._beta = (1.0 / kT).to(dev).contiguous()
+        self._up = torch.tensor([math.sqrt(float(kT[s + 1]) / float(kT[s])) for s in range(R - 1)], dtype=torch.float64).to(torch.float32).to(dev)
+        self._down = torch.tensor([math.sqrt(float(kT[s]) / float(kT[s + 1])) for s in range(R - 1)], dtype=torch.float64).to(torch.float32).to(dev)
+        self.slot = torch.arange(R, dtype=torch.int32, device=dev).repeat(G).contiguous()
+        self.holder = torch.arange(R, dtype=torch.int32, device=dev).repeat(G, 1).contiguous()
+        self.slot_log = torch.zeros((self._n_attempts, B), dtype=torch.int32, device=dev)
+        self.accepted = torch.zeros((self._n_attempts, G, R - 1), dtype=torch.uint8, device=dev)
+        self._counters = torch.zeros((2, G, R - 1), dtype=torch.int64, device=dev)
+        nbytes = C.c_size_t(0)
+        if _C.lib().tmdnet_md_exchange_workspace_bytes(B, R, C.byref(nbytes)) != _C.OK:
+            raise ValueError(f"capture_remd: {G} ladders of {R} slots are not a valid layout")
+        self._ex_ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
+        return self.sigma_table[self.slot.long()].reshape(-1).contiguous()
+
+    @property
+    def attempts(self) -> Tensor:
+        return self._counters[0]
+
+    @property
+    def accepts(self) -> Tensor:
+        return self._counters[1]
+
+    def acceptance(self) -> Tensor:
+        """accepts / attempts [G,R-1] float64 on the host (one read-back); NaN for a pair never tried"""
+        c = self._counters.cpu().to(torch.float64)
+        return c[1] / c[0]
+
+    def _capture_step(self, k, K, out):
+        X = self.exchange_every
+        if not X or (k + 1) % X:
+            return super()._capture_step(k, K, out)
+        # CLOSE, the exchange, OPEN: bit for bit MIDDLE (the rounding contract) around an attempt that sees the step's energies
+        self._advance(MD_CLOSE, out[1], out[0], k)
+        st = self._model._engine
+        a = (k + 1) // X - 1
+        rc = _C.lib().tmdnet_md_exchange(st.handle, _stream_ptr(self.pos.device), _ptr(st.graph_ws), _ptr(self._ws), _ptr(self._ex_ws),
+                                         self.n_atoms, self.n_mol, self.n_slots, X, _ptr(self.vel), _ptr(self.sigma), _ptr(self.epot[k]),
+                                         _ptr(self._beta), _ptr(self.sigma_table), _ptr(self._up), _ptr(self._down), self.seed,
+                                         _ptr(self.slot), _ptr(self.holder), _ptr(self.slot_log[a]), _ptr(self.accepted[a]),
+                                         _ptr(self._counters))
+        if rc != _C.OK:
+            raise RuntimeError(f"tmdnet_md_exchange: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
+        if k + 1 < K:
+            self._advance(MD_OPEN, self.forces, None, k)
+
+    def by_slot(self, t: Tensor) -> Tensor:
+        """Gather a per-replica [B,...] or per-atom [N,...] tensor into slot order [G,R,...] with the current assignment, so that
+        ``by_slot(remd.pos)[:, 0]`` is what the first temperature of every ladder holds now."""
+        B, G, R = self.n_mol, self.n_ladders, self.n_slots
+        if t.shape[0] == self.n_atoms and self.n_atoms != B:
+            t = t.reshape(B, self.n_atoms // B, *t.shape[1:])
+        elif t.shape[0] != B:
+            raise ValueError(f"by_slot: the first dimension must be {B} replicas or {self.n_atoms} atoms, got {tuple(t.shape)}")
+        idx = torch.arange(G, device=self.holder.device)[:, None] * R + self.holder.long()
+        return t[idx.to(t.device)]
+
+    def reset(self, pos: Optional[Tensor] = None, vel: Optional[Tensor] = None, step: int = 0, slots: Optional[Tensor] = None):
+        """``DeviceMD.reset`` (``pos`` / ``vel`` in any shape of B n atoms), plus ``slots`` [B] or [G,R]: the slot of every replica,
+        a permutation of 0..R-1 within each ladder (ValueError otherwise, before anything is changed); ``sigma`` is staged again
+        for it.  None keeps the current assignment.  The attempt and accept counters are cleared."""
+        G, R = self.n_ladders, self.n_slots
+        if slots is not None:
+            s = torch.as_tensor(slots).detach().cpu()
+            if s.dtype.is_floating_point or s.numel() != G * R:
+                raise ValueError(f"reset(slots=...): needs {G * R} integers, got {tuple(s.shape)} {s.dtype}")
+            s = s.reshape(G, R).to(torch.int64)
+            if not bool((s.sort(dim=1).values == torch.arange(R)).all()):
+                raise ValueError(f"reset(slots=...): every ladder's slots must be a permutation of 0..{R - 1}, got {s.tolist()}")
+        pos = None if pos is None else pos.reshape(-1, 3)
+        vel = None if vel is None else vel.reshape(-1, 3)
+        if slots is not None:
+            dev = self.slot.device
+            self.slot.copy_(s.reshape(-1).to(torch.int32).to(dev))
+            self.holder.copy_(s.argsort(dim=1).to(torch.int32).to(dev))
+            self.sigma.copy_(self.sigma_table[self.slot.long()].reshape(-1))
+        self._counters.zero_()
+        return super().reset(pos, vel, step)

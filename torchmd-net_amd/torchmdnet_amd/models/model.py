@@ -1473,6 +1473,87 @@ class TorchMD_Net(nn.Module):
         return DeviceMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
                         barostat, constraints)
 
+    def capture_remd(self, z: Tensor, pos: Tensor, vel: Optional[Tensor], masses: Tensor, dt: float, temperatures=None,
+                     exchange_every: int = 100, box: Optional[Tensor] = None, q: Optional[Tensor] = None, steps_per_replay: int = 100,
+                     force_scale: float = 1.0, thermostat: Optional[dict] = None, warmup: int = 3, atom_weights=None,
+                     halo_exchange=None, barostat=None, constraints=None):
+        """Temperature replica exchange (parallel tempering) inside the captured MD graph: ``capture_md`` for B = G R replicas of ONE
+        system - ``z`` [n], ``masses`` [n], ``pos`` [R,n,3] (one ladder) or [G,R,n,3] (G independent ladders), ``vel`` the same shape
+        or None (Maxwell-Boltzmann velocities at each slot's kT, drawn on the host from the thermostat's seed) - where replica
+        b = g R + r starts at ``temperatures[r]`` ([R] kT, in the unit of the energies; ``md.geometric_ladder``) and, after every
+        ``exchange_every`` steps, neighbouring slots try to swap their TEMPERATURES by the Metropolis rule on the step's potential
+        energies (``tmdnet_md_exchange``: two small launches between the closing and the opening half of the step; positions never
+        move between replicas).  ``steps_per_replay`` must be a multiple of ``exchange_every``; ``exchange_every=0`` captures plain
+        multi-temperature MD with no exchange launches.  ``thermostat=dict(friction=, seed=)`` is required (kT comes from
+        ``temperatures``).  ``box`` [3,3] is shared, ``q`` holds one entry per ladder.  Every architecture ``capture_md`` serves;
+        ``barostat``, ``constraints``, ``atom_weights`` and ``halo_exchange`` are refused.  Returns a ``torchmdnet_amd.md.DeviceREMD``:
+        ``DeviceMD``'s surface plus ``slot`` [B], ``holder`` [G,R], ``slot_log`` [K/X,B], ``accepted`` [K/X,G,R-1], ``attempts`` /
+        ``accepts`` [G,R-1], ``acceptance()``, ``temperatures``, ``by_slot(t)`` and ``reset(pos, vel, step, slots)``."""
+        from torchmdnet_amd.md import DeviceREMD
+
+        for name, val in (("barostat", barostat), ("constraints", constraints), ("atom_weights", atom_weights),
+                          ("halo_exchange", halo_exchange)):
+            if val is not None:
+                raise ValueError(f"capture_remd has no path with {name}: neither the virial of the scaled state nor the constrained "
+                                 "opening half is wired into the exchange")
+        if thermostat is None:
+            raise ValueError("capture_remd needs thermostat=dict(friction=, seed=): the temperatures act through the Langevin O step")
+        if "kT" in thermostat:
+            raise ValueError("capture_remd: the thermostat takes no 'kT'; give the ladder as temperatures=[R] kT")
+        unknown = set(thermostat) - {"friction", "seed"}
+        if unknown or "friction" not in thermostat:
+            raise ValueError(f"capture_remd: thermostat=dict(friction=, seed=), got keys {sorted(thermostat)}")
+        if temperatures is None:
+            raise ValueError("capture_remd needs temperatures=[R] kT")
+        kT = torch.as_tensor(temperatures, dtype=torch.float64).detach().cpu().reshape(-1)
+        R = int(kT.numel())
+        if R < 2 or not bool((torch.isfinite(kT) & (kT > 0)).all()):
+            raise ValueError(f"capture_remd: temperatures must be at least two positive kT, got {kT.tolist()}")
+        K, X = int(steps_per_replay), int(exchange_every)
+        if K < 1 or X < 0:
+            raise ValueError(f"capture_remd: steps_per_replay must be at least 1 and exchange_every at least 0, got {K}, {X}")
+        if X and K % X:
+            raise ValueError(f"capture_remd: steps_per_replay ({K}) must be a multiple of exchange_every ({X})")
+        n = int(z.shape[0])
+        if z.dim() != 1 or pos.dim() not in (3, 4) or tuple(pos.shape[-3:]) != (R, n, 3):
+            raise ValueError(f"capture_remd: pos must be [R,n,3] = [{R},{n},3] or [G,{R},{n},3], got {tuple(pos.shape)}")
+        if vel is not None and vel.shape != pos.shape:
+            raise ValueError(f"capture_remd: vel {tuple(vel.shape)} must have the shape of pos {tuple(pos.shape)}")
+        if masses.numel() != n:
+            raise ValueError(f"capture_remd: masses must have one entry per atom of the system ({n}), got {masses.numel()}")
+        if not getattr(self.representation_model, "static_shapes", False):
+            raise RuntimeError("capture_remd() needs a model created with static_shapes=True")
+        if self._head_kind() != _C.HEAD_SCALAR:
+            raise NotImplementedError(f"capture_remd has no HIP path with output_model {type(self.output_model).__name__}: molecular "
+                                      "dynamics needs energies and their forces (scalar head)")
+        if self.parameter_gradients:
+            raise NotImplementedError("capture_remd has no HIP path with parameter_gradients=True (a training model)")
+        _require_cuda(pos, "capture_remd")
+        if pos.dtype != torch.float32:
+            raise NotImplementedError("torchmdnet_amd computes in fp32; cast positions to float32")
+        G = int(pos.shape[0]) if pos.dim() == 4 else 1
+        B, dev = G * R, pos.device
+        rm = self.representation_model
+        if box is None and rm.distance.use_periodic:
+            box = rm.distance.box
+        if box is not None:
+            if tuple(box.shape) != (3, 3):
+                raise ValueError(f"capture_remd: box must be one shared [3,3] box, got {tuple(box.shape)}")
+            box = box.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if q is not None:
+            q = q.detach().to(device=dev, dtype=torch.float32).reshape(-1)
+            if q.numel() != G:
+                raise ValueError(f"capture_remd: q must have one entry per ladder ({G}), got {q.numel()}")
+            q = torch.repeat_interleave(q, R).contiguous()
+        m_all = masses.detach().to(device=dev, dtype=torch.float64).reshape(-1).repeat(B)
+        if vel is None:  # Maxwell-Boltzmann at each slot's kT: sqrt(kT force_scale / m) per component, host generator
+            gen = torch.Generator().manual_seed(int(thermostat.get("seed", 0)) & (2 ** 63 - 1))
+            sd = torch.sqrt(kT[:, None] * float(force_scale) / masses.detach().cpu().to(torch.float64).reshape(1, n))  # [R,n]; m = inf: 0
+            vel = (torch.randn((G, R, n, 3), generator=gen, dtype=torch.float64) * sd[None, :, :, None]).to(torch.float32).to(dev)
+        z_all = z.detach().to(device=dev, dtype=torch.long).repeat(B).contiguous()
+        return DeviceREMD(self, z_all, pos.reshape(-1, 3), vel.reshape(-1, 3), m_all, dt, kT, X, G, box, q, K, force_scale,
+                          dict(thermostat), warmup)
+
     def capture_minimize(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
                          q: Optional[Tensor] = None, num_systems: Optional[int] = None, steps_per_replay: int = 10,
                          fmax: float = 0.05, fire: Optional[dict] = None, fixed: Optional[Tensor] = None, warmup: int = 3,
