@@ -584,8 +584,9 @@ int tmdnet_md_advance(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws
                       float* epot_log_row, float* ekin_log_row);
 /* host[0] = steps completed (the device counter), host[1] = status (1: an evaluation overflowed; the state is that of step
  * host[0].  2: a barostat move was unusable, see tmdnet_md_barostat; step host[0] is complete but for that move.  3: a constraint
- * cluster did not converge, see tmdnet_md_advance_constrained).  Synchronises the stream.  Returns TMDNET_ERR_OVERFLOW for status 1
- * and TMDNET_ERR_STATE for status 2 and 3. */
+ * cluster did not converge, see tmdnet_md_advance_constrained.  4: a walker's collective variable, its gradient or its bias was not
+ * finite, see tmdnet_md_bias; the state is half a step ahead of step host[0]).  Synchronises the stream.  Returns
+ * TMDNET_ERR_OVERFLOW for status 1 and TMDNET_ERR_STATE for status 2, 3 and 4. */
 int tmdnet_md_status(void* stream, void* md_ws, uint64_t host[2]);
 
 /* ---- Barostat of the device-resident MD loop (csrc/tn_md.hip; additive exports, the ABI revision stays 10) --------------------
@@ -666,6 +667,62 @@ int tmdnet_md_exchange(tmdnet_model* m, void* stream, void* graph_ws, void* md_w
                        int32_t ladder, int64_t exchange_every, float* vel, float* sigma, const float* epot_row, const double* beta,
                        const float* sigma_table, const float* scale_up, const float* scale_down, uint64_t seed, int32_t* slot,
                        int32_t* holder, int32_t* slot_log_row, uint8_t* accept_log_row, int64_t* counters);
+
+/* ---- Collective-variable restraints and metadynamics of the device-resident MD loop (csrc/tn_bias.hip; additive exports, the ABI
+ * revision stays 10) ------------------------------------------------------------------------------------------------------------
+ * Enhanced sampling inside the captured graph: ONE launch between the evaluation of a step and the integrator launch that closes
+ * it adds a bias force to the evaluation's force buffer in place, so a captured step is
+ *     evaluation;  tmdnet_md_bias(forces = the evaluation's output);  tmdnet_md_advance(TMDNET_MD_MIDDLE or _CLOSE, the same forces)
+ * The n_mol molecules are walkers.  Every walker has the same n_cv <= 8 collective variables (CVs), on atoms given relative to the
+ * first atom of its molecule (mol_start); positions are the unwrapped ones, no minimum image is applied.  In fp64 on the fp32
+ * positions (csrc/tn_bias_math.h):
+ *     kind 0  distance(i, j)       |x_i - x_j|
+ *     kind 1  angle(i, j, k)       atan2(|r1 x r2|, r1.r2) at j, radians
+ *     kind 2  torsion(i, j, k, l)  in (-pi, pi], IUPAC sign, by atan2; gradients in the Blondel-Karplus form (no 1 / sin)
+ * diff(a, b) = a - b, for a torsion wrapped into (-pi, pi].
+ * Restraints, one per CV (restraint_kind 0: none): V = 0.5 kappa D^2 with D = diff(s, center); kind 1 harmonic, 2 upper (D > 0
+ * only), 3 lower (D < 0 only); kappa and center are [n_mol, n_cv] doubles: umbrella windows are one batch.
+ * Metadynamics on n_metad_cv = 1 or 2 of the CVs (0: none): consecutive walkers form groups of walkers_per_group = W that share
+ * one list of `capacity` = H hills, V(s) = sum_h w_h exp(-sum_d diff(s_d, c_hd)^2 / (2 sigma_d^2)), no truncation and no grid.
+ * Which hills exist: n is the step counter of md_ws, which only the closing launch advances; step0 and hill_base are what
+ * tmdnet_md_bias_reset wrote.  A launch reads the slots below hill_base + ((n - step0) / pace) W (at most H).  With deposit != 0
+ * and (n + 1 - step0) % pace == 0, walker w of a group writes slot hill_base + ((n + 1 - step0) / pace - 1) W + w: its centre is
+ * the walker's s, its height h0 exp(-V(s) / (kT (bias_factor - 1))) with the V(s) this launch computed (well-tempered), or h0 when
+ * bias_factor == 0 (plain).  A slot >= H is not written.  No launch reads a slot it writes, and there is no counter to race on.
+ * deposit == 0 only evaluates (the forces of a start geometry).
+ * Force: per distinct atom of a walker the fp64 sum, in CV order and then slot order, of -dV/ds_cv * ds_cv/dx over the entries
+ * that name it, rounded to fp32 ONCE and added to forces[atom] with ONE rounded fp32 addition under the rounding contract above.
+ * Atoms in no CV keep their bits.  The reduction over the hills has a fixed order (a thread strides by 256, lanes add by the wave
+ * xor tree, waves in turn), without floating-point atomics: repeats are bit-identical.
+ * Frozen state: when the status word is set, or the evaluation of this step overflowed (graph_ws), nothing is written.  A walker
+ * whose CV, gradient, bias or force is not finite (coincident atoms, a collinear angle or torsion, a NaN position, an atom index
+ * outside the batch) leaves its forces alone, deposits nothing, writes no log row and stores status 4: the closing launch that
+ * follows then returns at once, the state stays finite and half a step ahead of the last completed step, until tmdnet_md_reset.
+ * Enqueues one launch, one block of 256 threads per walker.
+ *   bias_ws       tmdnet_md_bias_workspace_bytes(...) bytes, aligned up to 256 by the callee: a 256-byte header (uint64 step0,
+ *                 uint64 hill_base), then per group (n_metad_cv + 1) arrays of H doubles: centre 0 [, centre 1], height.
+ *   pos [n_atoms, 3] read;  forces [n_atoms, 3] updated in place.
+ *   cv_kind [n_cv], cv_atoms [n_cv, 4] (unused slots are not read), mol_start [n_mol]   int32.
+ *   n_distinct, atom_rel [n_distinct], entry_offsets [n_distinct + 1], entries [32]   int32: the distinct atoms of a walker's
+ *                 CVs (relative), and for each the entries (cv << 2 | slot) that name it, in CV order then slot order.
+ *   sigma0, sigma1, height, kT, bias_factor, pace   the metadynamics parameters (sigma1 with n_metad_cv == 2 only).
+ *   cv_log_row [n_mol, n_cv], restraint_log_row [n_mol], bias_log_row [n_mol]   double or NULL: s, the restraint energy and V(s).
+ *   force_log_row [n_mol, n_distinct, 3]   float or NULL: the fp32 bias force of every distinct atom.
+ * TMDNET_ERR_INVALID: n_cv outside 1..8, n_distinct outside 1..32, n_metad_cv outside 0..2 or above n_cv, a metad CV out of range
+ * or named twice, sigma <= 0, pace < 1, height < 0, bias_factor neither 0 nor > 1, kT <= 0 with a bias factor, W < 1,
+ * n_mol % W != 0, capacity < W, or a NULL workspace, position, force or table pointer. */
+int tmdnet_md_bias_workspace_bytes(int64_t n_mol, int32_t n_cv, int32_t n_metad_cv, int32_t walkers_per_group, int64_t capacity,
+                                   size_t* bytes);
+/* Enqueues: the header of bias_ws = (step0, hill_base).  Required once before the first tmdnet_md_bias on a workspace; the hills
+ * themselves are the caller's to fill (a restart) or to leave (slots below hill_base must hold hills). */
+int tmdnet_md_bias_reset(void* stream, void* bias_ws, uint64_t step0, uint64_t hill_base);
+int tmdnet_md_bias(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, void* bias_ws, int64_t n_atoms, int64_t n_mol,
+                   int32_t deposit, const float* pos, float* forces, int32_t n_cv, const int32_t* cv_kind, const int32_t* cv_atoms,
+                   const int32_t* mol_start, int32_t n_distinct, const int32_t* atom_rel, const int32_t* entry_offsets,
+                   const int32_t* entries, const int32_t* restraint_kind, const double* kappa, const double* center,
+                   int32_t n_metad_cv, int32_t metad_cv0, int32_t metad_cv1, double sigma0, double sigma1, double height, double kT,
+                   double bias_factor, int64_t pace, int32_t walkers_per_group, int64_t capacity, double* cv_log_row,
+                   double* restraint_log_row, double* bias_log_row, float* force_log_row);
 
 /* ---- Distance constraints of the device-resident MD loop (csrc/tn_md_cons.hip; additive exports, the ABI revision stays 10) ------
  * Holonomic constraints |x_i - x_j| = d_c by RATTLE (Andersen, J. Comput. Phys. 52, 24, 1983) in the splitting above:

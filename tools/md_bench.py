@@ -45,7 +45,20 @@ atoms), Langevin, K = 100 steps per replay:
   (b) ``remd_X0`` / ``remd_X10`` / ``remd_X100``: ``capture_remd`` on a geometric ladder with ``exchange_every`` = 0, 10, 100.
 
 Same alternating blocks, median and min / max; prints the acceptance matrix [G,R-1] of every leg with exchanges and records the
-ratios to (a).  Writes the key ``timing`` of profiles/md_remd.json (the other keys of that file are kept)."""
+ratios to (a).  Writes the key ``timing`` of profiles/md_remd.json (the other keys of that file are kept).
+
+``--bias``: collective-variable restraints and metadynamics, K = 10, NVE, on 1 x 64 and 256 x 64 atoms (the 64-atom molecule above,
+one walker and 256 walkers in groups of 4):
+
+  (a) ``capture_md``: the unbiased loop;
+  (b) ``restraints``: ``capture_md_biased`` with a distance, an angle and a torsion restrained; ``metad_0`` / ``metad_1000`` /
+      ``metad_10000``: the same plus two-dimensional metadynamics whose groups hold 0, 1 000 and 10 000 hills (loaded with
+      ``reset(hills=)``; the pace is longer than the run, so the lists stay as they are);
+  (c) ``eager_restraint`` / ``eager_metad_1000``: the loop a caller builds on ``capture()`` - one graph launch per step, velocity
+      Verlet and a distance restraint (plus 1 000 one-dimensional hills per group) as eager torch ops, nothing read back.
+
+Same alternating blocks, median and min / max; records the ratios to (a) and the slope of the cost per step in the number of hills.
+Writes the key ``timing`` of profiles/md_bias.json (the other keys of that file are kept)."""
 import argparse
 import json
 import os
@@ -420,6 +433,110 @@ def remd_main(a):
     print("wrote", out)
 
 
+def bias_main(a):
+    import torch
+
+    import __graft_entry__ as ge
+
+    ge.build_hip(verbose=False)
+    from torchmdnet_amd import md as MD
+    from torchmdnet_amd import workloads as W
+    from torchmdnet_amd.models.model import create_model
+
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)
+    dt, mass_amu, fs, K, n = 1e-3, 12.0, MD.FORCE_SCALE_EV_A_AMU_FS, 10, 64
+    cvs = [("distance", 0, 1), ("angle", 1, 2, 3), ("torsion", 2, 3, 4, 5)]
+    out = a.out if a.out else os.path.join(ROOT, "profiles", "md_bias.json")
+    result = {}
+    if os.path.exists(out):
+        with open(out) as fh:
+            result = json.load(fh)
+    timing = {"device": torch.cuda.get_device_name(dev), "model": "TensorNet F=128 L=2 (C2_ARGS), static_shapes", "steps_per_replay": K,
+              "atoms_per_walker": n, "seconds_per_block": a.seconds, "rounds": a.rounds, "cvs": [list(c) for c in cvs], "sizes": {}}
+    for B, Wg in ((1, 1), (256, 4)):
+        torch.manual_seed(0)
+        model = create_model(dict(W.C2_ARGS, static_shapes=True, max_num_neighbors=64)).to(dev)
+        z1, pos1, _ = W.synthetic_batch(n_mol=1, n_atoms=n)
+        z, pos = z1.to(dev).repeat(B), pos1.to(dev).float().repeat(B, 1).contiguous()
+        batch = torch.repeat_interleave(torch.arange(B, device=dev), n)
+        vel0 = torch.zeros_like(pos)
+        masses = torch.full((B * n,), mass_amu, device=dev)
+        G = B // Wg
+        x1 = pos1.double()
+        d0 = float((x1[0] - x1[1]).norm())
+        res = [dict(cv=0, kappa=1.0, center=d0 + 0.05), dict(cv=1, kind="upper", kappa=1.0, center=1.0), dict(cv=2, kappa=0.5, center=0.3)]
+        mds = {"capture_md": model.capture_md(z, pos, vel0, masses, dt, batch=batch, steps_per_replay=K, force_scale=fs)}
+        mds["restraints"] = model.capture_md_biased(z, pos, vel0, masses, dt, batch=batch, steps_per_replay=K, force_scale=fs,
+                                                    bias=dict(cvs=cvs, restraints=res))
+        gen = torch.Generator().manual_seed(3)
+        for nh in (0, 1000, 10000):
+            metad = dict(cvs=[2, 0], sigma=[0.3, 0.1], height=0.01, pace=10 ** 9, kT=0.0259, bias_factor=8.0, walkers_per_group=Wg,
+                         capacity=max(nh, Wg))
+            md = model.capture_md_biased(z, pos, vel0, masses, dt, batch=batch, steps_per_replay=K, force_scale=fs,
+                                         bias=dict(cvs=cvs, restraints=res, metad=metad))
+            if nh:  # hills spread over the torsion's range and around the distance: every one of them is summed (no truncation)
+                c = torch.stack([6.28 * torch.rand(G, nh, generator=gen, dtype=torch.float64) - 3.14,
+                                 d0 + 0.3 * torch.randn(G, nh, generator=gen, dtype=torch.float64)], 2)
+                md.reset(hills=(c, torch.full((G, nh), 1e-4, dtype=torch.float64)))
+                assert md.n_hills == nh
+            mds[f"metad_{nh}"] = md
+        legs = {k: (md, K) for k, md in mds.items()}
+
+        # ---- the eager alternative on capture(): a distance restraint, and 1 000 one-dimensional hills per group on the distance
+        replay = model.capture(z, pos, batch)
+        vel = vel0.clone()
+        _, forces = replay(pos)
+        ia, ib = torch.arange(B, device=dev) * n, torch.arange(B, device=dev) * n + 1
+        hk = 0.5 * dt * fs / mass_amu
+        hc = (d0 + 0.3 * torch.randn(G, 1000, generator=gen, dtype=torch.float64)).to(dev)
+        hw = torch.full((G, 1000), 1e-4, dtype=torch.float64, device=dev)
+        grp = torch.arange(B, device=dev) // Wg
+        total = forces.clone()
+
+        def eager(hills):
+            def step():
+                vel.add_(total, alpha=hk)
+                replay.pos.add_(vel, alpha=dt)
+                replay()
+                x = replay.pos
+                r = (x[ia] - x[ib]).double()
+                s = r.norm(dim=1)
+                dV = 1.0 * (s - (d0 + 0.05))
+                if hills:
+                    dl = s[:, None] - hc[grp]
+                    dV = dV - (hw[grp] * torch.exp(-0.5 * (dl / 0.1) ** 2) * dl).sum(1) / 0.01
+                f = (-(dV / s)[:, None] * r).float()
+                total.copy_(forces)
+                total.index_add_(0, ia, f)
+                total.index_add_(0, ib, -f)
+                vel.add_(total, alpha=hk)
+            return step
+
+        legs["eager_restraint"] = (eager(False), 1)
+        legs["eager_metad_1000"] = (eager(True), 1)
+        times = {k: [] for k in legs}
+        for _ in range(a.rounds):  # alternating blocks: every round visits every leg once
+            for k, (fn, spc) in legs.items():
+                times[k].append(_block(fn, spc, a.seconds, sync))
+        for md in mds.values():
+            md.check()  # raises if a trajectory froze: its timings would be of a loop that does nothing
+        entry = _summary(times)
+        base = entry["capture_md"]["ms_per_step"]
+        entry["ratio_over_capture_md"] = {k: entry[k]["ms_per_step"] / base for k in entry if k != "capture_md"}
+        entry["us_per_step_per_1000_hills"] = 1e3 * (entry["metad_10000"]["ms_per_step"] - entry["metad_0"]["ms_per_step"]) / 10.0
+        entry["walkers"], entry["walkers_per_group"] = B, Wg
+        timing["sizes"][f"{B}x{n}"] = entry
+        for k in legs:
+            print(f"{B:4d} x {n}  {k:18s} {entry[k]['ms_per_step']:.4f} ms/step  (min {entry[k]['min']:.4f}, max {entry[k]['max']:.4f})", flush=True)
+        del replay, mds, legs
+    result["timing"] = timing
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=2.0)
@@ -428,6 +545,7 @@ def main():
     ap.add_argument("--npt", action="store_true", help="time the constant-pressure loop instead (profiles/md_npt.json)")
     ap.add_argument("--constraints", action="store_true", help="time the constrained loop instead (profiles/md_constraints.json)")
     ap.add_argument("--remd", action="store_true", help="time temperature replica exchange instead (key 'timing' of profiles/md_remd.json)")
+    ap.add_argument("--bias", action="store_true", help="time restraints and metadynamics instead (key 'timing' of profiles/md_bias.json)")
     ap.add_argument("--block-steps", type=int, default=100, help="--constraints: steps of one timed block (a multiple of 10)")
     ap.add_argument("--out", default=None, help="default: profiles/md_loop.json, with --npt profiles/md_npt.json, with --constraints "
                                                 "profiles/md_constraints.json")
@@ -438,6 +556,8 @@ def main():
         return constraints_main(a)
     if a.remd:
         return remd_main(a)
+    if a.bias:
+        return bias_main(a)
     a.out = a.out or os.path.join(ROOT, "profiles", "md_loop.json")
 
     import torch

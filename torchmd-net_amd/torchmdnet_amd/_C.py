@@ -169,6 +169,10 @@ def lib():
                                      u64, vp, vp, vp]
     L.tmdnet_md_exchange_workspace_bytes.argtypes = [i64, i32, C.POINTER(sz)]
     L.tmdnet_md_exchange.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i64, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp]
+    L.tmdnet_md_bias_workspace_bytes.argtypes = [i64, i32, i32, i32, i64, C.POINTER(sz)]
+    L.tmdnet_md_bias_reset.argtypes = [vp, vp, u64, u64]
+    L.tmdnet_md_bias.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32,
+                                 f64, f64, f64, f64, f64, i64, i32, i64, vp, vp, vp, vp]
     L.tmdnet_md_constraints_workspace_bytes.argtypes = [i64, i64, i64, C.POINTER(sz)]
     L.tmdnet_md_advance_constrained.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, u64, vp, vp,
                                                 vp, vp, i64, i64, vp, vp, vp, vp, f64, i32]

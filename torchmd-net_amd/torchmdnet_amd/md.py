@@ -8,7 +8,9 @@ rounding contract and the noise generator are documented with the C entries in i
 With ``constraints=`` (``TorchMD_Net.capture_md_constrained``) the integrator launches are those of csrc/tn_md_cons.hip
 (``tmdnet_md_advance_constrained``): SHAKE after the drift and RATTLE after the closing kick, one group of lanes per cluster of
 coupled constraints, still one launch between two evaluations.  ``TorchMD_Net.capture_remd`` (``DeviceREMD``) runs G ladders of R
-replicas of one system and exchanges their temperatures inside the graph (csrc/tn_remd.hip, ``tmdnet_md_exchange``)."""
+replicas of one system and exchanges their temperatures inside the graph (csrc/tn_remd.hip, ``tmdnet_md_exchange``).
+``TorchMD_Net.capture_md_biased`` (``DeviceBiasedMD``) adds collective-variable restraints and metadynamics: one launch per step
+(csrc/tn_bias.hip, ``tmdnet_md_bias``) adds the bias force to the evaluation's forces before the integrator reads them."""
 import ctypes as C
 import math
 from typing import Optional
@@ -292,6 +294,7 @@ class DeviceMD:
                     f0 = self._evaluate()[1]
                 self.forces = f0.clone()  # forces at the initial positions: what the first OPEN launch reads
                 L.tmdnet_md_reset(_stream_ptr(dev), _ptr(self._ws), 0)
+                self._start(0)
                 if constraints is not None:  # velocities drawn from a Maxwell-Boltzmann distribution: consistent before step 1
                     self._advance(MD_PROJECT, None, None, 0)
             torch.cuda.current_stream(dev).wait_stream(side)
@@ -310,6 +313,9 @@ class DeviceMD:
     def _stage_sigma(self, m64):
         """[N] fp32 thermal velocities sqrt(kT force_scale / m) the O step reads, from fp64, rounded once"""
         return torch.sqrt(float(self.thermostat["kT"]) * self.force_scale / m64).to(torch.float32).contiguous()
+
+    def _start(self, step):
+        """What a subclass enqueues on ``forces`` and its own state after ``tmdnet_md_reset(step)``, at capture and at ``reset``"""
 
     def _capture_step(self, k, K, out):
         """The launches that follow evaluation k of a replay (inside the capture): close step k, open step k + 1"""
@@ -389,7 +395,9 @@ class DeviceMD:
         the barostat when one of its moves was unusable (zero volume, or a NaN from the virial): the state is frozen before that
         move.  Raises a RuntimeError naming the constraints when a cluster did not converge within ``max_iter`` sweeps (or met a
         value that is not finite): that cluster is back at its saved state, the whole state is frozen and finite but is not a point
-        of the trajectory - other clusters may be half a step ahead -, and ``reset(pos=, vel=)`` is required.  Returns the step
+        of the trajectory - other clusters may be half a step ahead -, and ``reset(pos=, vel=)`` is required.  Raises a RuntimeError
+        naming the bias (``DeviceBiasedMD``) when a walker's collective variable, its gradient or its bias was not finite: the state
+        is frozen, finite and half a step ahead of the last completed step, and ``reset(pos=, vel=)`` is required.  Returns the step
         counter."""
         host = (C.c_uint64 * 2)()
         dev = self.pos.device
@@ -409,6 +417,10 @@ class DeviceMD:
                                f"tol={self.constraints['tol']:g} after step {int(host[0])} (or met a value that is not finite); the MD "
                                "state is frozen and finite but is not a point of the trajectory (other clusters may be half a step "
                                "ahead): reset(pos=, vel=) is required")
+        if int(host[1]) == 4:
+            raise RuntimeError(f"bias: a collective variable, its gradient or the bias of a walker was not finite after step {int(host[0])} "
+                               "(coincident atoms, a collinear angle or torsion, or a NaN position); the MD state is frozen and finite "
+                               "but half a step ahead of that step: reset(pos=, vel=) is required")
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_md_status failed (code {rc})")
         return int(host[0])
@@ -443,6 +455,7 @@ class DeviceMD:
         self.forces.copy_(f)
         with torch.cuda.device(dev):
             _C.lib().tmdnet_md_reset(_stream_ptr(dev), _ptr(self._ws), int(step))
+            self._start(int(step))
             if self.constraints is not None:
                 self._cons_ws.zero_()
                 self._advance(MD_PROJECT, None, None, 0)
@@ -565,4 +578,283 @@ class DeviceREMD(DeviceMD):
             self.holder.copy_(s.argsort(dim=1).to(torch.int32).to(dev))
             self.sigma.copy_(self.sigma_table[self.slot.long()].reshape(-1))
         self._counters.zero_()
+        return super().reset(pos, vel, step)
+
+
+# ---- collective-variable restraints and metadynamics (csrc/tn_bias.hip) ---------------------------------------------------------------
+CV_KINDS = {"distance": (0, 2), "angle": (1, 3), "torsion": (2, 4)}  # name -> (kind of tmdnet_md_bias, number of atoms)
+RESTRAINT_KINDS = {"harmonic": 1, "upper": 2, "lower": 3}
+MAX_CVS = 8
+_BIAS_KEYS = ("cvs", "restraints", "metad", "log_forces")
+_METAD_KEYS = ("cvs", "sigma", "height", "pace", "kT", "bias_factor", "walkers_per_group", "capacity")
+
+
+def prepare_bias(bias, batch, n_atoms, n_mol):
+    """``bias=dict(cvs=, restraints=, metad=, log_forces=)`` -> everything ``DeviceBiasedMD`` needs, on the host, before anything is
+    staged: the CV tables, the table of distinct atoms and their (cv, slot) entries, kappa and the centres per walker [B,D] and the
+    metadynamics parameters.  Raises ValueError naming the cause."""
+    b = dict(bias)
+    unknown = set(b) - set(_BIAS_KEYS)
+    if unknown:
+        raise ValueError(f"bias: unknown keys {sorted(unknown)} ({', '.join(_BIAS_KEYS)})")
+    B = int(n_mol)
+    bt = torch.as_tensor(batch).detach().cpu().to(torch.int64).reshape(-1)
+    if bt.numel() != int(n_atoms):
+        raise ValueError(f"bias: batch must have one entry per atom ({n_atoms}), got {bt.numel()}")
+    if bt.numel() > 1 and bool((bt[1:] < bt[:-1]).any()):
+        raise ValueError("bias: batch must be sorted (CV atoms are given relative to each molecule's first atom)")
+    sizes = torch.bincount(bt, minlength=B)
+    if sizes.numel() != B or int(sizes.min()) < 1:
+        raise ValueError(f"bias: every one of the {B} molecules needs at least one atom, got sizes {sizes.tolist()}")
+    start = torch.cumsum(sizes, 0) - sizes
+    cvs = list(b.get("cvs") or [])
+    D = len(cvs)
+    if D < 1:
+        raise ValueError("bias: 'cvs' needs at least one collective variable")
+    if D > MAX_CVS:
+        raise ValueError(f"bias: {D} collective variables, at most {MAX_CVS} per walker")
+    kinds, atoms = [], []
+    smallest = int(sizes.min())
+    for c, cv in enumerate(cvs):
+        name, idx = cv[0], [int(i) for i in cv[1:]]
+        if name not in CV_KINDS:
+            raise ValueError(f"bias: cv {c} has kind {name!r} ({', '.join(CV_KINDS)})")
+        kind, na = CV_KINDS[name]
+        if len(idx) != na:
+            raise ValueError(f"bias: cv {c} ({name}) takes {na} atoms, got {len(idx)}")
+        for i in idx:
+            if not 0 <= i < smallest:
+                raise ValueError(f"bias: cv {c} ({name}) names atom {i}, outside its molecule (the smallest molecule has {smallest} atoms; "
+                                 "indices are relative to each molecule's first atom)")
+        if len(set(idx)) != na:
+            raise ValueError(f"bias: cv {c} ({name}) names an atom twice: {idx}")
+        kinds.append(kind)
+        atoms.append(idx + [-1] * (4 - na))
+    distinct = sorted({i for row in atoms for i in row if i >= 0})
+    offsets, entries = [0], []
+    for a in distinct:
+        entries += [(c << 2) | s for c, row in enumerate(atoms) for s, i in enumerate(row) if i == a]
+        offsets.append(len(entries))
+    res_kind = [0] * D
+    kappa, center = torch.zeros((B, D), dtype=torch.float64), torch.zeros((B, D), dtype=torch.float64)
+    for r, res in enumerate(b.get("restraints") or []):
+        res = dict(res)
+        unknown = set(res) - {"cv", "kind", "kappa", "center"}
+        if unknown or not {"cv", "kappa", "center"} <= set(res):
+            raise ValueError(f"bias: restraint {r} is dict(cv=, kind=, kappa=, center=), got keys {sorted(res)}")
+        c, kind = int(res["cv"]), res.get("kind", "harmonic")
+        if not 0 <= c < D:
+            raise ValueError(f"bias: restraint {r} names cv {c}, outside 0..{D - 1}")
+        if kind not in RESTRAINT_KINDS:
+            raise ValueError(f"bias: restraint {r} has kind {kind!r} ({', '.join(RESTRAINT_KINDS)})")
+        if res_kind[c]:
+            raise ValueError(f"bias: cv {c} has two restraints; one per collective variable")
+        res_kind[c] = RESTRAINT_KINDS[kind]
+        for name, dst in (("kappa", kappa), ("center", center)):
+            v = torch.as_tensor(res[name], dtype=torch.float64).detach().cpu().reshape(-1)
+            if v.numel() not in (1, B) or not bool(torch.isfinite(v).all()):
+                raise ValueError(f"bias: restraint {r}: {name} must be a finite scalar or [{B}] (one per walker), got {tuple(v.shape)}")
+            dst[:, c] = v
+    out = dict(D=D, kinds=torch.tensor(kinds, dtype=torch.int32), atoms=torch.tensor(atoms, dtype=torch.int32),
+               mol_start=start.to(torch.int32), distinct=torch.tensor(distinct, dtype=torch.int32),
+               offsets=torch.tensor(offsets, dtype=torch.int32),
+               entries=torch.tensor(entries + [0] * (4 * MAX_CVS - len(entries)), dtype=torch.int32), res_kind=torch.tensor(res_kind, dtype=torch.int32),
+               kappa=kappa, center=center, log_forces=bool(b.get("log_forces", False)), cvs=[tuple(cv) for cv in cvs],
+               dm=0, mcv=(0, 0), sigma=(0.0, 0.0), height=0.0, pace=1, kT=0.0, gamma=0.0, W=1, H=0)
+    metad = b.get("metad")
+    if metad is not None:
+        m = dict(metad)
+        unknown = set(m) - set(_METAD_KEYS)
+        if unknown:
+            raise ValueError(f"bias: metad has unknown keys {sorted(unknown)} ({', '.join(_METAD_KEYS)})")
+        for key in ("cvs", "sigma", "height", "pace", "kT", "capacity"):
+            if key not in m:
+                raise ValueError(f"bias: metad needs '{key}'")
+        mcv = [int(c) for c in m["cvs"]]
+        if len(mcv) not in (1, 2):
+            raise ValueError(f"bias: metadynamics acts on 1 or 2 collective variables, got {len(mcv)}")
+        if any(not 0 <= c < D for c in mcv) or len(set(mcv)) != len(mcv):
+            raise ValueError(f"bias: metad cvs {mcv} must be distinct indices into the {D} collective variables")
+        sigma = [float(s) for s in (m["sigma"] if hasattr(m["sigma"], "__len__") else [m["sigma"]])]
+        if len(sigma) != len(mcv) or not all(s > 0 and math.isfinite(s) for s in sigma):
+            raise ValueError(f"bias: metad sigma must be {len(mcv)} positive widths, got {sigma}")
+        height, pace, kT = float(m["height"]), int(m["pace"]), float(m["kT"])
+        if not height >= 0 or not math.isfinite(height):
+            raise ValueError(f"bias: metad height must not be negative, got {height}")
+        if pace < 1:
+            raise ValueError(f"bias: metad pace must be at least 1 step, got {pace}")
+        gamma = m.get("bias_factor")
+        if gamma is not None and not float(gamma) > 1:
+            raise ValueError(f"bias: metad bias_factor must exceed 1 (None: plain metadynamics), got {gamma}")
+        if gamma is not None and not kT > 0:
+            raise ValueError(f"bias: well-tempered metadynamics needs kT > 0, got {kT}")
+        W, H = int(m.get("walkers_per_group", 1)), int(m["capacity"])
+        if W < 1 or B % W:
+            raise ValueError(f"bias: the {B} walkers are no whole number of groups of walkers_per_group={W}")
+        if H < W:
+            raise ValueError(f"bias: metad capacity {H} is below walkers_per_group={W}: not one deposit fits")
+        out.update(dm=len(mcv), mcv=(mcv[0], mcv[-1]), sigma=(sigma[0], sigma[-1]), height=height, pace=pace, kT=kT,
+                   gamma=0.0 if gamma is None else float(gamma), W=W, H=H)
+    return out
+
+
+class DeviceBiasedMD(DeviceMD):
+    """The object ``TorchMD_Net.capture_md_biased`` returns: ``DeviceMD`` whose every step adds the force of collective-variable
+    restraints and / or metadynamics to the model's force inside the graph (``tmdnet_md_bias``, one launch between the evaluation and
+    the integrator launch; the scheme is documented in include/tmdnet_amd.h and DESIGN.md section 13).  The B molecules are walkers;
+    consecutive walkers form G = B / W groups that share one list of hills.  ``forces`` is the TOTAL force.  Logs of the last
+    replay's steps: ``cv`` [K,B,D], ``restraint_energy`` and ``bias_energy`` [K,B] (float64; the bias each step's force came from),
+    and with ``log_forces`` ``bias_forces`` [K,B,A,3] float32 on the atoms ``bias_atoms`` [B,A] (global indices) and
+    ``start_bias_forces`` [B,A,3], the bias force in ``forces`` at the capture or the last ``reset``."""
+
+    def __init__(self, model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup, bias):
+        self.bias = bias
+        self._step0, self._hill_base = 0, 0
+        self._bias_ready = False
+        super().__init__(model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup)
+
+    def _stage_bias(self):
+        bs, dev, K, B = self.bias, self.pos.device, self.steps_per_replay, self.n_mol
+        D, A = bs["D"], int(bs["distinct"].numel())
+        self._tab = {k: bs[k].to(dev).contiguous() for k in ("kinds", "atoms", "mol_start", "distinct", "offsets", "entries", "res_kind", "kappa", "center")}
+        self.cv = torch.zeros((K, B, D), dtype=torch.float64, device=dev)
+        self.restraint_energy = torch.zeros((K, B), dtype=torch.float64, device=dev)
+        self.bias_energy = torch.zeros((K, B), dtype=torch.float64, device=dev)
+        self.bias_forces = torch.zeros((K, B, A, 3), dtype=torch.float32, device=dev) if bs["log_forces"] else None
+        self.bias_atoms = (self._tab["mol_start"][:, None] + self._tab["distinct"][None, :]).long()
+        self.start_bias_forces = torch.zeros((B, A, 3), dtype=torch.float32, device=dev) if bs["log_forces"] else None
+        self._start_row = (torch.zeros((B, D), dtype=torch.float64, device=dev), torch.zeros(B, dtype=torch.float64, device=dev),
+                           torch.zeros(B, dtype=torch.float64, device=dev))
+        nbytes = C.c_size_t(0)
+        if _C.lib().tmdnet_md_bias_workspace_bytes(B, D, bs["dm"], bs["W"], bs["H"], C.byref(nbytes)) != _C.OK:
+            raise ValueError(f"capture_md_biased: {B} walkers, {D} cvs, walkers_per_group={bs['W']}, capacity={bs['H']} are not a valid layout")
+        self._bias_ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
+        self._bias_ready = True
+
+    @property
+    def n_groups(self) -> int:
+        return self.n_mol // self.bias["W"]
+
+    def _hill_store(self) -> Tensor:
+        """[G, dm + 1, H] float64 view of the hills in the workspace: centre 0 [, centre 1], height"""
+        bs = self.bias
+        off = (-self._bias_ws.data_ptr()) % 256 + 256
+        n = self.n_groups * (bs["dm"] + 1) * bs["H"]
+        return self._bias_ws[off:off + 8 * n].view(torch.float64).view(self.n_groups, bs["dm"] + 1, bs["H"])
+
+    def _bias_launch(self, deposit, forces, rows, force_row):
+        st, dev, bs, tb = self._model._engine, self.pos.device, self.bias, self._tab
+        rc = _C.lib().tmdnet_md_bias(
+            st.handle, _stream_ptr(dev), _ptr(st.graph_ws), _ptr(self._ws), _ptr(self._bias_ws), self.n_atoms, self.n_mol, int(deposit),
+            _ptr(self.pos), _ptr(forces), bs["D"], _ptr(tb["kinds"]), _ptr(tb["atoms"]), _ptr(tb["mol_start"]), int(tb["distinct"].numel()),
+            _ptr(tb["distinct"]), _ptr(tb["offsets"]), _ptr(tb["entries"]), _ptr(tb["res_kind"]), _ptr(tb["kappa"]), _ptr(tb["center"]),
+            bs["dm"], bs["mcv"][0], bs["mcv"][1], bs["sigma"][0], bs["sigma"][1], bs["height"], bs["kT"], bs["gamma"], bs["pace"], bs["W"],
+            bs["H"], _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), _ptr(force_row))
+        if rc != _C.OK:
+            raise RuntimeError(f"tmdnet_md_bias: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
+
+    def _start(self, step):
+        # the bias of the start geometry joins ``forces`` (what the first OPEN launch reads): evaluate only, nothing is deposited
+        if not self._bias_ready:
+            self._stage_bias()
+        self._step0 = int(step)
+        _C.lib().tmdnet_md_bias_reset(_stream_ptr(self.pos.device), _ptr(self._bias_ws), self._step0, self._hill_base)
+        self._bias_launch(0, self.forces, self._start_row, self.start_bias_forces)
+
+    def _capture_step(self, k, K, out):
+        self._bias_launch(1, out[1], (self.cv[k], self.restraint_energy[k], self.bias_energy[k]),
+                          None if self.bias_forces is None else self.bias_forces[k])
+        super()._capture_step(k, K, out)
+
+    def _hills_after(self, steps):
+        bs = self.bias
+        return self._hill_base + ((int(steps) - self._step0) // bs["pace"]) * bs["W"] if bs["dm"] else 0
+
+    @property
+    def n_hills(self) -> int:
+        """hills per group that the next step reads (host arithmetic on ``steps_done``; after a frozen replay ``check()`` first)"""
+        return min(self.bias["H"], self._hills_after(self.steps_done))
+
+    def __call__(self, n: int = 1):
+        after = self._hills_after(self.steps_done + int(n) * self.steps_per_replay)
+        if after > self.bias["H"]:
+            raise ValueError(f"metad: {int(n)} replay(s) would deposit up to hill {after} of a group, past capacity={self.bias['H']}; "
+                             "capture with a larger capacity, or reset(hills='clear')")
+        return super().__call__(n)
+
+    def hills(self):
+        """-> (centres [G,n,dm], heights [G,n]) float64 clones of the ``n_hills`` hills of every group"""
+        bs = self.bias
+        if not bs["dm"]:
+            raise ValueError("hills(): this loop was captured without metadynamics")
+        store, n = self._hill_store(), self.n_hills
+        return store[:, :bs["dm"], :n].transpose(1, 2).clone(), store[:, bs["dm"], :n].clone()
+
+    def bias_potential(self, s) -> Tensor:
+        """V(s) of every group's hills in torch float64: ``s`` [...,dm] (or [...] for dm = 1) -> [G,...]; a torsion's difference is
+        wrapped into (-pi, pi]"""
+        bs = self.bias
+        c, w = self.hills()
+        s = torch.as_tensor(s, dtype=torch.float64).to(c.device)
+        if bs["dm"] == 1 and (s.dim() == 0 or s.shape[-1] != 1):
+            s = s[..., None]
+        if s.shape[-1] != bs["dm"]:
+            raise ValueError(f"bias_potential: the last dimension of s must be dm = {bs['dm']}, got {tuple(s.shape)}")
+        shape = s.shape[:-1]
+        d = s.reshape(1, -1, 1, bs["dm"]) - c[:, None, :, :]  # [G,P,n,dm]
+        for k in range(bs["dm"]):
+            if int(bs["kinds"][bs["mcv"][k]]) == CV_KINDS["torsion"][0]:
+                d[..., k] = d[..., k] - 2.0 * math.pi * torch.ceil((d[..., k] - math.pi) / (2.0 * math.pi))
+        sig = torch.tensor(bs["sigma"][:bs["dm"]], dtype=torch.float64, device=c.device)
+        V = (w[:, None, :] * torch.exp(-0.5 * ((d / sig) ** 2).sum(-1))).sum(-1)
+        return V.reshape(self.n_groups, *shape)
+
+    def free_energy(self, s) -> Tensor:
+        """The well-tempered estimate F(s) = -gamma / (gamma - 1) V(s) [G,...], up to a constant.  Plain metadynamics has no such
+        factor (its V keeps growing): ValueError."""
+        g = self.bias["gamma"]
+        if not g > 1:
+            raise ValueError("free_energy: needs well-tempered metadynamics (bias_factor > 1); with plain metadynamics use -bias_potential(s)")
+        return -(g / (g - 1.0)) * self.bias_potential(s)
+
+    def _device_state(self):
+        host = (C.c_uint64 * 2)()
+        dev = self.pos.device
+        with torch.cuda.device(dev):
+            _C.lib().tmdnet_md_status(_stream_ptr(dev), _ptr(self._ws), host)
+        return int(host[0]), int(host[1])
+
+    def reset(self, pos: Optional[Tensor] = None, vel: Optional[Tensor] = None, step: int = 0, hills="keep"):
+        """``DeviceMD.reset``, plus the hills: ``"keep"`` (the device's step counter is read first, so the count is the device's also
+        after a frozen replay), ``"clear"``, or ``(centres [G,n,dm], heights [G,n])`` to restart from saved hills.  Deposits are
+        counted from ``step`` on.  After ``check()`` named the bias (a CV that was not finite) the state is half a step ahead: both
+        ``pos`` and ``vel`` are required."""
+        self._check_fresh()
+        bs = self.bias
+        n_dev, status = self._device_state()
+        if status == 4 and (pos is None or vel is None):
+            raise RuntimeError("bias: a collective variable was not finite, so the MD state is half a step ahead of the last completed "
+                               "step: reset(pos=, vel=) needs both pos and vel")
+        if isinstance(hills, str):
+            if hills not in ("keep", "clear"):
+                raise ValueError(f"reset(hills=...): 'keep', 'clear' or (centres, heights), got {hills!r}")
+            base = min(bs["H"], self._hills_after(n_dev)) if hills == "keep" else 0
+            new = None
+        else:
+            if not bs["dm"]:
+                raise ValueError("reset(hills=(centres, heights)): this loop was captured without metadynamics")
+            c = torch.as_tensor(hills[0], dtype=torch.float64)
+            w = torch.as_tensor(hills[1], dtype=torch.float64)
+            G = self.n_groups
+            if c.dim() == 2 and bs["dm"] == 1:
+                c = c[..., None]
+            if c.dim() != 3 or c.shape[0] != G or c.shape[2] != bs["dm"] or tuple(w.shape) != tuple(c.shape[:2]) or c.shape[1] > bs["H"]:
+                raise ValueError(f"reset(hills=...): needs centres [{G},n,{bs['dm']}] and heights [{G},n] with n <= capacity={bs['H']}, got "
+                                 f"{tuple(c.shape)} and {tuple(w.shape)}")
+            base, new = int(c.shape[1]), (c, w)
+        if new is not None and base:
+            store = self._hill_store()
+            store[:, :bs["dm"], :base] = new[0].to(store.device).transpose(1, 2)
+            store[:, bs["dm"], :base] = new[1].to(store.device)
+        self._hill_base = base
         return super().reset(pos, vel, step)

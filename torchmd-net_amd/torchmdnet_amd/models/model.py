@@ -1425,7 +1425,42 @@ class TorchMD_Net(nn.Module):
         one cluster are limited to 8 atoms and 12 constraints; ``pos`` must satisfy the constraints; ``vel`` is projected onto them.
         Every architecture; not together with ``barostat`` (the constraint forces' virial is not built).  ``md.constraints``,
         ``md.ndof`` [B]; ``md.check()`` raises when an iteration did not converge."""
-        from torchmdnet_amd.md import DeviceMD, parse_barostat, prepare_constraints
+        return self._capture_md(z, pos, vel, masses, dt, batch, box, q, num_systems, steps_per_replay, force_scale, thermostat, warmup,
+                                atom_weights, halo_exchange, barostat, constraints, None)
+
+    def capture_md_biased(self, z: Tensor, pos: Tensor, vel: Tensor, masses: Tensor, dt: float, batch: Optional[Tensor] = None,
+                          box: Optional[Tensor] = None, q: Optional[Tensor] = None, num_systems: Optional[int] = None,
+                          steps_per_replay: int = 10, force_scale: float = 1.0, thermostat: Optional[dict] = None, warmup: int = 3,
+                          atom_weights=None, halo_exchange=None, barostat: Optional[dict] = None, constraints: Optional[dict] = None,
+                          bias: Optional[dict] = None):
+        """``capture_md`` - its parameters in its order, with its meaning - plus ``bias``: collective-variable restraints and
+        metadynamics inside the graph (``tmdnet_md_bias``: one launch per step, between the evaluation and the integrator launch, adds
+        the bias force to the model's force).  The B molecules of the batch are walkers.
+        ``bias=dict(cvs=, restraints=, metad=, log_forces=False)``:
+        ``cvs=[("distance", i, j), ("angle", i, j, k), ("torsion", i, j, k, l), ...]``, at most 8, indices relative to each
+        molecule's first atom (``batch`` must be sorted), on the unwrapped positions without minimum image;
+        ``restraints=[dict(cv=, kind="harmonic" | "upper" | "lower", kappa=, center=)]``, V = kappa / 2 (s - center)^2, ``kappa`` and
+        ``center`` scalars or [B] - umbrella windows are one batch;
+        ``metad=dict(cvs=[...], sigma=[...], height=, pace=, kT=, bias_factor=None, walkers_per_group=1, capacity=)`` on 1 or 2 of
+        the CVs: every ``pace`` steps each walker deposits a Gaussian hill; consecutive walkers form groups of
+        ``walkers_per_group`` that share one list of ``capacity`` hills; ``bias_factor`` gamma > 1 is well-tempered (None: plain).
+        Every architecture ``capture_md`` serves; ``barostat`` and ``constraints`` are refused (the bias forces' virial and the
+        constrained opening half are not wired in).  Returns a ``torchmdnet_amd.md.DeviceBiasedMD``: ``DeviceMD``'s surface
+        (``forces`` is the total force) plus ``cv`` [K,B,D], ``restraint_energy`` / ``bias_energy`` [K,B], ``n_hills``, ``hills()``,
+        ``bias_potential(s)``, ``free_energy(s)`` and ``reset(pos, vel, step, hills="keep" | "clear" | (centres, heights))``."""
+        if bias is None:
+            raise ValueError("capture_md_biased needs bias=dict(cvs=, restraints=, metad=); without a bias use capture_md")
+        if barostat is not None:
+            raise NotImplementedError("capture_md_biased has no HIP path with a barostat: the virial of the bias forces is not built")
+        if constraints is not None:
+            raise NotImplementedError("capture_md_biased has no HIP path with constraints: the bias launch is not wired into the "
+                                      "constrained integrator")
+        return self._capture_md(z, pos, vel, masses, dt, batch, box, q, num_systems, steps_per_replay, force_scale, thermostat, warmup,
+                                atom_weights, halo_exchange, None, None, bias)
+
+    def _capture_md(self, z, pos, vel, masses, dt, batch, box, q, num_systems, steps_per_replay, force_scale, thermostat, warmup,
+                    atom_weights, halo_exchange, barostat, constraints, bias):
+        from torchmdnet_amd.md import DeviceBiasedMD, DeviceMD, parse_barostat, prepare_bias, prepare_constraints
 
         if not getattr(self.representation_model, "static_shapes", False):
             raise RuntimeError("capture_md() needs a model created with static_shapes=True")
@@ -1469,7 +1504,12 @@ class TorchMD_Net(nn.Module):
             box = box if staged.data_ptr() == box.data_ptr() and not box.requires_grad else staged
         if constraints is not None:  # refused before anything is staged or captured
             constraints = prepare_constraints(constraints, pos, batch, masses, n_mol)
+        if bias is not None:  # likewise
+            bias = prepare_bias(bias, batch, z.shape[0], n_mol)
         q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if bias is not None:
+            return DeviceBiasedMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
+                                  bias)
         return DeviceMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
                         barostat, constraints)
 
