@@ -10,7 +10,9 @@ With ``constraints=`` (``TorchMD_Net.capture_md_constrained``) the integrator la
 coupled constraints, still one launch between two evaluations.  ``TorchMD_Net.capture_remd`` (``DeviceREMD``) runs G ladders of R
 replicas of one system and exchanges their temperatures inside the graph (csrc/tn_remd.hip, ``tmdnet_md_exchange``).
 ``TorchMD_Net.capture_md_biased`` (``DeviceBiasedMD``) adds collective-variable restraints and metadynamics: one launch per step
-(csrc/tn_bias.hip, ``tmdnet_md_bias``) adds the bias force to the evaluation's forces before the integrator reads them."""
+(csrc/tn_bias.hip, ``tmdnet_md_bias``) adds the bias force to the evaluation's forces before the integrator reads them.
+The capture sequence, the stale-graph guard, ``md(n)``, the status read-back and the skeleton of ``reset`` are those of every
+captured loop: ``torchmdnet_amd.captured``."""
 import ctypes as C
 import math
 from typing import Optional
@@ -19,6 +21,7 @@ import torch
 from torch import Tensor
 
 from torchmdnet_amd import _C
+from torchmdnet_amd.captured import CapturedLoop
 from torchmdnet_amd.models.utils import _ptr, _stream_ptr
 
 MD_OPEN, MD_MIDDLE, MD_CLOSE, MD_PROJECT = 0, 1, 2, 3  # TMDNET_MD_* of include/tmdnet_amd.h
@@ -225,7 +228,7 @@ def hydrogen_pairs(z, pos, batch=None, cutoff=1.3, rigid_water=False):
     return torch.tensor(pairs, dtype=torch.int64).reshape(-1, 2)
 
 
-class DeviceMD:
+class DeviceMD(CapturedLoop):
     """The object ``TorchMD_Net.capture_md`` returns.  ``md(n)`` replays the captured graph n times (``steps_per_replay`` steps
     each) and returns ``md``; nothing is read back.  Static tensors, rewritten by every replay: ``pos``, ``vel``, ``forces``
     [N,3] at the last completed step, ``epot`` and ``ekin`` [K,B] of the last replay's steps (``ekin`` = sum of 0.5 m v^2 in the
@@ -237,13 +240,15 @@ class DeviceMD:
     ``ndof`` [B] int64 the degrees of freedom per molecule (three per atom of finite mass, minus the molecule's constraints), and
     ``vel`` is projected onto the constraints at capture and at every ``reset``."""
 
+    _capture_name, _noun = "capture_md", "the MD state"
+
     def __init__(self, model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
                  barostat=None, constraints=None):
+        super().__init__(model, steps_per_replay)
         L = _C.lib()
         dev = pos.device
         n = int(z.shape[0])
-        self._model = model
-        self.steps_per_replay = K = int(steps_per_replay)
+        K = self.steps_per_replay
         self.n_atoms, self.n_mol = n, n_mol
         self.dt, self.force_scale = float(dt), float(force_scale)
         self.inputs = (z, batch, box, q)  # what the graph reads, kept alive for as long as it can be replayed
@@ -285,30 +290,22 @@ class DeviceMD:
                                  for k in ("cluster_atoms", "cluster_offsets", "constraint_ends", "constraint_d2"))
             L.tmdnet_md_constraints_workspace_bytes(n, self._tables[0].shape[0], self._tables[2].shape[0], C.byref(nbytes))
             self._cons_ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
-        self.steps_done = 0
-        with torch.cuda.device(dev):
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(max(warmup, 1)):  # uploads parameters, sizes the workspaces, checks overflow
-                    f0 = self._evaluate()[1]
-                self.forces = f0.clone()  # forces at the initial positions: what the first OPEN launch reads
-                L.tmdnet_md_reset(_stream_ptr(dev), _ptr(self._ws), 0)
-                self._start(0)
-                if constraints is not None:  # velocities drawn from a Maxwell-Boltzmann distribution: consistent before step 1
-                    self._advance(MD_PROJECT, None, None, 0)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            if constraints is not None:
-                self.check()
-            self.graph = torch.cuda.CUDAGraph()
-            self._step_outputs = []  # the evaluations' output buffers live in the graph's pool; kept for the graph's lifetime
-            with torch.cuda.graph(self.graph):
-                self._advance(MD_OPEN, self.forces, None, 0)
-                for k in range(K):
-                    out = self._evaluate()
-                    self._step_outputs.append(out)
-                    self._capture_step(k, K, out)
-        self._engine, self._generation = model._engine, model._engine.generation
+
+        def start(out):
+            self.forces = out[1].clone()  # forces at the initial positions: what the first OPEN launch reads
+            self._restart(0)  # with constraints: velocities drawn from a Maxwell-Boltzmann distribution are consistent before step 1
+
+        self._capture(warmup, start, lambda: self._advance(MD_OPEN, self.forces, None, 0),
+                      self.check if constraints is not None else None)
+
+    def _restart(self, step):
+        """What follows the evaluation of the start geometry, at capture and at ``reset``: counter and status, the subclass's
+        ``_start``, and with constraints their status bits cleared and the velocities projected"""
+        _C.lib().tmdnet_md_reset(_stream_ptr(self.pos.device), _ptr(self._ws), step)
+        self._start(step)
+        if self.constraints is not None:
+            self._cons_ws.zero_()
+            self._advance(MD_PROJECT, None, None, 0)
 
     def _stage_sigma(self, m64):
         """[N] fp32 thermal velocities sqrt(kT force_scale / m) the O step reads, from fp64, rounded once"""
@@ -376,18 +373,6 @@ class DeviceMD:
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_md_barostat: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
 
-    def _check_fresh(self):
-        # the graph holds raw pointers into the engine's parameter block and workspaces (TorchMD_Net.capture's replay)
-        if self._model._engine is not self._engine or self._engine.generation != self._generation:
-            raise RuntimeError("stale HIP graph: the model's parameters or workspaces changed after capture_md(); capture again")
-
-    def __call__(self, n: int = 1):
-        self._check_fresh()
-        for _ in range(int(n)):
-            self.graph.replay()
-        self.steps_done += int(n) * self.steps_per_replay
-        return self
-
     def check(self) -> int:
         """Read the device's step counter and status (one synchronisation).  Raises the reference's overflow RuntimeError when an
         evaluation found more neighbours than ``max_num_neighbors`` allows: ``pos`` / ``vel`` / ``forces`` (and ``box``) and the
@@ -399,31 +384,26 @@ class DeviceMD:
         naming the bias (``DeviceBiasedMD``) when a walker's collective variable, its gradient or its bias was not finite: the state
         is frozen, finite and half a step ahead of the last completed step, and ``reset(pos=, vel=)`` is required.  Returns the step
         counter."""
-        host = (C.c_uint64 * 2)()
-        dev = self.pos.device
-        with torch.cuda.device(dev):
-            rc = _C.lib().tmdnet_md_status(_stream_ptr(dev), _ptr(self._ws), host)
+        rc, (step, status) = self._status(_C.lib().tmdnet_md_status, 2)
         if rc == _C.ERR_OVERFLOW:
-            raise RuntimeError("Found num_pairs > max_num_pairs, please increase max_num_pairs "
-                               f"(max_num_neighbors={self._model.representation_model.max_num_neighbors}; the MD state is frozen at "
-                               f"step {int(host[0])})")
-        if int(host[1]) == 2:
-            raise RuntimeError(f"barostat: the move after step {int(host[0])} was not finite (zero volume, or a NaN in the virial or "
+            raise self._overflow(step)
+        if status == 2:
+            raise RuntimeError(f"barostat: the move after step {step} was not finite (zero volume, or a NaN in the virial or "
                                "the kinetic energy); the MD state is frozen before that move")
-        if int(host[1]) == 3:
+        if status == 3:
             bits = int(self._cons_ws.view(torch.int32).max().item()) if self.constraints is not None else 0
             stage = " and ".join(n for b, n in ((1, "SHAKE (positions)"), (2, "RATTLE (velocities)")) if bits & b) or "an iteration"
             raise RuntimeError(f"constraints: {stage} did not converge within max_iter={self.constraints['max_iter']} sweeps to "
-                               f"tol={self.constraints['tol']:g} after step {int(host[0])} (or met a value that is not finite); the MD "
+                               f"tol={self.constraints['tol']:g} after step {step} (or met a value that is not finite); the MD "
                                "state is frozen and finite but is not a point of the trajectory (other clusters may be half a step "
                                "ahead): reset(pos=, vel=) is required")
-        if int(host[1]) == 4:
-            raise RuntimeError(f"bias: a collective variable, its gradient or the bias of a walker was not finite after step {int(host[0])} "
+        if status == 4:
+            raise RuntimeError(f"bias: a collective variable, its gradient or the bias of a walker was not finite after step {step} "
                                "(coincident atoms, a collinear angle or torsion, or a NaN position); the MD state is frozen and finite "
                                "but half a step ahead of that step: reset(pos=, vel=) is required")
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_md_status failed (code {rc})")
-        return int(host[0])
+        return step
 
     def reset(self, pos: Optional[Tensor] = None, vel: Optional[Tensor] = None, step: int = 0, box: Optional[Tensor] = None):
         """New positions and / or velocities (copied into the static buffers), forces evaluated there, status cleared, device step
@@ -432,35 +412,29 @@ class DeviceMD:
         naming the worst pair, before anything is changed), and the velocities are projected onto them again.  After a cluster
         did not converge (``check()`` named the constraints) the state is not a point of the trajectory, so both ``pos`` and ``vel``
         are required: a reset without one of them raises RuntimeError and changes nothing."""
-        self._check_fresh()
         dev = self.pos.device
-        if self.constraints is not None and (pos is None or vel is None):
-            host = (C.c_uint64 * 2)()
-            with torch.cuda.device(dev):
-                _C.lib().tmdnet_md_status(_stream_ptr(dev), _ptr(self._ws), host)
-            if int(host[1]) == 3:
-                raise RuntimeError("constraints: an iteration did not converge, so the MD state is not a point of the trajectory: "
-                                   "reset(pos=, vel=) needs both pos and vel")
-        if self.constraints is not None and pos is not None:
-            _check_positions(pos, self.constraints)
-        if box is not None:
-            if self.box is None:
-                raise ValueError("reset(box=...): this loop was captured without a box")
-            self.box.copy_(box.detach().to(device=dev, dtype=torch.float32).reshape(self.box.shape))
-        if pos is not None:
-            self.pos.copy_(pos.detach().to(device=dev, dtype=torch.float32))
-        if vel is not None:
-            self.vel.copy_(vel.detach().to(device=dev, dtype=torch.float32))
-        f = self._evaluate()[1]  # raises when these positions overflow
-        self.forces.copy_(f)
-        with torch.cuda.device(dev):
-            _C.lib().tmdnet_md_reset(_stream_ptr(dev), _ptr(self._ws), int(step))
-            self._start(int(step))
-            if self.constraints is not None:
-                self._cons_ws.zero_()
-                self._advance(MD_PROJECT, None, None, 0)
-        self.steps_done = int(step)
-        self._check_fresh()  # the evaluation must not have re-created what the graph points into
+
+        def copy_in():
+            if self.constraints is not None and (pos is None or vel is None):
+                if self._status(_C.lib().tmdnet_md_status, 2)[1][1] == 3:
+                    raise RuntimeError("constraints: an iteration did not converge, so the MD state is not a point of the trajectory: "
+                                       "reset(pos=, vel=) needs both pos and vel")
+            if self.constraints is not None and pos is not None:
+                _check_positions(pos, self.constraints)
+            if box is not None:
+                if self.box is None:
+                    raise ValueError("reset(box=...): this loop was captured without a box")
+                self.box.copy_(box.detach().to(device=dev, dtype=torch.float32).reshape(self.box.shape))
+            if pos is not None:
+                self.pos.copy_(pos.detach().to(device=dev, dtype=torch.float32))
+            if vel is not None:
+                self.vel.copy_(vel.detach().to(device=dev, dtype=torch.float32))
+
+        def start(out):
+            self.forces.copy_(out[1])
+            self._restart(int(step))
+
+        self._reset(copy_in, start, step)
         if self.constraints is not None:
             self.check()
         return self
@@ -818,11 +792,7 @@ class DeviceBiasedMD(DeviceMD):
         return -(g / (g - 1.0)) * self.bias_potential(s)
 
     def _device_state(self):
-        host = (C.c_uint64 * 2)()
-        dev = self.pos.device
-        with torch.cuda.device(dev):
-            _C.lib().tmdnet_md_status(_stream_ptr(dev), _ptr(self._ws), host)
-        return int(host[0]), int(host[1])
+        return tuple(self._status(_C.lib().tmdnet_md_status, 2)[1])
 
     def reset(self, pos: Optional[Tensor] = None, vel: Optional[Tensor] = None, step: int = 0, hills="keep"):
         """``DeviceMD.reset``, plus the hills: ``"keep"`` (the device's step counter is read first, so the count is the device's also

@@ -6,7 +6,8 @@ step.  One step is the per-atom update, neighbour list + energy + forces, the pe
 as HIP kernels (csrc/tn_min.hip, ``tmdnet_min_advance``) inside the captured graph, so nothing is issued from the host between two
 steps.  The box is fixed unless ``cell=`` is given: then it relaxes with the atoms (ASE's ``UnitCellFilter`` scheme,
 ``tmdnet_min_advance_cell``).  The scheme and its rounding are documented with the C entries in include/tmdnet_amd.h and in DESIGN.md
-section 14."""
+section 14.  The capture sequence, the stale-graph guard, ``opt(n)``, ``run``, the status read-back and the skeleton of ``reset`` are
+those of every captured loop: ``torchmdnet_amd.captured``."""
 import ctypes as C
 from typing import Optional
 
@@ -14,6 +15,7 @@ import torch
 from torch import Tensor
 
 from torchmdnet_amd import _C
+from torchmdnet_amd.captured import ConvergingLoop
 from torchmdnet_amd.models.utils import _ptr, _stream_ptr
 
 MIN_OPEN, MIN_MIDDLE, MIN_CLOSE = 0, 1, 2  # TMDNET_MIN_* of include/tmdnet_amd.h
@@ -69,7 +71,19 @@ def parse_cell(cell):
     return out
 
 
-class DeviceMinimizer:
+def fire_logs(loop, phase, k):
+    """The seven log pointers of a FIRE advance (``tmdnet_min_advance`` and its cell and band siblings): none for the OPEN phase,
+    the rows of the start geometry for ``k is None``, row k of the last replay's logs otherwise, then the controller's state"""
+    if phase == MIN_OPEN:
+        return [None] * 7
+    if k is None:
+        rows = (loop.epot0, loop.fmax0, loop._sums0, loop.coef0)
+    else:
+        rows = (loop.epot[k], loop.fmax[k], loop.sums[k], loop.coef[k])
+    return [_ptr(t) for t in rows + (loop.step_size, loop.alpha, loop.converged_at)]
+
+
+class DeviceMinimizer(ConvergingLoop):
     """The object ``TorchMD_Net.capture_minimize`` returns.  ``opt(n)`` replays the captured graph n times (``steps_per_replay``
     steps each) and returns ``opt``; nothing is read back.  Static tensors, rewritten by every replay: ``pos`` [N,3]; ``forces``
     [N,3], the forces at ``pos``; ``epot`` and ``fmax`` [K,B], the energy and the largest atomic force norm after each step of the
@@ -87,12 +101,14 @@ class DeviceMinimizer:
     rotation of the cell is not a degree of freedom here: the entries of the cell force below the diagonal are dropped, D stays
     upper triangular and ``H0 D^T`` lower triangular (a shear allowed by ``mask`` acts through the entry above the diagonal)."""
 
+    _capture_name, _noun = "capture_minimize", "the minimiser"
+
     def __init__(self, model, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, fire, fixed, warmup, cell=None):
+        super().__init__(model, steps_per_replay)
         L = _C.lib()
         dev = pos.device
         n = int(z.shape[0])
-        self._model = model
-        self.steps_per_replay = K = int(steps_per_replay)
+        K = self.steps_per_replay
         self.n_atoms, self.n_mol = n, n_mol
         self.fire, self.fmax_bound = parse_fire(fire), float(fmax)
         if not self.fmax_bound > 0:
@@ -118,27 +134,18 @@ class DeviceMinimizer:
         nbytes = C.c_size_t(0)
         L.tmdnet_min_workspace_bytes(n, n_mol, C.byref(nbytes))
         self._ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
-        self.steps_done = 0
         if self.cell is not None:
             self._stage_cell(box, batch)
-        with torch.cuda.device(dev):
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(max(warmup, 1)):  # uploads parameters, sizes the workspaces, checks overflow
-                    e0, f0, *w0 = self._evaluate()
-                self.forces = f0.clone()
-                self._start(e0, f0, *w0)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            self._step_outputs = []  # the evaluations' output buffers live in the graph's pool; kept for the graph's lifetime
-            with torch.cuda.graph(self.graph):
-                self._advance(MIN_OPEN, self.forces, None, None)
-                for k in range(K):
-                    out = self._evaluate()
-                    self._step_outputs.append(out)
-                    self._advance(MIN_MIDDLE if k + 1 < K else MIN_CLOSE, out[1], out[0], k, *out[2:])
-        self._engine, self._generation = model._engine, model._engine.generation
+
+        def start(out):
+            self.forces = out[1].clone()
+            self._start(*out)
+
+        self._capture(warmup, start, lambda: self._advance(MIN_OPEN, self.forces, None, None))
+
+    def _capture_step(self, k, K, out):
+        """The launch that follows evaluation k of a replay (inside the capture): close step k, open step k + 1"""
+        self._advance(MIN_MIDDLE if k + 1 < K else MIN_CLOSE, out[1], out[0], k, *out[2:])
 
     def _stage_cell(self, box, batch):
         """the cell's state and logs, and the workspace with room for it"""
@@ -186,20 +193,17 @@ class DeviceMinimizer:
         st = self._model._engine
         dev = self.pos.device
         f = self.fire
+        is_open = phase == MIN_OPEN
         if k is None:  # the start geometry
-            rows = (self.epot0, self.fmax0, self._sums0, self.coef0)
             cell_rows = (self.stress0, self.volume0, self.cell_force0)
         else:
-            rows = (self.epot[k], self.fmax[k], self.sums[k], self.coef[k])
             cell_rows = (self.stress[k], self.volume[k], self.cell_force[k])
-        is_open = phase == MIN_OPEN
-        logs = [None] * 7 if is_open else [_ptr(t) for t in rows + (self.step_size, self.alpha, self.converged_at)]
         cell_logs = [None] * 3 if is_open else [_ptr(t) for t in cell_rows]
         rc = _C.lib().tmdnet_min_advance_cell(st.handle, _stream_ptr(dev), _ptr(st.graph_ws), _ptr(self._ws), self.n_atoms, self.n_mol,
                                               phase, _ptr(self.pos), _ptr(self.vel), _ptr(forces), _ptr(energy), _ptr(self.fixed),
                                               _ptr(self.inputs[1]), None if is_open else _ptr(self.forces), f["dt_max"], f["n_min"],
-                                              f["f_inc"], f["f_dec"], f["alpha"], f["f_alpha"], f["max_step"], self.fmax_bound, *logs,
-                                              _ptr(self._xt), _ptr(self.box), _ptr(self.deform), _ptr(self._cell_vel), _ptr(virial),
+                                              f["f_inc"], f["f_dec"], f["alpha"], f["f_alpha"], f["max_step"], self.fmax_bound,
+                                              *fire_logs(self, phase, k), _ptr(self._xt), _ptr(self.box), _ptr(self.deform), _ptr(self._cell_vel), _ptr(virial),
                                               _ptr(self._cell_factor), self._mask, self._flags, self.cell["pressure"], *cell_logs)
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_min_advance_cell: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
@@ -210,30 +214,13 @@ class DeviceMinimizer:
         st = self._model._engine
         dev = self.pos.device
         f = self.fire
-        if k is None:  # the start geometry
-            rows = (self.epot0, self.fmax0, self._sums0, self.coef0)
-        else:
-            rows = (self.epot[k], self.fmax[k], self.sums[k], self.coef[k])
-        logs = [None] * 7 if phase == MIN_OPEN else [_ptr(t) for t in rows + (self.step_size, self.alpha, self.converged_at)]
         rc = _C.lib().tmdnet_min_advance(st.handle, _stream_ptr(dev), _ptr(st.graph_ws), _ptr(self._ws), self.n_atoms, self.n_mol, phase,
                                          _ptr(self.pos), _ptr(self.vel), _ptr(forces), _ptr(energy), _ptr(self.fixed),
                                          _ptr(self.inputs[1]), None if phase == MIN_OPEN else _ptr(self.forces), f["dt_max"],
                                          f["n_min"], f["f_inc"], f["f_dec"], f["alpha"], f["f_alpha"], f["max_step"], self.fmax_bound,
-                                         *logs)
+                                         *fire_logs(self, phase, k))
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_min_advance: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
-
-    def _check_fresh(self):
-        # the graph holds raw pointers into the engine's parameter block and workspaces (TorchMD_Net.capture's replay)
-        if self._model._engine is not self._engine or self._engine.generation != self._generation:
-            raise RuntimeError("stale HIP graph: the model's parameters or workspaces changed after capture_minimize(); capture again")
-
-    def __call__(self, n: int = 1):
-        self._check_fresh()
-        for _ in range(int(n)):
-            self.graph.replay()
-        self.steps_done += int(n) * self.steps_per_replay
-        return self
 
     def check(self) -> int:
         """Read the device's step counter and status (one synchronisation).  Raises the reference's overflow RuntimeError when an
@@ -241,64 +228,43 @@ class DeviceMinimizer:
         was not finite: ``pos`` / ``forces``, the logs and the counter are then those of the last valid step, and replays change
         nothing until ``reset``.  With ``cell=`` the error also names a virial that was not finite or a box without volume, and
         ``box`` / ``deform`` are those of the last valid step as well.  Returns the step counter."""
-        host = (C.c_uint64 * 3)()
-        dev = self.pos.device
-        with torch.cuda.device(dev):
-            if self.cell is not None:
-                rc = _C.lib().tmdnet_min_status_cell(_stream_ptr(dev), _ptr(self._ws), host)
-            else:
-                rc = _C.lib().tmdnet_min_status(_stream_ptr(dev), _ptr(self._ws), C.cast(host, C.POINTER(C.c_uint64)))
+        L = _C.lib()
+        rc, (step, status, cause) = self._status(L.tmdnet_min_status if self.cell is None else L.tmdnet_min_status_cell, 3)
         if rc == _C.ERR_OVERFLOW:
-            raise RuntimeError("Found num_pairs > max_num_pairs, please increase max_num_pairs "
-                               f"(max_num_neighbors={self._model.representation_model.max_num_neighbors}; the minimiser is frozen at "
-                               f"step {int(host[0])})")
-        if int(host[1]) == 2 and int(host[2]) == 2:
-            raise RuntimeError(f"minimiser: the virial after step {int(host[0])} is not finite; the state, the box included, is frozen "
+            raise self._overflow(step)
+        if status == 2 and cause == 2:
+            raise RuntimeError(f"minimiser: the virial after step {step} is not finite; the state, the box included, is frozen "
                                "at that step")
-        if int(host[1]) == 2 and int(host[2]) == 3:
-            raise RuntimeError(f"minimiser: the box after step {int(host[0])} has no volume, or the next move would leave it without "
+        if status == 2 and cause == 3:
+            raise RuntimeError(f"minimiser: the box after step {step} has no volume, or the next move would leave it without "
                                "one or not finite; the state, the box included, is frozen at that step")
-        if int(host[1]) == 2:
-            raise RuntimeError(f"minimiser: the forces after step {int(host[0])} are not finite (a NaN or an infinite force sum); the "
+        if status == 2:
+            raise RuntimeError(f"minimiser: the forces after step {step} are not finite (a NaN or an infinite force sum); the "
                                "state is frozen at that step")
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_min_status failed (code {rc})")
-        return int(host[0])
+        return step
 
     def reset(self, pos: Optional[Tensor] = None, box: Optional[Tensor] = None):
         """New positions (copied into the static buffer), forces evaluated there, velocity zero, every molecule's controller back to
         its start values, status cleared, step counters zero.  With ``cell=``: ``box`` (copied into ``self.box``; None: the box as it
         is) becomes the new reference box and ``deform`` the identity."""
-        self._check_fresh()
         dev = self.pos.device
-        if box is not None:
-            if self.cell is None:
-                raise ValueError("reset(box=) needs a minimiser captured with cell=...: the box of this one is fixed")
-            new = box.detach().to(device=dev, dtype=torch.float32).reshape(self.box.shape)
-            if bool((torch.linalg.det(new.double()) == 0).any()):
-                raise ValueError("reset(box=): a box has no volume")
-            self.box.copy_(new)
-        if pos is not None:
-            self.pos.copy_(pos.detach().to(device=dev, dtype=torch.float32))
-        self.vel.zero_()
-        e, f, *w = self._evaluate()  # raises when these positions overflow
-        self.forces.copy_(f)
-        with torch.cuda.device(dev):
-            self._start(e, f, *w)
-        self.steps_done = 0
-        self._check_fresh()  # the evaluation must not have re-created what the graph points into
-        return self
 
-    def run(self, max_steps: int, check_every: int = 1) -> int:
-        """Replay until every molecule has converged or another replay would exceed ``max_steps`` steps; ``converged_at`` is read
-        back (one synchronisation) before the first replay and then after every ``check_every`` replays.  Steps come in whole
-        replays of ``steps_per_replay``.  Returns the number of steps taken by this call; ``check()`` tells whether they were valid."""
-        K, every = self.steps_per_replay, max(int(check_every), 1)
-        taken = 0
-        while not bool((self.converged_at >= 0).all()):
-            n = min(every, (int(max_steps) - taken) // K)
-            if n < 1:
-                break
-            self(n)
-            taken += n * K
-        return taken
+        def copy_in():
+            if box is not None:
+                if self.cell is None:
+                    raise ValueError("reset(box=) needs a minimiser captured with cell=...: the box of this one is fixed")
+                new = box.detach().to(device=dev, dtype=torch.float32).reshape(self.box.shape)
+                if bool((torch.linalg.det(new.double()) == 0).any()):
+                    raise ValueError("reset(box=): a box has no volume")
+                self.box.copy_(new)
+            if pos is not None:
+                self.pos.copy_(pos.detach().to(device=dev, dtype=torch.float32))
+            self.vel.zero_()
+
+        def start(out):
+            self.forces.copy_(out[1])
+            self._start(*out)
+
+        return self._reset(copy_in, start)

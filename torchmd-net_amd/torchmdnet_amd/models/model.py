@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 from torch import Tensor, nn
 
-from torchmdnet_amd import _C, ops, priors
+from torchmdnet_amd import _C, captured, ops, priors
 from torchmdnet_amd.models import output_modules
 from torchmdnet_amd.models.utils import _ptr, _require_cuda, _stream_ptr, dtype_mapping
 
@@ -1328,50 +1328,70 @@ class TorchMD_Net(nn.Module):
         L.tmdnet_graph_cell_grid(st.handle, _stream_ptr(st.graph_ws.device), _ptr(st.graph_ws), n_atoms, n_mol, grid)
         return tuple(int(v) for v in grid)
 
+    def _capture_inputs(self, name, needs, z, pos, batch, box, q, num_systems, steps_per_replay=1, atom_weights=None,
+                        halo_exchange=None, box_moves=False, coords="positions"):
+        """The prelude of every ``capture*`` method ``name``: what no captured graph can serve is refused, then the inputs are staged.
+        ``needs`` is the loop's noun phrase ("a band needs"); None: ``capture`` itself, which serves every head, training models and
+        whatever ``energy_and_forces`` takes as positions.  -> (z, batch, box, q, n_mol, dev)
+
+        The graph records raw device pointers of EVERY input.  They are brought to the device / dtype the engine takes HERE (inside
+        energy_and_forces a conversion would be a temporary) and whoever holds the graph keeps them alive (``inputs``): before this
+        rule a caller that passed temporaries (z.cuda(), an int32 batch, ...) replayed over freed memory.  A box that needs no
+        conversion stays the caller's own object, so that in-place updates remain visible to the graph and a loop's ``box`` IS the
+        tensor the caller scales or reads.  ``box_moves``: the graph also WRITES the box (a barostat, a cell relaxation), so the
+        model's own box is cloned first: it stays as it was created."""
+        if not getattr(self.representation_model, "static_shapes", False):
+            raise RuntimeError(f"{name}() needs a model created with static_shapes=True")
+        if needs is not None and self._head_kind() != _C.HEAD_SCALAR:
+            raise NotImplementedError(f"{name} has no HIP path with output_model {type(self.output_model).__name__}: {needs} energies "
+                                      "and their forces (scalar head)")
+        if needs is not None and self.parameter_gradients:
+            raise NotImplementedError(f"{name} has no HIP path with parameter_gradients=True (a training model); create the model "
+                                      "without it")
+        if atom_weights is not None or halo_exchange is not None:
+            raise NotImplementedError(f"{name} has no HIP path with atom weights or the halo exchange (domain decomposition)")
+        if int(steps_per_replay) < 1:
+            raise ValueError(f"steps_per_replay must be at least 1, got {steps_per_replay}")
+        _require_cuda(pos, name)
+        if needs is not None and pos.dtype != torch.float32:
+            raise NotImplementedError(f"torchmdnet_amd computes in fp32; cast {coords} to float32")
+        batch = torch.zeros_like(z) if batch is None else batch
+        n_mol = int(num_systems) if num_systems is not None else int(batch.max().item()) + 1
+        rm = self.representation_model
+        if box is None and rm.distance.use_periodic:
+            box = rm.distance.box
+        dev = pos.device
+        z = z.detach().to(device=dev, dtype=torch.long).contiguous()
+        batch = batch.detach().to(device=dev, dtype=torch.long).contiguous()
+        q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if box is not None:
+            if box_moves and box is getattr(rm.distance, "box", None):
+                box = box.clone()
+            staged = box.detach().to(device=dev, dtype=torch.float32).contiguous()
+            box = box if staged.data_ptr() == box.data_ptr() and not box.requires_grad else staged
+        return z, batch, box, q, n_mol, dev
+
     def capture(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
                 q: Optional[Tensor] = None, num_systems: Optional[int] = None, warmup: int = 3, virial: bool = False):
         """Capture one energy+force evaluation into a HIP graph (needs ``static_shapes=True``).  ``virial=True``: the graph also
         computes the virial; the replay then returns ``(energy, forces, W [B,3,3])`` and ``replay.virial`` is the static W buffer.
         Returns ``replay(pos) -> (energy [B,1] ([B,3]: vector output), forces [N,3])`` writing into static buffers - the reference gets
         the same effect with torch.cuda.graphs around its model (calculators.py:117-128)."""
-        if not getattr(self.representation_model, "static_shapes", False):
-            raise RuntimeError("capture() needs a model created with static_shapes=True")
-        _require_cuda(pos, "capture")
-        batch = torch.zeros_like(z) if batch is None else batch
-        n_mol = int(num_systems) if num_systems is not None else int(batch.max().item()) + 1
+        z, batch, box, q, n_mol, dev = self._capture_inputs("capture", None, z, pos, batch, box, q, num_systems)
         s_pos = pos.detach().clone().contiguous()
-        rm = self.representation_model
-        if box is None and rm.distance.use_periodic:
-            box = rm.distance.box
-        # the graph records raw device pointers of EVERY input.  They are brought to the device / dtype the engine takes HERE (inside
-        # energy_and_forces a conversion would be a temporary) and the replay closure keeps them alive: before round 4 a caller that
-        # passed temporaries (z.cuda(), an int32 batch, ...) replayed over freed memory.  A tensor that needs no conversion stays the
-        # caller's own object, so in-place updates remain visible to the graph - a barostat scaling `box` between replays.
-        dev = pos.device
-        z = z.detach().to(device=dev, dtype=torch.long).contiguous()
-        batch = batch.detach().to(device=dev, dtype=torch.long).contiguous()
-        box = None if box is None else box.detach().to(device=dev, dtype=torch.float32).contiguous()
-        q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).contiguous()
-        side = torch.cuda.Stream(device=pos.device)
-        side.wait_stream(torch.cuda.current_stream(pos.device))
-        with torch.cuda.stream(side):
-            for _ in range(max(warmup, 1)):  # uploads parameters, sizes the workspaces, checks overflow
-                self.energy_and_forces(z, s_pos, batch, box, q, n_mol, want_forces=True, want_virial=virial)
-        torch.cuda.current_stream(pos.device).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        s_w = None
-        with torch.cuda.graph(graph):
+        out = []
+
+        def evaluate():
             if virial:
-                s_e, s_f, s_w = self.energy_and_forces(z, s_pos, batch, box, q, n_mol, want_forces=True, want_virial=True)
-            else:
-                s_e, s_f = self.energy_and_forces(z, s_pos, batch, box, q, n_mol, want_forces=True)
-        engine, generation = self._engine, self._engine.generation
+                return self.energy_and_forces(z, s_pos, batch, box, q, n_mol, want_forces=True, want_virial=True)
+            return self.energy_and_forces(z, s_pos, batch, box, q, n_mol, want_forces=True)
+
+        graph = captured.capture_graph(dev, evaluate, lambda: out.extend(evaluate()), warmup)
+        s_e, s_f, s_w = out if virial else (*out, None)
+        token = captured.engine_token(self)
 
         def replay(new_pos: Optional[Tensor] = None):
-            # the graph holds raw pointers into the engine's parameter block and workspaces: an eager call after a parameter
-            # change / device move, or with a larger system, re-creates them; replaying would then touch freed memory
-            if self._engine is not engine or engine.generation != generation:
-                raise RuntimeError("stale HIP graph: the model's parameters or workspaces changed after capture(); capture again")
+            captured.check_fresh(captured.engine_token(self), token, "capture()")
             if new_pos is not None:
                 # an elementwise kernel, not Tensor.copy_: a same-dtype device copy goes through the runtime's blit path, which
                 # costs ~3x a small kernel between two graph launches.  Integrators that can write in place use replay.pos.
@@ -1462,33 +1482,12 @@ class TorchMD_Net(nn.Module):
                     atom_weights, halo_exchange, barostat, constraints, bias):
         from torchmdnet_amd.md import DeviceBiasedMD, DeviceMD, parse_barostat, prepare_bias, prepare_constraints
 
-        if not getattr(self.representation_model, "static_shapes", False):
-            raise RuntimeError("capture_md() needs a model created with static_shapes=True")
-        if self._head_kind() != _C.HEAD_SCALAR:
-            raise NotImplementedError(f"capture_md has no HIP path with output_model {type(self.output_model).__name__}: molecular "
-                                      "dynamics needs energies and their forces (scalar head)")
-        if self.parameter_gradients:
-            raise NotImplementedError("capture_md has no HIP path with parameter_gradients=True (a training model); create the model "
-                                      "without it")
-        if atom_weights is not None or halo_exchange is not None:
-            raise NotImplementedError("capture_md has no HIP path with atom weights or the halo exchange (domain decomposition)")
         if constraints is not None and barostat is not None:
             raise NotImplementedError("capture_md has no HIP path with constraints and a barostat together: the virial of the "
                                       "constraint forces is not built")
-        if int(steps_per_replay) < 1:
-            raise ValueError(f"steps_per_replay must be at least 1, got {steps_per_replay}")
-        _require_cuda(pos, "capture_md")
-        if pos.dtype != torch.float32:
-            raise NotImplementedError("torchmdnet_amd computes in fp32; cast positions to float32")
-        batch = torch.zeros_like(z) if batch is None else batch
-        n_mol = int(num_systems) if num_systems is not None else int(batch.max().item()) + 1
-        rm = self.representation_model
-        if box is None and rm.distance.use_periodic:
-            box = rm.distance.box
-        dev = pos.device  # staged as in capture(): the graph records raw pointers, conversions must not be temporaries
-        z = z.detach().to(device=dev, dtype=torch.long).contiguous()
-        batch = batch.detach().to(device=dev, dtype=torch.long).contiguous()
-        if barostat is not None:  # refused before anything is staged or captured
+        z, batch, box, q, n_mol, _ = self._capture_inputs("capture_md", "molecular dynamics needs", z, pos, batch, box, q, num_systems,
+                                                          steps_per_replay, atom_weights, halo_exchange, box_moves=barostat is not None)
+        if barostat is not None:  # everything below is refused before anything is allocated or captured
             parse_barostat(barostat, thermostat)
             self._refuse_virial()
             if box is None:
@@ -1496,18 +1495,10 @@ class TorchMD_Net(nn.Module):
             if box.dim() == 2 and n_mol > 1:
                 raise NotImplementedError("capture_md(barostat=...) has one barostat per molecule: give every molecule its own box "
                                           f"[{n_mol},3,3], not one shared [3,3] box")
-            if box is getattr(rm.distance, "box", None):
-                box = box.clone()  # the model's own box stays as it was created
-        if box is not None:
-            staged = box.detach().to(device=dev, dtype=torch.float32).contiguous()
-            # no conversion: the caller's own object, so that md.box IS the tensor the caller scales or reads
-            box = box if staged.data_ptr() == box.data_ptr() and not box.requires_grad else staged
-        if constraints is not None:  # refused before anything is staged or captured
+        if constraints is not None:
             constraints = prepare_constraints(constraints, pos, batch, masses, n_mol)
-        if bias is not None:  # likewise
-            bias = prepare_bias(bias, batch, z.shape[0], n_mol)
-        q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).contiguous()
         if bias is not None:
+            bias = prepare_bias(bias, batch, z.shape[0], n_mol)
             return DeviceBiasedMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
                                   bias)
         return DeviceMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
@@ -1561,27 +1552,13 @@ class TorchMD_Net(nn.Module):
             raise ValueError(f"capture_remd: vel {tuple(vel.shape)} must have the shape of pos {tuple(pos.shape)}")
         if masses.numel() != n:
             raise ValueError(f"capture_remd: masses must have one entry per atom of the system ({n}), got {masses.numel()}")
-        if not getattr(self.representation_model, "static_shapes", False):
-            raise RuntimeError("capture_remd() needs a model created with static_shapes=True")
-        if self._head_kind() != _C.HEAD_SCALAR:
-            raise NotImplementedError(f"capture_remd has no HIP path with output_model {type(self.output_model).__name__}: molecular "
-                                      "dynamics needs energies and their forces (scalar head)")
-        if self.parameter_gradients:
-            raise NotImplementedError("capture_remd has no HIP path with parameter_gradients=True (a training model)")
-        _require_cuda(pos, "capture_remd")
-        if pos.dtype != torch.float32:
-            raise NotImplementedError("torchmdnet_amd computes in fp32; cast positions to float32")
         G = int(pos.shape[0]) if pos.dim() == 4 else 1
-        B, dev = G * R, pos.device
-        rm = self.representation_model
-        if box is None and rm.distance.use_periodic:
-            box = rm.distance.box
-        if box is not None:
-            if tuple(box.shape) != (3, 3):
-                raise ValueError(f"capture_remd: box must be one shared [3,3] box, got {tuple(box.shape)}")
-            box = box.detach().to(device=dev, dtype=torch.float32).contiguous()
+        B = G * R
+        z, _, box, q, _, dev = self._capture_inputs("capture_remd", "molecular dynamics needs", z, pos, None, box, q, B, K)
+        if box is not None and tuple(box.shape) != (3, 3):
+            raise ValueError(f"capture_remd: box must be one shared [3,3] box, got {tuple(box.shape)}")
         if q is not None:
-            q = q.detach().to(device=dev, dtype=torch.float32).reshape(-1)
+            q = q.reshape(-1)
             if q.numel() != G:
                 raise ValueError(f"capture_remd: q must have one entry per ladder ({G}), got {q.numel()}")
             q = torch.repeat_interleave(q, R).contiguous()
@@ -1590,8 +1567,7 @@ class TorchMD_Net(nn.Module):
             gen = torch.Generator().manual_seed(int(thermostat.get("seed", 0)) & (2 ** 63 - 1))
             sd = torch.sqrt(kT[:, None] * float(force_scale) / masses.detach().cpu().to(torch.float64).reshape(1, n))  # [R,n]; m = inf: 0
             vel = (torch.randn((G, R, n, 3), generator=gen, dtype=torch.float64) * sd[None, :, :, None]).to(torch.float32).to(dev)
-        z_all = z.detach().to(device=dev, dtype=torch.long).repeat(B).contiguous()
-        return DeviceREMD(self, z_all, pos.reshape(-1, 3), vel.reshape(-1, 3), m_all, dt, kT, X, G, box, q, K, force_scale,
+        return DeviceREMD(self, z.repeat(B).contiguous(), pos.reshape(-1, 3), vel.reshape(-1, 3), m_all, dt, kT, X, G, box, q, K, force_scale,
                           dict(thermostat), warmup)
 
     def capture_minimize(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
@@ -1619,33 +1595,14 @@ class TorchMD_Net(nn.Module):
         fixed-box path, unchanged."""
         from torchmdnet_amd.minimize import DeviceMinimizer, parse_cell, parse_fire
 
-        if not getattr(self.representation_model, "static_shapes", False):
-            raise RuntimeError("capture_minimize() needs a model created with static_shapes=True")
-        if self._head_kind() != _C.HEAD_SCALAR:
-            raise NotImplementedError(f"capture_minimize has no HIP path with output_model {type(self.output_model).__name__}: a "
-                                      "minimisation needs energies and their forces (scalar head)")
-        if self.parameter_gradients:
-            raise NotImplementedError("capture_minimize has no HIP path with parameter_gradients=True (a training model); create the "
-                                      "model without it")
-        if atom_weights is not None or halo_exchange is not None:
-            raise NotImplementedError("capture_minimize has no HIP path with atom weights or the halo exchange (domain decomposition)")
-        if int(steps_per_replay) < 1:
-            raise ValueError(f"steps_per_replay must be at least 1, got {steps_per_replay}")
         if not float(fmax) > 0:
             raise ValueError(f"fmax must be positive, got {fmax}")
-        parse_fire(fire)  # refused before anything is staged or captured
+        parse_fire(fire)
         if fixed is not None and fixed.numel() != z.shape[0]:
             raise ValueError(f"fixed must have one entry per atom ({z.shape[0]}), got {fixed.numel()}")
-        _require_cuda(pos, "capture_minimize")
-        if pos.dtype != torch.float32:
-            raise NotImplementedError("torchmdnet_amd computes in fp32; cast positions to float32")
-        batch = torch.zeros_like(z) if batch is None else batch
-        n_mol = int(num_systems) if num_systems is not None else int(batch.max().item()) + 1
-        rm = self.representation_model
-        if box is None and rm.distance.use_periodic:
-            box = rm.distance.box
-        dev = pos.device  # staged as in capture(): the graph records raw pointers, conversions must not be temporaries
-        if cell is not None:  # refused before anything is staged or captured
+        z, batch, box, q, n_mol, _ = self._capture_inputs("capture_minimize", "a minimisation needs", z, pos, batch, box, q, num_systems,
+                                                          steps_per_replay, atom_weights, halo_exchange, box_moves=cell is not None)
+        if cell is not None:  # refused before anything is allocated or captured
             parse_cell(cell)
             self._refuse_virial()
             if box is None:
@@ -1655,18 +1612,6 @@ class TorchMD_Net(nn.Module):
                                           f"[{n_mol},3,3], not one shared [3,3] box")
             if bool((torch.linalg.det(box.detach().to(torch.float64)) == 0).any()):
                 raise ValueError("capture_minimize(cell=...): a box has no volume")
-            if box is getattr(rm.distance, "box", None):
-                box = box.clone()  # the model's own box stays as it was created
-            staged = box.detach().to(device=dev, dtype=torch.float32).contiguous()
-            # no conversion: the caller's own object, so that opt.box IS the tensor the caller reads (as md.box)
-            box = box if staged.data_ptr() == box.data_ptr() and not box.requires_grad else staged
-        z = z.detach().to(device=dev, dtype=torch.long).contiguous()
-        batch = batch.detach().to(device=dev, dtype=torch.long).contiguous()
-        if cell is None:
-            box = None if box is None else box.detach().to(device=dev, dtype=torch.float32).contiguous()
-        q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).contiguous()
-        if cell is None:
-            return DeviceMinimizer(self, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, fire, fixed, warmup)
         return DeviceMinimizer(self, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, fire, fixed, warmup, cell)
 
     def capture_neb(self, z: Tensor, images: Tensor, box: Optional[Tensor] = None, q: Optional[Tensor] = None,
@@ -1688,19 +1633,9 @@ class TorchMD_Net(nn.Module):
         from torchmdnet_amd.minimize import parse_fire
         from torchmdnet_amd.neb import DeviceNEB, parse_neb
 
-        if not getattr(self.representation_model, "static_shapes", False):
-            raise RuntimeError("capture_neb() needs a model created with static_shapes=True")
-        if self._head_kind() != _C.HEAD_SCALAR:
-            raise NotImplementedError(f"capture_neb has no HIP path with output_model {type(self.output_model).__name__}: a band "
-                                      "needs energies and their forces (scalar head)")
-        if self.parameter_gradients:
-            raise NotImplementedError("capture_neb has no HIP path with parameter_gradients=True (a training model); create the "
-                                      "model without it")
-        if int(steps_per_replay) < 1:
-            raise ValueError(f"steps_per_replay must be at least 1, got {steps_per_replay}")
         if not float(fmax) > 0:
             raise ValueError(f"fmax must be positive, got {fmax}")
-        parse_fire(fire)  # refused before anything is staged or captured
+        parse_fire(fire)
         parse_neb(dict(spring=spring, climb=climb))
         if z.dim() != 1:
             raise ValueError(f"z must be [n], the atoms of ONE image, got {tuple(z.shape)}")
@@ -1716,18 +1651,11 @@ class TorchMD_Net(nn.Module):
             raise ValueError(f"fixed must have one entry per atom of an image ({n}), got {fixed.numel()}")
         if q is not None and q.numel() != n_bands:
             raise ValueError(f"q must have one entry per band ({n_bands}), got {q.numel()}")
-        _require_cuda(images, "capture_neb")
-        if images.dtype != torch.float32:
-            raise NotImplementedError("torchmdnet_amd computes in fp32; cast the images to float32")
-        rm = self.representation_model
-        if box is None and rm.distance.use_periodic:
-            box = rm.distance.box
+        z, _, box, q, _, _ = self._capture_inputs("capture_neb", "a band needs", z, images, None, box, q,
+                                                  n_bands * int(images.shape[-3]), steps_per_replay, coords="the images")
         if box is not None and box.dim() != 2:
             raise ValueError(f"capture_neb takes one [3,3] box shared by all images, got {tuple(box.shape)}")
-        dev = images.device  # staged as in capture(): the graph records raw pointers, conversions must not be temporaries
-        z = z.detach().to(device=dev, dtype=torch.long).contiguous()
-        box = None if box is None else box.detach().to(device=dev, dtype=torch.float32).contiguous()
-        q = None if q is None else q.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        q = None if q is None else q.reshape(-1)
         images = images if images.dim() == 4 else images[None]
         return DeviceNEB(self, z, images, box, q, steps_per_replay, fmax, spring, climb, fire, fixed, warmup)
 

@@ -6,7 +6,8 @@ same n atoms; the M images of G bands are evaluated as one batch of G M molecule
 controller and the per-atom update run as HIP kernels (csrc/tn_neb.hip, ``tmdnet_neb_advance``) inside the captured graph, so nothing
 is issued from the host between two steps.  Images 0 and M - 1 of every band never move.  No minimum image is applied between
 images: the caller supplies an unwrapped path.  The scheme and its rounding are documented with the C entries in
-include/tmdnet_amd.h and in DESIGN.md section 15."""
+include/tmdnet_amd.h and in DESIGN.md section 15.  The capture sequence, the stale-graph guard, ``neb(n)``, ``run``, the status
+read-back and the skeleton of ``reset`` are those of every captured loop: ``torchmdnet_amd.captured``."""
 import ctypes as C
 import math
 from typing import Optional
@@ -15,7 +16,8 @@ import torch
 from torch import Tensor
 
 from torchmdnet_amd import _C
-from torchmdnet_amd.minimize import MIN_CLOSE, MIN_MIDDLE, MIN_OPEN, parse_fire
+from torchmdnet_amd.captured import ConvergingLoop
+from torchmdnet_amd.minimize import MIN_CLOSE, MIN_MIDDLE, MIN_OPEN, fire_logs, parse_fire
 from torchmdnet_amd.models.utils import _ptr, _stream_ptr
 
 #: the band's own parameters and their defaults (``spring`` in E / length^2)
@@ -51,7 +53,7 @@ def interpolate(initial: Tensor, final: Tensor, n_images: int) -> Tensor:
     return path
 
 
-class DeviceNEB:
+class DeviceNEB(ConvergingLoop):
     """The object ``TorchMD_Net.capture_neb`` returns.  ``neb(n)`` replays the captured graph n times (``steps_per_replay`` steps
     each) and returns ``neb``; nothing is read back.  Static tensors, rewritten by every replay: ``images`` [G,M,n,3], a view of the
     position buffer the graph reads; ``forces`` [G,M,n,3], the band forces F_neb at ``images`` (zero on the endpoint images);
@@ -63,12 +65,14 @@ class DeviceNEB:
     the device's own logs, and ``epot0 / fmax0 / coef0 / tangent_coef0 / climber0`` those of the start path.  ``steps_done`` counts on
     the host; ``check()`` reads the device."""
 
+    _capture_name, _noun = "capture_neb", "the band"
+
     def __init__(self, model, z, images, box, q, steps_per_replay, fmax, spring, climb, fire, fixed, warmup):
+        super().__init__(model, steps_per_replay)
         L = _C.lib()
         dev = images.device
         G, M, n = (int(s) for s in images.shape[:3])
-        self._model = model
-        self.steps_per_replay = K = int(steps_per_replay)
+        K = self.steps_per_replay
         self.n_bands, self.n_images, self.n_atoms = G, M, n
         self.fire, self.fmax_bound = parse_fire(fire), float(fmax)
         opts = parse_neb(dict(spring=spring, climb=climb))
@@ -101,26 +105,17 @@ class DeviceNEB:
         if L.tmdnet_neb_workspace_bytes(n, M, G, C.byref(nbytes)) != _C.OK:
             raise ValueError(f"a band of {G} x {M} x {n} rows is beyond what tmdnet_neb_workspace_bytes accepts")
         self._ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
-        self.steps_done = 0
-        with torch.cuda.device(dev):
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(max(warmup, 1)):  # uploads parameters, sizes the workspaces, checks overflow
-                    e0, f0 = self._evaluate()
-                self._forces = torch.zeros_like(f0)
-                self._start(e0, f0)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            self._step_outputs = []  # the evaluations' output buffers live in the graph's pool; kept for the graph's lifetime
-            with torch.cuda.graph(self.graph):
-                self._advance(MIN_OPEN, self._forces, None, None)
-                for k in range(K):
-                    out = self._evaluate()
-                    self._step_outputs.append(out)
-                    self._advance(MIN_MIDDLE if k + 1 < K else MIN_CLOSE, out[1], out[0], k)
+
+        def start(out):
+            self._forces = torch.zeros_like(out[1])
+            self._start(*out)
+
+        self._capture(warmup, start, lambda: self._advance(MIN_OPEN, self._forces, None, None))
         self.forces = self._forces.view(G, M, n, 3)
-        self._engine, self._generation = model._engine, model._engine.generation
+
+    def _capture_step(self, k, K, out):
+        """The launch that follows evaluation k of a replay (inside the capture): close step k, open step k + 1"""
+        self._advance(MIN_MIDDLE if k + 1 < K else MIN_CLOSE, out[1], out[0], k)
 
     def _evaluate(self):
         z, batch, box, q = self.inputs
@@ -139,100 +134,59 @@ class DeviceNEB:
         dev = self.pos.device
         f = self.fire
         if k is None:  # the start path
-            rows = (self.epot0, self.fmax0, self._sums0, self.coef0)
             band = (self.path_sums0, self.weights0, self.tangent_coef0, self.climber0)
         else:
-            rows = (self.epot[k], self.fmax[k], self.sums[k], self.coef[k])
             band = (self.path_sums[k], self.weights[k], self.tangent_coef[k], self.climber[k])
         is_open = phase == MIN_OPEN
-        logs = [None] * 7 if is_open else [_ptr(t) for t in rows + (self.step_size, self.alpha, self.converged_at)]
         band_logs = [None] * 4 if is_open else [_ptr(t) for t in band]
         rc = _C.lib().tmdnet_neb_advance(st.handle, _stream_ptr(dev), _ptr(st.graph_ws), _ptr(self._ws), self.n_atoms, self.n_images,
                                          self.n_bands, phase, _ptr(self.pos), _ptr(self.vel), _ptr(forces), _ptr(energy),
                                          _ptr(self.fixed), None if is_open else _ptr(self._forces), f["dt_max"], f["n_min"], f["f_inc"],
-                                         f["f_dec"], f["alpha"], f["f_alpha"], f["max_step"], self.fmax_bound, self.spring, *logs,
-                                         *band_logs)
+                                         f["f_dec"], f["alpha"], f["f_alpha"], f["max_step"], self.fmax_bound, self.spring,
+                                         *fire_logs(self, phase, k), *band_logs)
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_neb_advance: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
-
-    def _check_fresh(self):
-        # the graph holds raw pointers into the engine's parameter block and workspaces (TorchMD_Net.capture's replay)
-        if self._model._engine is not self._engine or self._engine.generation != self._generation:
-            raise RuntimeError("stale HIP graph: the model's parameters or workspaces changed after capture_neb(); capture again")
-
-    def __call__(self, n: int = 1):
-        self._check_fresh()
-        for _ in range(int(n)):
-            self.graph.replay()
-        self.steps_done += int(n) * self.steps_per_replay
-        return self
 
     def check(self) -> int:
         """Read the device's step counter and status (one synchronisation).  Raises the reference's overflow RuntimeError when an
         evaluation found more neighbours than ``max_num_neighbors`` allows, and a RuntimeError naming the cause when a band was
         unusable - band forces or an energy that are not finite, or coincident images: ``images`` / ``forces``, the logs and the
         counter are then those of the last valid step, and replays change nothing until ``reset``.  Returns the step counter."""
-        host = (C.c_uint64 * 3)()
-        dev = self.pos.device
-        with torch.cuda.device(dev):
-            rc = _C.lib().tmdnet_neb_status(_stream_ptr(dev), _ptr(self._ws), host)
+        rc, (step, status, cause) = self._status(_C.lib().tmdnet_neb_status, 3)
         if rc == _C.ERR_OVERFLOW:
-            raise RuntimeError("Found num_pairs > max_num_pairs, please increase max_num_pairs "
-                               f"(max_num_neighbors={self._model.representation_model.max_num_neighbors}; the band is frozen at "
-                               f"step {int(host[0])})")
-        if int(host[1]) == 2:
-            why = _CAUSES.get(int(host[2]), "a sum is not finite")
-            raise RuntimeError(f"nudged elastic band: after step {int(host[0])} {why}; the state is frozen at that step")
+            raise self._overflow(step)
+        if status == 2:
+            why = _CAUSES.get(cause, "a sum is not finite")
+            raise RuntimeError(f"nudged elastic band: after step {step} {why}; the state is frozen at that step")
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_neb_status failed (code {rc})")
-        return int(host[0])
+        return step
 
     def reset(self, images: Optional[Tensor] = None, climb: Optional[bool] = None):
         """New images (copied into the static buffer; None: the path as it is), ``climb`` switched (None: as it is), forces evaluated
         there, velocity zero, every band's controller back to its start values, status cleared, step counters zero.  The captured
         graph serves both phases: relax with ``climb=False``, then ``reset(climb=True)`` and go on from the relaxed path."""
-        self._check_fresh()
-        dev = self.pos.device
-        if images is not None:
-            want = tuple(self.images.shape)
-            if tuple(images.shape) != want and not (self.n_bands == 1 and tuple(images.shape) == want[1:]):
-                raise ValueError(f"reset(images=) needs {want}" + (f" or {want[1:]}" if self.n_bands == 1 else "") +
-                                 f", got {tuple(images.shape)}")
-            self.pos.copy_(images.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3))
-        if climb is not None:
-            self.climb = bool(climb)
-        self.vel.zero_()
-        e, f = self._evaluate()  # raises when these positions overflow
-        with torch.cuda.device(dev):
-            self._start(e, f)
-        self.steps_done = 0
-        self._check_fresh()  # the evaluation must not have re-created what the graph points into
-        return self
 
-    def run(self, max_steps: int, check_every: int = 1) -> int:
-        """Replay until every band has converged or another replay would exceed ``max_steps`` steps; ``converged_at`` is read back
-        (one synchronisation) before the first replay and then after every ``check_every`` replays.  Steps come in whole replays of
-        ``steps_per_replay``.  Returns the number of steps taken by this call; ``check()`` tells whether they were valid."""
-        K, every = self.steps_per_replay, max(int(check_every), 1)
-        taken = 0
-        while not bool((self.converged_at >= 0).all()):
-            n = min(every, (int(max_steps) - taken) // K)
-            if n < 1:
-                break
-            self(n)
-            taken += n * K
-        return taken
+        def copy_in():
+            if images is not None:
+                want = tuple(self.images.shape)
+                if tuple(images.shape) != want and not (self.n_bands == 1 and tuple(images.shape) == want[1:]):
+                    raise ValueError(f"reset(images=) needs {want}" + (f" or {want[1:]}" if self.n_bands == 1 else "") +
+                                     f", got {tuple(images.shape)}")
+                self.pos.copy_(images.detach().to(device=self.pos.device, dtype=torch.float32).reshape(-1, 3))
+            if climb is not None:
+                self.climb = bool(climb)
+            self.vel.zero_()
+
+        return self._reset(copy_in, lambda out: self._start(*out))
 
     def barrier(self) -> Tensor:
         """``max_i E_i - E_0`` of every band at the last valid evaluated step, [G] on the host.  The step is the device's counter
         (read as ``check()`` reads it, without raising), so after a replay that froze part-way the row of the step the state is
         frozen at is taken, not the last row of the log; then one read-back of that row."""
-        host = (C.c_uint64 * 3)()
-        dev = self.pos.device
-        with torch.cuda.device(dev):
-            rc = _C.lib().tmdnet_neb_status(_stream_ptr(dev), _ptr(self._ws), host)
+        rc, (step, _, _) = self._status(_C.lib().tmdnet_neb_status, 3)
         if rc not in (_C.OK, _C.ERR_OVERFLOW, _C.ERR_STATE):
             raise RuntimeError(f"tmdnet_neb_status failed (code {rc})")
-        step = int(host[0])  # step s > 0 was logged in row (s - 1) % K, and nothing was written after it
-        e = self.epot0 if step == 0 else self.epot[(step - 1) % self.steps_per_replay]
+        # step s > 0 was logged in row (s - 1) % K, and nothing was written after it
+        e =self.epot0 if step == 0 else self.epot[(step - 1) % self.steps_per_replay]
         return (e.max(dim=1).values - e[:, 0]).cpu()

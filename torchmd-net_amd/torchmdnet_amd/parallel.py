@@ -11,6 +11,8 @@ from typing import Callable, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from torchmdnet_amd.captured import capture_graph, check_fresh
+
 
 def molecule_ranges(batch: torch.Tensor, n_mol: int, world: int):
     """Contiguous molecule ranges balanced by atom count (edges ~ atoms).  ``batch`` must be sorted.
@@ -133,15 +135,7 @@ class ShardSession:
         if graph and m_hi > m_lo:
             if not pos.is_cuda:
                 raise RuntimeError("graph=True needs device tensors")
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(max(warmup, 1)):
-                    self._local()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self._local()
+            self.graph = capture_graph(dev, self._local, self._local, warmup)
             self._token = guard() if guard else None
 
     def _local(self):
@@ -159,8 +153,8 @@ class ShardSession:
             else:
                 self.pos_l.copy_(src)
         if self.graph is not None:
-            if self.guard and self.guard() != self._token:
-                raise RuntimeError("stale HIP graph: the model's parameters or workspaces changed after prepare(); prepare again")
+            if self.guard:
+                check_fresh(self.guard(), self._token, "prepare()", "prepare again")
             self.graph.replay()
         else:
             self._local()
