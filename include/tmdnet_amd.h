@@ -342,6 +342,16 @@ const char* tmdnet_profile_category_name(int idx);
  * Copy an intermediate of the last tmdnet_energy_forces call out of the workspace (device -> device).
  * Names: "X_embed", "X_layer<l>", "x", "phi", "Q", "u0", "G_embed".  Used by the parity tests. */
 int tmdnet_debug_tensor(tmdnet_model* m, void* stream, const char* name, float* out, int64_t numel);
+/* Copy one array of the graph that tmdnet_build_graph[_static] last left in `graph_ws` into the device buffer `out` (device ->
+ * device on `stream`, no kernel; n_atoms / n_mol as in that build, `bytes` = the array's whole capacity).  Names, element type
+ * and count, with ecap = max_num_neighbors * n_atoms and pcap = ecap / 2 + 1: int32 "counts" [8], "mstart" / "mend" [n_mol],
+ * "nlow" / "ntot" / "perm" / "cell_key_sorted" [n_atoms], "rowptr" / "pairptr" [n_atoms + 1], "col" / "epair" [ecap],
+ * "pair_i" / "pair_j" [pcap], "cgrid" [4], "cell_start" [8 n_atoms + 2]; float "esign" [ecap], "pd" [pcap + 1],
+ * "pdelta" / "prhat" [3 pcap], "boxd" [12]; int64 "z_c" / "bat_c" [n_atoms].  TMDNET_ERR_STATE when no graph was built on
+ * `graph_ws`, TMDNET_ERR_INVALID for an unknown name, a wrong byte count or other n_atoms / n_mol; nothing is written then.
+ * Used by the graph unit tests (tests/test_gpu_graph.py). */
+int tmdnet_debug_graph(tmdnet_model* m, void* stream, const void* graph_ws, int64_t n_atoms, int64_t n_mol, const char* name,
+                       void* out, int64_t bytes);
 /* plain dense contraction through the path's MFMA GEMM: C[M,N] = A[M,K] @ W[N,K]^T (+bias) (silu != 0: silu of it); Wsb as
  * for tmdnet_debug_gemm_dual (NULL: fp32-MFMA kernels); for unit tests */
 /* value + tangent GEMM of the edge MLP (kind 0 plain, 1 silu, 2 silu * rs with rs2 = d rs): C = f(A W^T + b), C2 = d/dd.

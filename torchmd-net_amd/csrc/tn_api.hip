@@ -205,9 +205,9 @@ void tensor_linear(hipStream_t s, const float* A, const float* const W3[3], floa
 
 
 // per-workspace record of the last graph build (tn_model.h GraphRecord)
-void remember_graph(tmdnet_model* m, const void* graph_ws) {
+void remember_graph(tmdnet_model* m, const void* graph_ws, int64_t n_atoms, int64_t n_mol) {
   if (m->graph_rec.size() >= 64 && !m->graph_rec.count(graph_ws)) m->graph_rec.clear();  // workspaces regrown many times: old addresses are dead
-  m->graph_rec[graph_ws] = tmdnet_model::GraphRecord{m->graph_is_cell, m->graph_cell_multi, m->graph_has_z, m->last_nt, m->lastE, m->graph_no_ghost_pairs};
+  m->graph_rec[graph_ws] = tmdnet_model::GraphRecord{m->graph_is_cell, m->graph_cell_multi, m->graph_has_z, m->last_nt, m->lastE, m->graph_no_ghost_pairs, n_atoms, n_mol};
 }
 void recall_graph(tmdnet_model* m, const void* graph_ws) {
   auto it = m->graph_rec.find(graph_ws);
@@ -1249,7 +1249,7 @@ int tmdnet_build_graph(tmdnet_model* m, void* stream, void* graph_ws, size_t gra
   for (int k = 0; k < 8; ++k) counts_host[k] = counts[k];
   m->last_nt = (z && m->rb_fwd && n_atoms >= m->rb_min_atoms) ? counts[6] : 0;
   m->lastE = counts[1];
-  remember_graph(m, graph_ws);
+  remember_graph(m, graph_ws, n_atoms, n_mol);
   if (counts[5])
     return fail(m, TMDNET_ERR_INVALID, "batch index out of range: every entry must be in [0, " + std::to_string(n_mol) + ")");
   if (counts[4])
@@ -1313,7 +1313,7 @@ int tmdnet_build_graph_static(tmdnet_model* m, void* stream, void* graph_ws, siz
   }
   m->lastE = ecap;
   m->last_nt = 0;  // static shapes: no read-back, the embedding keeps the per-pair tables
-  remember_graph(m, graph_ws);
+  remember_graph(m, graph_ws, n_atoms, n_mol);
   HIP_TRY(m, hipGetLastError());
   return TMDNET_OK;
 }
@@ -2258,6 +2258,34 @@ int tmdnet_debug_tensor(tmdnet_model* m, void* stream, const char* name, float* 
   if (!src || numel != n) return fail(m, TMDNET_ERR_INVALID, "debug tensor size mismatch: expected " + std::to_string(n));
   HIP_TRY(m, hipMemcpyAsync(out, src, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
   return TMDNET_OK;
+}
+
+// one named array of the graph last built on graph_ws (carve_graph locates it), whole capacity, device -> device; no kernel
+int tmdnet_debug_graph(tmdnet_model* m, void* stream, const void* graph_ws, int64_t n_atoms, int64_t n_mol, const char* name,
+                       void* out, int64_t bytes) {
+  if (!m || !graph_ws || !name || !out || n_atoms < 0 || n_mol < 0) return TMDNET_ERR_INVALID;
+  const auto it = m->graph_rec.find(graph_ws);
+  if (it == m->graph_rec.end()) return fail(m, TMDNET_ERR_STATE, "no graph was built on this workspace");
+  if (it->second.n_atoms != n_atoms || it->second.n_mol != n_mol)
+    return fail(m, TMDNET_ERR_INVALID, "debug graph: the last build on this workspace had other n_atoms / n_mol");
+  const int64_t N = n_atoms, B = n_mol;
+  const Graph g = carve_graph(const_cast<void*>(graph_ws), N, B, (int64_t)m->hp.max_num_neighbors * N, nullptr);
+  const struct { const char* name; const void* ptr; int64_t bytes; } arrays[] = {
+      {"counts", g.counts, 8 * 4},          {"mstart", g.mstart, B * 4},          {"mend", g.mend, B * 4},
+      {"nlow", g.nlow, N * 4},              {"ntot", g.ntot, N * 4},              {"rowptr", g.rowptr, (N + 1) * 4},
+      {"pairptr", g.pairptr, (N + 1) * 4},  {"col", g.col, g.ecap * 4},           {"epair", g.epair, g.ecap * 4},
+      {"esign", g.esign, g.ecap * 4},       {"pair_i", g.pair_i, g.pcap * 4},     {"pair_j", g.pair_j, g.pcap * 4},
+      {"pd", g.pd, (g.pcap + 1) * 4},       {"pdelta", g.pdelta, g.pcap * 12},    {"prhat", g.prhat, g.pcap * 12},
+      {"perm", g.perm, N * 4},              {"z_c", g.z_c, N * 8},                {"bat_c", g.bat_c, N * 8},
+      {"cgrid", g.cgrid, 4 * 4},            {"boxd", g.boxd, 12 * 4},             {"cell_key_sorted", g.cell_key_sorted, N * 4},
+      {"cell_start", g.cell_start, (8 * N + 2) * 4}};
+  for (const auto& a : arrays) {
+    if (std::strcmp(a.name, name)) continue;
+    if (bytes != a.bytes) return fail(m, TMDNET_ERR_INVALID, "debug graph size mismatch: expected " + std::to_string(a.bytes) + " bytes");
+    if (a.bytes > 0) HIP_TRY(m, hipMemcpyAsync(out, a.ptr, (size_t)a.bytes, hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
+    return TMDNET_OK;
+  }
+  return fail(m, TMDNET_ERR_INVALID, std::string("unknown graph array: ") + name);
 }
 
 int tmdnet_debug_gemm_dual(void* stream, const float* A, const float* A2, const float* W, const float* bias, float* C, float* C2,

@@ -189,7 +189,7 @@ struct tmdnet_model {
   bool graph_has_z = false;   // last build validated z into Graph::z_c (internal order)
   // what each graph workspace was last built as (host side, keyed by its address): a call that takes a workspace restores the four
   // fields above / last_nt from its record, so builds on several workspaces may be interleaved with their evaluations
-  struct GraphRecord { bool is_cell, cell_multi, has_z; int nt; int64_t lastE; bool no_ghost_pairs; };
+  struct GraphRecord { bool is_cell, cell_multi, has_z; int nt; int64_t lastE; bool no_ghost_pairs; int64_t n_atoms, n_mol; };
   std::unordered_map<const void*, GraphRecord> graph_rec;
   std::vector<ParamSpec> specs;
   std::map<std::string, std::vector<float>> host;
