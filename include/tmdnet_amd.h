@@ -167,7 +167,12 @@ const char* tmdnet_param_name(const tmdnet_model* m, int idx, int64_t* numel);
  * rows (one definition, csrc/tn_interp.h): energies and forces are bit-identical.  Needs the tables (verified, not switched
  * off); tmdnet_energy_forces reports TMDNET_ERR_STATE otherwise.  tmdnet_forward_workspace_bytes plans for the embedding form
  * of the graph this handle built LAST (query it after tmdnet_build_graph of the same system, as the Python host does); a plan made
- * for another graph is refused with TMDNET_ERR_WORKSPACE, never overrun. */
+ * for another graph is refused with TMDNET_ERR_WORKSPACE, never overrun.
+ * "fold_node_adjoint" (TensorNet handle; default 1): when the graph came from tmdnet_build_graph on the brute-force path, `batch`
+ * was sorted and no molecule lies across a multiple of 64 atoms (counts_host[7] == 0), and the step takes the tile sweeps
+ * (TMDNET_MSG_GD_TILE) without halo exchange, parameter gradients or "recompute_pair_rows", the reverse tile sweep computes the
+ * adjoint of the group product in its prologue instead of reading it from a kernel of its own.  Same arithmetic (one definition,
+ * csrc/tn_common.h): forces are bit-identical with 0 and 1.  Info "message_adjoint_fold_last": 1 when the last call ran that way. */
 int tmdnet_set_option(tmdnet_model* m, const char* name, double value);
 int tmdnet_get_info(const tmdnet_model* m, const char* name, double* value);
 
@@ -179,7 +184,8 @@ int tmdnet_get_info(const tmdnet_model* m, const char* name, double* value);
  * Produces a deterministic pair list + symmetric CSR inside `graph_ws`.
  * counts_host[0] = number of undirected pairs P, [1] = number of directed edges incl. self loops E,
  * [2] = overflow flag, [3] = 1 if `batch` was not sorted (slow path), [4] = 1 if an atomic number was outside
- * [0, max_z), [5] = 1 if a molecule index was outside [0, n_mol); [6..7] reserved.
+ * [0, max_z), [5] = 1 if a molecule index was outside [0, n_mol); [6] = species count (embedding in the radial basis),
+ * [7] = 1 if an atom i > 0, i % 64 == 0, shares its molecule with atom i - 1 (a molecule across a 64-row tile boundary).
  * `z` (int64 [n_atoms], may be NULL) is validated here, in the same read-back: out-of-range values return
  * TMDNET_ERR_INVALID before any table is indexed with them (the reference's nn.Embedding raises IndexError,
  * tensornet.py:473); a validated copy in the graph's internal atom order is kept in `graph_ws` and used by
@@ -486,6 +492,36 @@ typedef struct tmdnet_message_args {
   int64_t slot_stride;
 } tmdnet_message_args;
 int tmdnet_debug_message(void* stream, const tmdnet_message_args* args, int32_t* route_out, int32_t* slot_arrays_out);
+/* The reverse tile sweep with the adjoint of the group product in its prologue (k_message_adjoint_rows8_fold), or the sequence it
+ * replaces, on a caller-built graph (additive; no model handle; for unit tests).  With gM, gY the gradients of
+ * sum(gCh * C_hat(Pn, Mi)) with respect to Mi and Pn (C_hat as out2 of TMDNET_MSG_OP_FWD above, kap from q / batch the same way):
+ *   gPn[i] = gY[i] + sum_e w[p] gM[j];   slots[a][2 p + dir] as TMDNET_MSG_OP_GD above with src = gM, src2 = Pn, a over F / 32.
+ * folded != 0: one launch; gMi is neither read nor written (may be NULL).  folded == 0: k_message_bwd_node writes gMi and gY,
+ * then k_message_adjoint_rows8 - the same result, gMi required.  gPn need not be initialised in either mode.
+ * The graph is in the engine's form (tmdnet_debug_message) and, for folded != 0, must have CLOSED tiles: col[e] / 64 == i / 64
+ * for every entry e of every row i.  This one property IS validated (the arrays are read back; the call synchronises the
+ * stream): TMDNET_ERR_INVALID and no launch otherwise, as for N < 1, P < 0, F % 32, slot_stride < 2 P, a NULL or misaligned
+ * (16 bytes) operand. */
+typedef struct tmdnet_message_fold_args {
+  int32_t N, F, P, o3, folded;
+  const int32_t* rowptr; /* [N + 1] */
+  const int32_t* col;
+  const int32_t* epair;
+  const float* esign;
+  const int32_t* counts; /* [8] */
+  const float* w;        /* [P + 1, 3, F] */
+  const float* dw;       /* [P + 1, 3, F] */
+  const float* gCh;      /* [N, 9, F] */
+  const float* Pn;       /* [N, 9, F] */
+  const float* Mi;       /* [N, 9, F] */
+  const float* q;        /* optional */
+  const int64_t* batch;  /* optional */
+  float* gMi;            /* [N, 9, F], written when folded == 0 */
+  float* gPn;            /* [N, 9, F] */
+  float* slots;          /* F / 32 arrays of slot_stride floats */
+  int64_t slot_stride;
+} tmdnet_message_fold_args;
+int tmdnet_debug_message_fold(void* stream, const tmdnet_message_fold_args* args);
 
 /* ---- First-order parameter gradients (TensorNet, TensorNet2 and Equivariant Transformer handles; energy-only training).
  * Replaces what autograd does in the reference for `loss(E).backward()` over torchmdnet/models/tensornet.py:543-619, 729-814,

@@ -207,7 +207,7 @@ void tensor_linear(hipStream_t s, const float* A, const float* const W3[3], floa
 // per-workspace record of the last graph build (tn_model.h GraphRecord)
 void remember_graph(tmdnet_model* m, const void* graph_ws, int64_t n_atoms, int64_t n_mol) {
   if (m->graph_rec.size() >= 64 && !m->graph_rec.count(graph_ws)) m->graph_rec.clear();  // workspaces regrown many times: old addresses are dead
-  m->graph_rec[graph_ws] = tmdnet_model::GraphRecord{m->graph_is_cell, m->graph_cell_multi, m->graph_has_z, m->last_nt, m->lastE, m->graph_no_ghost_pairs, n_atoms, n_mol};
+  m->graph_rec[graph_ws] = tmdnet_model::GraphRecord{m->graph_is_cell, m->graph_cell_multi, m->graph_has_z, m->last_nt, m->lastE, m->graph_no_ghost_pairs, n_atoms, n_mol, m->graph_closed_tiles};
 }
 void recall_graph(tmdnet_model* m, const void* graph_ws) {
   auto it = m->graph_rec.find(graph_ws);
@@ -218,6 +218,7 @@ void recall_graph(tmdnet_model* m, const void* graph_ws) {
   m->last_nt = it->second.nt;
   m->lastE = it->second.lastE;
   m->graph_no_ghost_pairs = it->second.no_ghost_pairs;
+  m->graph_closed_tiles = it->second.closed_tiles;
 }
 
 // fused form (tn_tlin9.hip): the weights' fragment-major images must exist (F % 32 == 0); `tensors` = [N, 9, F] tensors the
@@ -1161,6 +1162,11 @@ int tmdnet_set_option(tmdnet_model* m, const char* name, double value) {
     m->recompute_rows = value != 0.0;
     return TMDNET_OK;
   }
+  if (n == "fold_node_adjoint") {
+    if (m->et || m->tn2) return fail(m, TMDNET_ERR_INVALID, "fold_node_adjoint applies to the TensorNet handle only");
+    m->fold_node_adjoint = value != 0.0;
+    return TMDNET_OK;
+  }
   return fail(m, TMDNET_ERR_INVALID, "unknown option: " + n);
 }
 
@@ -1185,6 +1191,8 @@ int tmdnet_get_info(const tmdnet_model* m, const char* name, double* value) {
   else if (n == "halo_active_rows") *value = (double)m->halo_active[1];
   else if (n == "message_route_last") *value = (double)m->msg_route_last[0];  // TMDNET_MSG_* of the last TensorNet step's sweeps
   else if (n == "message_adjoint_route_last") *value = (double)m->msg_route_last[1];
+  else if (n == "fold_node_adjoint") *value = m->fold_node_adjoint ? 1.0 : 0.0;
+  else if (n == "message_adjoint_fold_last") *value = (double)m->msg_fold_last;  // 1: the last step's reverse tile sweeps ran folded
   else return TMDNET_ERR_INVALID;
   return TMDNET_OK;
 }
@@ -1249,6 +1257,8 @@ int tmdnet_build_graph(tmdnet_model* m, void* stream, void* graph_ws, size_t gra
   for (int k = 0; k < 8; ++k) counts_host[k] = counts[k];
   m->last_nt = (z && m->rb_fwd && n_atoms >= m->rb_min_atoms) ? counts[6] : 0;
   m->lastE = counts[1];
+  // closed tiles (k_mol_ranges): brute-force graph (pairs never cross molecules), sorted batch, no molecule across a multiple of 64 rows
+  m->graph_closed_tiles = !cell && counts[3] == 0 && counts[5] == 0 && counts[7] == 0;
   remember_graph(m, graph_ws, n_atoms, n_mol);
   if (counts[5])
     return fail(m, TMDNET_ERR_INVALID, "batch index out of range: every entry must be in [0, " + std::to_string(n_mol) + ")");
@@ -1313,6 +1323,7 @@ int tmdnet_build_graph_static(tmdnet_model* m, void* stream, void* graph_ws, siz
   }
   m->lastE = ecap;
   m->last_nt = 0;  // static shapes: no read-back, the embedding keeps the per-pair tables
+  m->graph_closed_tiles = false;  // ... and nothing is known about the molecules' rows
   remember_graph(m, graph_ws, n_atoms, n_mol);
   HIP_TRY(m, hipGetLastError());
   return TMDNET_OK;
@@ -1555,6 +1566,7 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
   const bool chain_gf = chain_gate && (m->chain_mask & 2) && fm_image(W.L1) && fm_image(W.L2);
   const bool chain_gb = chain_gate && (m->chain_mask & 4) && fm_image(W.L2T) && fm_image(W.L1T);
   m->chain_last = (chain_ro ? 1 : 0) | (chain_gf ? 2 : 0) | (chain_gb ? 4 : 0);
+  m->msg_fold_last = 0;  // set by the reverse half when its tile sweeps run folded
   if (run_fwd) {
     if (use_tab) {
       // radial tables (tn_edge_table.hip): sort the pairs by distance, one streaming Hermite-interpolation kernel for all
@@ -1839,16 +1851,23 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
     const int gd_nw = message_adjoint_gd_waves(g, N, F, recompute);
     const int64_t gd_stride = 2 * (int64_t)P1;
     if (!merged_gd) launch_fill(b.gd, 0.f, P1, s);  // the per-layer pair kernels accumulate into it
+    // Closed tiles: the reverse tile sweep computes the group-product adjoint in its prologue (k_message_adjoint_rows8_fold);
+    // k_message_bwd_node is not launched and gMi not written.  Everything that reads gMi or a row range keeps the pair of launches.
+    const bool fold = t9r && merged_gd && m->fold_node_adjoint && m->graph_closed_tiles && !m->graph_is_cell && !m->halo_fn && !rng &&
+                      !recompute && message_adjoint_gd_route(g, N, F, recompute, a0, -1, !m->graph_no_ghost_pairs) == MSG_GD_TILE;
+    m->msg_fold_last = fold ? 1 : 0;
     for (int l = L - 1; l >= 0; --l) {
       const LayerP& q_ = W.layer[l];
       if (t9r) {
-        // update adjoint while G is staged (g_D never reaches memory), transposed linear; the adjoint of the group product stays a
-        // kernel of its own: in the epilogue its 3x3 temporaries spilled and the fused launch lost to the pair (180 vs 77 + 62 us)
+        // update adjoint while G is staged (g_D never reaches memory), transposed linear; the adjoint of the group product is not
+        // part of it: in the epilogue its 3x3 temporaries spilled and the fused launch lost to the pair (180 vs 77 + 62 us).  It is a
+        // kernel of its own, or - closed tiles - the prologue of the reverse tile sweep below
         Tl9Args ta{};
         ta.A = b.G + o9F; ta.A2 = b.D[l] + o9F; ta.kap = q_a; ta.N = Na; ta.F = F; ta.C = b.gCh + o9F;
         tlin9(s, TL9_PRO_UPDBWD, TL9_EPI_PLAIN, q_.VT + 3, ta, 3.0, "updbwd");
-        KR(CAT_ELEMENTWISE, 5 * nodeB, launch_message_bwd_node(b.gCh + o9F, b.Pn[l] + o9F, b.Mi[l] + o9F, q_a, batch_a, o3, Na, F,
-                                                               b.gMi + o9F, b.gPn + o9F, s));
+        if (!fold)
+          KR(CAT_ELEMENTWISE, 5 * nodeB, launch_message_bwd_node(b.gCh + o9F, b.Pn[l] + o9F, b.Mi[l] + o9F, q_a, batch_a, o3, Na, F,
+                                                                 b.gMi + o9F, b.gPn + o9F, s));
       } else {
       // gD of the layers below the top one comes out of the previous iteration's fused normalisation adjoint
       if (l == L - 1) KR(CAT_ELEMENTWISE, 3 * nodeB, launch_update_bwd(b.G, b.D[l], q, batch_k, N, F, b.gD, s));
@@ -1878,7 +1897,12 @@ int tmdnet_energy_forces(tmdnet_model* m, void* stream, void* graph_ws, void* ws
       }
       m->msg_route_last[1] = merged_gd ? message_adjoint_gd_route(g, N, F, recompute, a0, rng ? a0 + Na : -1, !m->graph_no_ghost_pairs)
                                        : message_adjoint_route(N, F);
-      if (merged_gd) {
+      if (fold) {
+        const NodeAdjointFold nf{b.gCh, b.Mi[l], q_a, batch_a, o3};
+        KR(CAT_MESSAGE, 2 * wB + idxB + nodeB * 4.0 + 8 * (Pd + 1) * gd_nw,  // w, dw, gCh, Pn, Mi read and gPn written once each, g_d slots
+           launch_message_adjoint_gd(g, N, F, b.w[l], b.dw[l], nullptr, b.Pn[l], b.gPn, b.gd_slots + (int64_t)l * gd_nw * gd_stride,
+                                     gd_stride, s, nullptr, a0, -1, !m->graph_no_ghost_pairs, &nf));
+      } else if (merged_gd) {
         KR(CAT_MESSAGE, 2 * wB + idxB + nodeB * (2.0 + 2.0 * Na / Nd) + 8 * (Pd + 1) * gd_nw,  // w, dw, gMi, Pn, gPn (read + write: swept rows), g_d slots
            launch_message_adjoint_gd(g, N, F, b.w[l], b.dw[l], b.gMi, b.Pn[l], b.gPn, b.gd_slots + (int64_t)l * gd_nw * gd_stride,
                                      gd_stride, s, recompute ? &rts[l] : nullptr, a0, rng ? a0 + Na : -1, !m->graph_no_ghost_pairs));
@@ -2493,6 +2517,48 @@ int tmdnet_debug_message(void* stream, const tmdnet_message_args* x, int32_t* ro
       else launched = launch_message_dual_as(r, g, N, F, x->w, x->w2, x->src, x->src2, x->out, x->out2, s);
   }
   if (!launched) return TMDNET_ERR_INVALID;
+  return hipGetLastError() == hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
+}
+
+int tmdnet_debug_message_fold(void* stream, const tmdnet_message_fold_args* x) {
+  if (!x) return TMDNET_ERR_INVALID;
+  const int N = x->N, F = x->F;
+  if (N < 1 || F < 32 || F % 32 || x->P < 0 || x->slot_stride < 2 * (int64_t)x->P) return TMDNET_ERR_INVALID;
+  if (!x->rowptr || !x->col || !x->epair || !x->esign || !x->counts) return TMDNET_ERR_INVALID;
+  if (!x->w || !x->dw || !x->gCh || !x->Pn || !x->Mi || !x->gPn || !x->slots || (!x->folded && !x->gMi)) return TMDNET_ERR_INVALID;
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  if (!al16(x->w) || !al16(x->dw) || !al16(x->gCh) || !al16(x->Pn) || !al16(x->Mi) || !al16(x->gMi) || !al16(x->gPn)) return TMDNET_ERR_INVALID;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (hipGetLastError() != hipSuccess) return TMDNET_ERR_HIP;
+  Graph g{};
+  g.rowptr = const_cast<int*>(x->rowptr);
+  g.col = const_cast<int*>(x->col);
+  g.epair = const_cast<int*>(x->epair);
+  g.esign = const_cast<float*>(x->esign);
+  g.counts = const_cast<int*>(x->counts);
+  g.small_mols = 1;
+  if (x->folded) {
+    // closed tiles: the one property the folded kernel's window depends on
+    std::vector<int> rp((size_t)N + 1);
+    if (hipMemcpyAsync(rp.data(), x->rowptr, rp.size() * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
+    if (rp[0] != 0) return TMDNET_ERR_INVALID;
+    for (int i = 0; i < N; ++i)
+      if (rp[i + 1] < rp[i] || rp[i + 1] - rp[i] > 64) return TMDNET_ERR_INVALID;
+    std::vector<int> col((size_t)rp[N]);
+    if (!col.empty()) {
+      if (hipMemcpyAsync(col.data(), x->col, col.size() * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
+      if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
+    }
+    for (int i = 0; i < N; ++i)
+      for (int e = rp[i]; e < rp[i + 1]; ++e)
+        if (col[e] < 0 || col[e] >= N || (col[e] >> 6) != (i >> 6)) return TMDNET_ERR_INVALID;
+    const NodeAdjointFold nf{x->gCh, x->Mi, x->q, x->batch, x->o3};
+    launch_message_adjoint_pair(g, N, F, x->w, x->dw, nullptr, x->Pn, x->gPn, x->slots, x->slot_stride, s, &nf);
+  } else {
+    launch_message_bwd_node(x->gCh, x->Pn, x->Mi, x->q, x->batch, x->o3, N, F, x->gMi, x->gPn, s);
+    launch_message_adjoint_pair(g, N, F, x->w, x->dw, x->gMi, x->Pn, x->gPn, x->slots, x->slot_stride, s);
+  }
   return hipGetLastError() == hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
 }
 

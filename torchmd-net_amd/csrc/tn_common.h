@@ -170,6 +170,105 @@ __device__ __forceinline__ float frob2(const M3& x) {
   return s;
 }
 
+// per-atom factor of the O(3) group product; batch == null: q already is the per-atom factor (k_kappa, energy_forces passes it
+// that way)
+__device__ __forceinline__ float kappa_of(const float* __restrict__ q, const int64_t* __restrict__ batch, int n) {
+  return q ? (batch ? __builtin_fmaf(0.1f, q[batch[n]], 1.0f) : q[n]) : 1.0f;  // one rounding in every kernel
+}
+
+// Adjoint of (Y, M) -> C_hat = C / (||C||^2 + 1),  C = kappa (Y M + M Y)  (O(3))  or  2 Y M  (SO(3)), one channel:
+// gM wrt the message components, gY the direct part wrt the normalised node tensor.  The one definition of k_message_bwd_node
+// (tn_kernels.hip) and of the folded prologue of the reverse tile sweep (tn_message_pair.hip), which must agree BIT FOR BIT: the
+// engine switches between them per batch.  Left to the compiler they did not - one channel per thread there, four channels per
+// thread here, packed differently by the vectoriser, so a*b+c was fused in one kernel and not in the other (a few ulp in 40 % of
+// the elements).  As in pair_geometry: contraction off and the fused multiply-adds spelled out, here and in the 3x3 helpers the
+// function uses (xm_*: the helpers above with a fixed rounding; compose, compose_T and transpose only add or move).
+__device__ __forceinline__ M3 xm_matmul(const M3& x, const M3& y) {
+#pragma clang fp contract(off)
+  M3 r;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      r.a[i][j] = __builtin_fmaf(x.a[i][2], y.a[2][j], __builtin_fmaf(x.a[i][1], y.a[1][j], x.a[i][0] * y.a[0][j]));
+  return r;
+}
+__device__ __forceinline__ M3 xm_add_scaled(const M3& x, const M3& y, float s) {  // (x + y) * s
+#pragma clang fp contract(off)
+  M3 r;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) r.a[i][j] = (x.a[i][j] + y.a[i][j]) * s;
+  return r;
+}
+__device__ __forceinline__ M3 xm_scale(const M3& x, float s) {
+#pragma clang fp contract(off)
+  M3 r;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) r.a[i][j] = x.a[i][j] * s;
+  return r;
+}
+__device__ __forceinline__ void group_product_adjoint(const float gc[9], const float y[9], const float m[9], float kap, int o3,
+                                                      float gm[9], float gy[9]) {
+#pragma clang fp contract(off)
+  const M3 Y = compose(y), M = compose(m);
+  const M3 Cm = o3 ? xm_add_scaled(xm_matmul(Y, M), xm_matmul(M, Y), kap) : xm_scale(xm_matmul(Y, M), 2.0f);
+  // uc = dec(Cm) (decompose), its norm, and gCm = dec^T(gc * inv) + 2 g_t Cm
+  const float tr3 = (Cm.a[0][0] + Cm.a[1][1] + Cm.a[2][2]) * (1.0f / 3.0f);
+  const float uc[9] = {tr3,
+                       0.5f * (Cm.a[2][1] - Cm.a[1][2]),
+                       0.5f * (Cm.a[0][2] - Cm.a[2][0]),
+                       0.5f * (Cm.a[1][0] - Cm.a[0][1]),
+                       Cm.a[0][0] - tr3,
+                       0.5f * (Cm.a[0][1] + Cm.a[1][0]),
+                       0.5f * (Cm.a[0][2] + Cm.a[2][0]),
+                       Cm.a[1][1] - tr3,
+                       0.5f * (Cm.a[1][2] + Cm.a[2][1])};
+  float f2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) f2 = __builtin_fmaf(Cm.a[i][j], Cm.a[i][j], f2);
+  const float inv = 1.0f / (f2 + 1.0f);
+  float dot = 0.f, g[9];
+#pragma unroll
+  for (int c = 0; c < 9; ++c) {
+    dot = __builtin_fmaf(gc[c], uc[c], dot);
+    g[c] = gc[c] * inv;
+  }
+  const float g2 = 2.0f * (-dot * inv * inv);
+  const float t = (g[0] - g[4] - g[7]) * (1.0f / 3.0f);
+  M3 D;  // decompose_T(g)
+  D.a[0][0] = t + g[4];
+  D.a[0][1] = 0.5f * (g[5] - g[3]);
+  D.a[0][2] = 0.5f * (g[6] + g[2]);
+  D.a[1][0] = 0.5f * (g[5] + g[3]);
+  D.a[1][1] = t + g[7];
+  D.a[1][2] = 0.5f * (g[8] - g[1]);
+  D.a[2][0] = 0.5f * (g[6] - g[2]);
+  D.a[2][1] = 0.5f * (g[8] + g[1]);
+  D.a[2][2] = t;
+  M3 gCm;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gCm.a[i][j] = __builtin_fmaf(Cm.a[i][j], g2, D.a[i][j]);
+  const M3 Yt = transpose(Y), Mt = transpose(M);
+  M3 gY, gM;
+  if (o3) {
+    gY = xm_add_scaled(xm_matmul(gCm, Mt), xm_matmul(Mt, gCm), kap);
+    gM = xm_add_scaled(xm_matmul(Yt, gCm), xm_matmul(gCm, Yt), kap);
+  } else {
+    gY = xm_scale(xm_matmul(gCm, Mt), 2.0f);
+    gM = xm_scale(xm_matmul(Yt, gCm), 2.0f);
+  }
+  compose_T(gM, gm);
+  compose_T(gY, gy);
+}
+
 __device__ __forceinline__ int type_of(int c) { return c == 0 ? 0 : (c < 4 ? 1 : 2); }
 
 // wave-level sum over 64 lanes (all lanes get the result)

@@ -177,6 +177,7 @@ __global__ __launch_bounds__(1024) void k_graph_small(Graph g, const float* __re
         const int64_t bp = s_batch[i - 1];
         if (bp > b) s_counts[3] = 1;
         if (bp != b) gl.mstart[b] = i;
+        else if ((i & 63) == 0) s_counts[7] = 1;  // a molecule across a multiple of 64 rows, as k_mol_ranges reports it
       } else {
         gl.mstart[b] = 0;
       }

@@ -133,12 +133,23 @@ void launch_message_adjoint(const Graph& g, int N, int F, const float* w, const 
 bool message_adjoint_gd_ok(int N, int F);
 int message_adjoint_gd_waves(const Graph& g, int N, int F, bool rows_from_table = false);  // slot arrays the sweep writes per layer
 bool message_adjoint_pair_ok(const Graph& g, int N, int F);  // tn_message_pair.hip: the reverse sweep in the tile layout
+// Operands of the group-product adjoint (k_message_bwd_node) when the tile sweep computes it in its prologue
+// (k_message_adjoint_rows8_fold): only for a graph whose tiles are closed - every neighbour of a row within the row's own aligned
+// 64 rows - which the caller has to know; the sweep then reads neither gMi nor an initialised gPn.
+struct NodeAdjointFold {
+  const float* gCh;
+  const float* Mi;
+  const float* q;
+  const int64_t* batch;
+  int o3;
+};
 void launch_message_adjoint_pair(const Graph& g, int N, int F, const float* w, const float* dw, const float* gMi, const float* Pn,
-                                 float* gPn, float* slots, int64_t slot_stride, hipStream_t s);
+                                 float* gPn, float* slots, int64_t slot_stride, hipStream_t s, const NodeAdjointFold* fold = nullptr);
 void launch_message_adjoint_gd(const Graph& g, int N, int F, const float* w, const float* dw, const float* gMi, const float* Pn,
                                float* gPn, float* slots, int64_t slot_stride, hipStream_t s, const PairRowTable* rt = nullptr, int own0 = 0,
-                               int own1 = -1, bool narrow = true);  // own1 >= 0: rows outside [own0, own1) are ghosts (no gPn; narrow: their pairs
-                                                                    // with owned atoms are searched for in the row - the graph holds ghost-ghost pairs)
+                               int own1 = -1, bool narrow = true,  // own1 >= 0: rows outside [own0, own1) are ghosts (no gPn; narrow: their pairs
+                                                                   // with owned atoms are searched for in the row - the graph holds ghost-ghost pairs)
+                               const NodeAdjointFold* fold = nullptr);  // non-null: the route must be MSG_GD_TILE (the caller checks)
 // next = 0: plain; 1: nxt = X_hat of the new X (next layer's k_norm_x); 2: nxt = readout invariants of the new X
 void launch_layer_update(const float* Xh, const float* D, const float* q, const int64_t* batch, int N, int F, float* Xn, int next,
                          float* nxt, hipStream_t s);

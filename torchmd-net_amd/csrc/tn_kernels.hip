@@ -34,6 +34,9 @@ __global__ void k_mol_ranges(const int64_t* __restrict__ batch, int N, int B, in
     int64_t bp = batch[i - 1];
     if (bp > b) counts[3] = 1;
     if (bp != b) mstart[b] = i;
+    // a molecule straddles a multiple of 64 rows: the tiles of the message sweeps are not closed (the host reads it with the
+    // pair counts; meaningful for a sorted batch only, counts[3] == 0)
+    else if ((i & 63) == 0) counts[7] = 1;
   } else {
     mstart[b] = 0;
   }
@@ -593,10 +596,6 @@ __device__ __forceinline__ void store9(float* __restrict__ p, int F, const float
 #pragma unroll
   for (int c = 0; c < 9; ++c) p[c * F] = u[c];
 }
-__device__ __forceinline__ float kappa_of(const float* __restrict__ q, const int64_t* __restrict__ batch, int n) {
-  // batch == null: q already is the per-atom factor (k_kappa, energy_forces passes it that way)
-  return q ? (batch ? 1.0f + 0.1f * q[batch[n]] : q[n]) : 1.0f;
-}
 
 // X_hat = X / (||X||^2 + 1)   (reference tensornet.py:745)
 __global__ void k_norm_x(const float* __restrict__ X, float* __restrict__ Xh, int N, int F) {
@@ -1033,7 +1032,12 @@ bool launch_message_adjoint_gd_as(MsgRoute r, const Graph& g, int N, int F, cons
   }
 }
 void launch_message_adjoint_gd(const Graph& g, int N, int F, const float* w, const float* dw, const float* gMi, const float* Pn,
-                               float* gPn, float* slots, int64_t slot_stride, hipStream_t s, const PairRowTable* rt, int own0, int own1, bool narrow) {
+                               float* gPn, float* slots, int64_t slot_stride, hipStream_t s, const PairRowTable* rt, int own0, int own1, bool narrow,
+                               const NodeAdjointFold* fold) {
+  if (fold) {  // the caller has checked that the route is MSG_GD_TILE and that the graph's tiles are closed
+    launch_message_adjoint_pair(g, N, F, w, dw, gMi, Pn, gPn, slots, slot_stride, s, fold);
+    return;
+  }
   launch_message_adjoint_gd_as(message_adjoint_gd_route(g, N, F, rt != nullptr, own0, own1, narrow), g, N, F, w, dw, gMi, Pn, gPn, slots,
                                slot_stride, s, rt, own0, own1, narrow);
 }
@@ -1424,33 +1428,10 @@ __global__ void k_message_bwd_node(const float* __restrict__ gCh, const float* _
   load9(Pn + (int64_t)n * 9 * F + f, F, y);
   load9(Mi + (int64_t)n * 9 * F + f, F, m);
   const float kap = kappa_of(q, batch, n);
-  const M3 Y = compose(y), M = compose(m);
-  const M3 Cm = o3 ? scale(add(matmul(Y, M), matmul(M, Y)), kap) : scale(matmul(Y, M), 2.0f);
-  float uc[9];
-  decompose(Cm, uc);
-  const float inv = 1.0f / (frob2(Cm) + 1.0f);
-  float dot = 0.f, guc[9];
-#pragma unroll
-  for (int c = 0; c < 9; ++c) {
-    dot += gc[c] * uc[c];
-    guc[c] = gc[c] * inv;
-  }
-  const float g_t = -dot * inv * inv;
-  const M3 gCm = add(decompose_T(guc), scale(Cm, 2.0f * g_t));
-  const M3 Yt = transpose(Y), Mt = transpose(M);
-  M3 gY, gM;
-  if (o3) {
-    gY = scale(add(matmul(gCm, Mt), matmul(Mt, gCm)), kap);
-    gM = scale(add(matmul(Yt, gCm), matmul(gCm, Yt)), kap);
-  } else {
-    gY = scale(matmul(gCm, Mt), 2.0f);
-    gM = scale(matmul(Yt, gCm), 2.0f);
-  }
-  float o[9];
-  compose_T(gM, o);
-  store9(gMi + (int64_t)n * 9 * F + f, F, o);
-  compose_T(gY, o);
-  store9(gPn + (int64_t)n * 9 * F + f, F, o);
+  float gm[9], gy[9];
+  group_product_adjoint(gc, y, m, kap, o3, gm, gy);  // tn_common.h
+  store9(gMi + (int64_t)n * 9 * F + f, F, gm);
+  store9(gPn + (int64_t)n * 9 * F + f, F, gy);
 }
 void launch_message_bwd_node(const float* gCh, const float* Pn, const float* Mi, const float* q, const int64_t* batch, int o3, int N,
                              int F, float* gMi, float* gPn, hipStream_t s) {

@@ -161,6 +161,10 @@ struct tmdnet_model {
   int* halo_rng = nullptr;          // device scratch: first / last / count of the owned rows in the engine's order
   bool graph_no_ghost_pairs = false;  // the last graph was built with the exchange set: no pairs of two ghosts in it
   int halo_active[2] = {0, 0};      // [first row, rows] the per-atom kernels of the last step ran on ("halo_active_rows")
+  bool fold_node_adjoint = true;    // option "fold_node_adjoint": the reverse tile sweep computes the group-product adjoint in its prologue
+  bool graph_closed_tiles = false;  // the last graph is a brute-force one of a sorted batch, built through tmdnet_build_graph, in which
+                                    // no molecule straddles a multiple of 64 rows (counts[7] of the read-back): every tile is closed
+  int msg_fold_last = 0;            // the last step's reverse sweeps ran folded ("message_adjoint_fold_last")
   int msg_route_last[2] = {0, 0};   // MsgRoute of the last step's forward and reverse neighbour sweeps ("message_route_last", "message_adjoint_route_last")
   tmdnet_hparams hp;
   int head_kind = 0;  // tmdnet_set_output_head: 0 scalar, 1 dipole moment, 2 electronic spatial extent (tn_heads.hip)
@@ -189,7 +193,7 @@ struct tmdnet_model {
   bool graph_has_z = false;   // last build validated z into Graph::z_c (internal order)
   // what each graph workspace was last built as (host side, keyed by its address): a call that takes a workspace restores the four
   // fields above / last_nt from its record, so builds on several workspaces may be interleaved with their evaluations
-  struct GraphRecord { bool is_cell, cell_multi, has_z; int nt; int64_t lastE; bool no_ghost_pairs; int64_t n_atoms, n_mol; };
+  struct GraphRecord { bool is_cell, cell_multi, has_z; int nt; int64_t lastE; bool no_ghost_pairs; int64_t n_atoms, n_mol; bool closed_tiles; };
   std::unordered_map<const void*, GraphRecord> graph_rec;
   std::vector<ParamSpec> specs;
   std::map<std::string, std::vector<float>> host;

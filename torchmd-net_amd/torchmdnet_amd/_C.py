@@ -65,6 +65,14 @@ class MessageArgs(C.Structure):
                                           "out2", "slots")] + [("slot_stride", C.c_int64)]
 
 
+class MessageFoldArgs(C.Structure):
+    """tmdnet_message_fold_args (include/tmdnet_amd.h): the reverse tile sweep with the group-product adjoint in its prologue, or
+    the sequence it replaces, tmdnet_debug_message_fold."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "F", "P", "o3", "folded")] + \
+               [(n, C.c_void_p) for n in ("rowptr", "col", "epair", "esign", "counts", "w", "dw", "gCh", "Pn", "Mi", "q", "batch",
+                                          "gMi", "gPn", "slots")] + [("slot_stride", C.c_int64)]
+
+
 # sweeps and kernels of tmdnet_debug_message (TMDNET_MSG_* in the header)
 MSG_OP_FWD, MSG_OP_ADJ, MSG_OP_GD, MSG_OP_DUAL = range(4)
 (MSG_AUTO, MSG_FWD_ROW, MSG_FWD_SPLIT, MSG_FWD_TILE, MSG_ADJ_ROW, MSG_ADJ_SPLIT, MSG_GD_ROW, MSG_GD_SPLIT, MSG_GD_TILE, MSG_DUAL,
@@ -150,6 +158,7 @@ def lib():
     L.tmdnet_debug_gemm_ex.argtypes = [vp, C.POINTER(GemmExArgs), C.POINTER(i32)]
     L.tmdnet_debug_tlin9.argtypes = [vp, i32, i32, i64, i64] + [vp] * 11 + [i32, vp, vp, vp, vp, C.POINTER(i64)]
     L.tmdnet_debug_message.argtypes = [vp, C.POINTER(MessageArgs), C.POINTER(i32), C.POINTER(i32)]
+    L.tmdnet_debug_message_fold.argtypes = [vp, C.POINTER(MessageFoldArgs)]
     L.tmdnet_param_grad_count.argtypes = [vp]
     L.tmdnet_param_grad_entry.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64)]
     L.tmdnet_param_grad_entry.restype = C.c_char_p
