@@ -934,6 +934,71 @@ int tmdnet_min_advance_cell(tmdnet_model* m, void* stream, void* graph_ws, void*
 /* tmdnet_min_status, and host[2] = what was unusable when status is 2: 1 a force sum, 2 the virial, 3 the volume of the box. */
 int tmdnet_min_status_cell(void* stream, void* min_ws, uint64_t host[3]);
 
+/* ---- L-BFGS in the device-resident minimiser (csrc/tn_lbfgs.hip; additive exports, the ABI revision stays 10) -------------------
+ * ASE's LBFGS without line search, one optimiser per molecule (replica): each has its own history and converges at its own step;
+ * the freezing rules are those of the FIRE entries above.  Parameters: memory (pairs held, 1 .. 512), alpha (H0 = 1 / alpha),
+ * max_step, damping.  The box is fixed.  With g = -F, per molecule and step (an atom with fixed[i] != 0 contributes nothing and never
+ * moves):
+ *   1. after a move, the candidate pair s = x - x_prev, y = F_prev - F, each component one rounded fp32 subtraction.  It enters the
+ *      history only when s.y > 0; when the history holds `memory` pairs the oldest leaves.  (ASE stores every pair and can divide by
+ *      zero or step uphill: dropping a pair that violates the curvature condition is the one deviation.  Where every pair passes, the
+ *      sequence is ASE's.)
+ *   2. the two-loop recursion: q = g; newest ... oldest: a_i = (s_i.q) / (y_i.s_i), q -= a_i y_i; z = q / alpha; oldest ... newest:
+ *      b = (y_i.z) / (y_i.s_i), z += s_i (a_i - b); p = -z.  It runs in fp64 on the coefficients of q and z in the basis (s_j, y_j, g),
+ *      given the Gram matrix of that basis: the scalar products are sums of exact fp64 products of widened fp32 values in a fixed
+ *      order (lanes stride the atoms, a wave tree, slices in slice order; no floating-point atomics).
+ *   3. per atom p_i = -(delta_g g_i + sum over the pairs, oldest first, (delta_s s_i + delta_y y_i)) in fp64, rounded to fp32 once
+ *   4. ASE's clamp for this class is per ATOM: longest = max_i |p_i| (fp64, of the rounded p); c = damping (longest >= max_step ?
+ *      max_step / longest : 1), rounded to fp32 once;  x <- x + (c p), one rounded product and one rounded sum
+ *   5. a molecule converges when sqrt(max_i |F_i|^2) < fmax and is then frozen: x is not touched (a branch, not a product with 0).
+ * A minimisation is a fixed sequence of IEEE operations, bit-identical from run to run. */
+/* Bytes of the L-BFGS state `lbfgs_ws`: a 256-byte header (64-bit step counter, sticky status, its cause); per atom x_prev and F_prev
+ * (24 bytes, also what an overflow restores) and the rings S and Y as fp32 [memory + 1][n_atoms][3] (24 (memory + 1) bytes: the extra
+ * slot holds the candidate, so a rejected candidate overwrites nothing); per molecule the pairs held, the ring order, converged_at,
+ * the three Gram blocks SS, SY, YY in fp64 by slot (24 (memory + 1)^2 bytes), the coefficients of the move prepared and the sums
+ * (64 (memory + 1) bytes, and 48 (memory + 1) per slice of at most 1 024 atoms on average).  A caller with thousands of small
+ * molecules picks a smaller memory.  memory < 1 or > 512: TMDNET_ERR_INVALID. */
+int tmdnet_lbfgs_workspace_bytes(int64_t n_atoms, int64_t n_mol, int32_t memory, size_t* bytes);
+/* Where the state lies, for a caller that wants to read it: byte offsets from the workspace pointer rounded up to 256 of
+ * [0] the header, [1] pairs held int32 [n_mol], [2] converged_at int64 [n_mol], [3] the ring order int32 [n_mol, memory + 1] (entries
+ * 0 .. h - 1: the slots held, oldest first; entry h: the spare slot, which holds the last candidate), [4] SS, [5] SY, [6] YY fp64
+ * [n_mol, memory + 1, memory + 1] by slot, [7] the coefficients fp64 [n_mol, 2 (memory + 1) + 1] (s by slot, y by slot, g), [8] the
+ * sums, [9] the slice sums, [10] the slice maxima of |p_i|^2, [11] x_prev, [12] F_prev fp32 [n_atoms, 3], [13] S, [14] Y fp32
+ * [memory + 1, n_atoms, 3], [15] the clamp factor of the last move fp32 [n_mol], [16] the end. */
+int tmdnet_lbfgs_layout(int64_t n_atoms, int64_t n_mol, int32_t memory, int64_t offsets[17]);
+/* Enqueues: step counter = step0, status = 0; the next control empties every molecule's history and sets converged_at = -1.  After a
+ * reset the first launch must be tmdnet_lbfgs_advance(TMDNET_MIN_CLOSE) on the forces at the start geometry: h = 0, p = F / alpha, a
+ * molecule already below fmax converges at step0, and no step is counted.  An OPEN launch before that does nothing. */
+int tmdnet_lbfgs_reset(void* stream, void* lbfgs_ws, uint64_t step0);
+/* Enqueues one phase, with the meaning of TMDNET_MIN_OPEN / MIDDLE / CLOSE above: a replay of K steps is OPEN, then K times
+ * { evaluation at `pos`; MIDDLE, or CLOSE after the last }.  MIDDLE is four launches - the scalar products on a grid (n_mol, slices),
+ * the controller with one wave per molecule, the direction on the same grid, one thread per atom for the move -,
+ * CLOSE the same four with a last one that only accepts the evaluation, OPEN the move alone: 4 K + 1 launches per replay.
+ *   m, graph_ws   as tmdnet_min_advance: the overflow flag and the atom ranges of the evaluation before this launch; both may be NULL
+ *                 (no overflow test, atoms filtered by `batch`).
+ *   pos           [n_atoms, 3], updated in place.   forces   [n_atoms, 3], read only: the evaluation's output (MIDDLE / CLOSE) or the
+ *                 kept forces (OPEN).   energy   [n_mol] or NULL: copied to epot_log_row.
+ *   fixed         [n_atoms] bytes or NULL;  batch   [n_atoms] int64 molecule index in the caller's order, or NULL (one molecule).
+ *   forces_keep   [n_atoms, 3] or NULL: MIDDLE / CLOSE copy `forces` here once the step is accepted.
+ *   direction     [n_atoms, 3], the caller's: p of the move prepared (0 for a fixed atom; not rewritten once a molecule is frozen).
+ *   memory ... fmax   the parameters above; the same memory as in tmdnet_lbfgs_workspace_bytes.
+ *   log rows      each [n_mol] or NULL, of the force set just controlled: epot, fmax = sqrt(fmax2) as fp32, sums [n_mol, 4] fp64 (ff,
+ *                 fmax2, s_c.y_c of the candidate (0: there was none), g.p of the move prepared, from the coefficients), pairs held
+ *                 (int32), accepted (int32: 1 when the candidate entered the history), scale (fp32: the clamp factor c of the move
+ *                 that LED to this force set, which the move kept in the workspace; 0 for the start geometry and for a molecule
+ *                 that was frozen), converged_at (int64, -1: not yet).
+ * Overflow: when the evaluation before a MIDDLE / CLOSE launch overflowed, the controller sets status 1 and pos goes back to x_prev;
+ * the history is intact, because the candidate sat in the spare slot.  Status 2: a sum of a molecule that still moves was not finite;
+ * nothing of that step is written.  Either way every later launch leaves pos, forces_keep, direction, the log rows, the history and
+ * the step counter alone until tmdnet_lbfgs_reset. */
+int tmdnet_lbfgs_advance(tmdnet_model* m, void* stream, void* graph_ws, void* lbfgs_ws, int64_t n_atoms, int64_t n_mol, int32_t phase,
+                         float* pos, const float* forces, const float* energy, const uint8_t* fixed, const int64_t* batch,
+                         float* forces_keep, float* direction, int32_t memory, double alpha, double max_step, double damping, double fmax,
+                         float* epot_log_row, float* fmax_log_row, double* sums_log_row, int32_t* pairs_log_row,
+                         int32_t* accepted_log_row, float* scale_log_row, int64_t* converged_log_row);
+/* tmdnet_min_status on the L-BFGS state, and host[2] = what was unusable when status is 2 (1: a sum). */
+int tmdnet_lbfgs_status(void* stream, void* lbfgs_ws, uint64_t host[3]);
+
 /* ---- Device-resident nudged elastic band (csrc/tn_neb.hip; additive exports, the ABI revision stays 10) ------------------------
  * A minimum-energy path and its saddle point: NEB with the improved tangent (Henkelman and Jonsson, J. Chem. Phys. 113, 9978, 2000)
  * and a climbing image, driven by the FIRE controller above with ONE controller per band.  The launches sit between two

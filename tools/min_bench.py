@@ -15,7 +15,13 @@ and both legs do the full work at every step.  Writes profiles/minimize.json.
 ``--cell``: the cell relaxation instead, on the 192-atom water box with TensorNet and the Equivariant Transformer, K = 10, three legs:
 ``c_cell_K10`` (``capture_minimize(cell=...)``), ``a_eager_cell`` (the loop a caller builds on ``capture(virial=True)``: FIRE and the
 UnitCellFilter algebra as eager torch ops, nothing read back) and ``b_fixed_K10`` (the fixed-box captured loop).  Writes
-profiles/minimize_cell.json."""
+profiles/minimize_cell.json.
+
+``--lbfgs``: captured FIRE against captured L-BFGS (``capture_minimize(lbfgs=...)``) and an eager torch L-BFGS built on ``capture()``
+with nothing read back (the history dot products chained through ``index_add_``), at the three sizes above: (1) evaluations to
+fmax = 0.05 from the same start with ASE's defaults, (2) ms per step with alternating blocks, tiny steps and memory 10, (3) the cost
+of the L-BFGS launches alone (one MIDDLE phase on forces that do not change, so every candidate has y = 0, is rejected, and the
+history stays as it is) with 0, 10 and 100 pairs held.  Writes the ``bench`` section of profiles/minimize_lbfgs.json."""
 import argparse
 import json
 import os
@@ -182,17 +188,174 @@ def main_cell(a):
     print("wrote", a.out)
 
 
+def eager_lbfgs(torch, replay, batch, n_mol, lb, fmax):
+    """-> step(): one L-BFGS step of every molecule as eager torch ops on replay.pos, then one graph launch.  The history is a ring
+    of `memory` slots per molecule; an empty slot has rho = 0 and contributes nothing.  2 x memory dependent per-molecule reductions."""
+    dev = replay.pos.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    m = lb["memory"]
+    _, forces = replay()
+    n = replay.pos.shape[0]
+    S, Y = torch.zeros((m, n, 3), device=dev), torch.zeros((m, n, 3), device=dev)
+    rho = torch.zeros((m, n_mol), **f64)
+    x_prev, f_prev = replay.pos.clone(), forces.clone()
+    s = dict(done=torch.zeros(n_mol, dtype=torch.bool, device=dev), first=True)
+
+    def mol_sum(t):
+        return torch.zeros(n_mol, **f64).index_add_(0, batch, t.sum(1).double())
+
+    def step():
+        nonlocal S, Y, rho
+        fmax2 = torch.zeros(n_mol, dtype=torch.float32, device=dev).index_reduce_(0, batch, (forces * forces).sum(1), "amax")
+        s["done"] |= fmax2.double().sqrt() < fmax
+        if not s["first"]:
+            sc, yc = replay.pos - x_prev, f_prev - forces
+            sy = mol_sum(sc * yc)
+            acc = (sy > 0) & ~s["done"]
+            a_atom = acc[batch][None, :, None]
+            S = torch.where(a_atom, torch.cat([S[1:], sc[None]]), S)
+            Y = torch.where(a_atom, torch.cat([Y[1:], yc[None]]), Y)
+            rho = torch.where(acc[None], torch.cat([rho[1:], (1.0 / sy.clamp_min(1e-300))[None]]), rho)
+        s["first"] = False
+        q = -forces
+        a = []
+        for i in range(m - 1, -1, -1):
+            a.append(rho[i] * mol_sum(S[i] * q))
+            q = q - a[-1].float()[batch][:, None] * Y[i]
+        a.reverse()
+        z = q / lb["alpha"]
+        for i in range(m):
+            b = rho[i] * mol_sum(Y[i] * z)
+            z = z + S[i] * (a[i] - b).float()[batch][:, None]
+        longest = torch.zeros(n_mol, dtype=torch.float32, device=dev).index_reduce_(0, batch, (z * z).sum(1), "amax").double().sqrt()
+        c = lb["damping"] * (lb["max_step"] / longest.clamp_min(1e-300)).clamp_max(1.0) * (~s["done"]).double()
+        x_prev.copy_(replay.pos)
+        f_prev.copy_(forces)
+        replay.pos.addcmul_(c.float()[batch][:, None], -z)
+        replay()
+
+    return step, s
+
+
+def main_lbfgs(a):
+    import torch
+
+    import __graft_entry__ as ge
+
+    ge.build_hip(verbose=False)
+    from torchmdnet_amd import workloads as W
+    from torchmdnet_amd.minimize import MIN_MIDDLE
+    from torchmdnet_amd.models.model import create_model
+
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)
+    K, tiny = 10, 1e-9
+    fire = dict(dt=1e-4, dt_max=1e-3, n_min=5, f_inc=1.1, f_dec=0.5, alpha=0.1, f_alpha=0.99, max_step=1e-4)
+    lb = dict(memory=10, alpha=70.0, max_step=1e-4, damping=1.0)
+    result = {"device": torch.cuda.get_device_name(dev), "model": "TensorNet F=128 L=2 (C2_ARGS), static_shapes, random weights",
+              "steps_per_replay": K, "seconds_per_block": a.seconds, "rounds": a.rounds, "fire": fire, "lbfgs_timing": lb,
+              "max_steps_to_fmax": a.max_steps, "sizes": {}}
+    for name in ("1x64", "256x64", "water192"):
+        torch.manual_seed(0)
+        if name == "water192":
+            model = create_model(dict(W.C2_ARGS, static_shapes=True, max_num_neighbors=128)).to(dev)
+            z, pos, box = W.water_box(n_side=4)
+            batch, box = torch.zeros_like(z), box.to(dev).float().contiguous()
+        else:
+            model = create_model(dict(W.C2_ARGS, static_shapes=True)).to(dev)
+            z, pos, batch = W.synthetic_batch(n_mol=int(name.split("x")[0]), n_atoms=64)
+            box = None
+        z, pos, batch = z.to(dev), pos.to(dev).float().contiguous(), batch.to(dev)
+        n_mol = int(batch.max()) + 1
+        entry = {"n_atoms": int(z.shape[0]), "n_mol": n_mol}
+        # (1) evaluations to fmax = 0.05, ASE's defaults, the same start
+        evals = {}
+        for leg, kw in (("fire", dict()), ("lbfgs", dict(lbfgs={}))):
+            opt = model.capture_minimize(z, pos, batch=batch, box=box, steps_per_replay=1, fmax=0.05, **kw)
+            taken = opt.run(a.max_steps, check_every=10)
+            opt.check()
+            conv = opt.converged_at.cpu()
+            done = conv >= 0
+            evals[leg] = {"steps_run": taken, "converged": int(done.sum()), "of": n_mol,
+                          "median_evaluations_of_converged": float(conv[done].double().median()) if bool(done.any()) else None,
+                          "max_evaluations_of_converged": int(conv[done].max()) if bool(done.any()) else None,
+                          "final_fmax_max": float(opt.fmax[-1].max())}
+            evals[leg]["conv"] = conv
+            del opt
+        both = (evals["fire"]["conv"] >= 0) & (evals["lbfgs"]["conv"] >= 0)
+        evals["converged_in_both"] = int(both.sum())
+        if bool(both.any()):
+            evals["median_evaluations_where_both_converged"] = {k: float(evals[k]["conv"][both].double().median()) for k in ("fire", "lbfgs")}
+            evals["lbfgs_fewer_evaluations"] = evals["median_evaluations_where_both_converged"]["lbfgs"] < \
+                evals["median_evaluations_where_both_converged"]["fire"]
+        for k in ("fire", "lbfgs"):
+            del evals[k]["conv"]
+        entry["evaluations_to_fmax_0.05"] = evals
+        # (2) ms per step: tiny steps, nothing freezes, every leg does the full work at every step
+        replay = model.capture(z, pos, batch, box)
+        replay(pos)
+        eager, state = eager_lbfgs(torch, replay, batch, n_mol, lb, tiny)
+        c_fire = model.capture_minimize(z, pos, batch=batch, box=box, steps_per_replay=K, fmax=tiny, fire=fire)
+        c_lbfgs = model.capture_minimize(z, pos, batch=batch, box=box, steps_per_replay=K, fmax=tiny, lbfgs=lb)
+        legs = {"eager_lbfgs": (eager, 1), "captured_fire_K10": (c_fire, K), "captured_lbfgs_K10": (c_lbfgs, K)}
+        times = {k: [] for k in legs}
+        for _ in range(a.rounds):  # alternating blocks: every round visits every leg once
+            for k, (fn, spc) in legs.items():
+                times[k].append(_block(fn, spc, a.seconds, sync))
+        c_fire.check()
+        c_lbfgs.check()
+        entry["ms_per_step"] = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in times.items()}
+        entry["pairs_held"] = {"captured_lbfgs": [int(c_lbfgs.pairs.min()), int(c_lbfgs.pairs.max())]}
+        entry["captured_lbfgs_not_slower_than_eager"] = entry["ms_per_step"]["captured_lbfgs_K10"]["median"] <= \
+            entry["ms_per_step"]["eager_lbfgs"]["median"]
+        entry["ratio_lbfgs_over_fire"] = entry["ms_per_step"]["captured_lbfgs_K10"]["median"] / entry["ms_per_step"]["captured_fire_K10"]["median"]
+        del replay, c_fire, c_lbfgs, legs, eager
+        # (3) the L-BFGS launches alone with 0, 10 and 100 pairs held
+        hist = {}
+        for h in (0, 10, 100):
+            mem = max(h, 1)
+            opt = model.capture_minimize(z, pos, batch=batch, box=box, steps_per_replay=K, fmax=tiny, lbfgs=dict(lb, memory=mem))
+            if h:
+                opt(-(-3 * h // K))  # fill the history
+            opt.check()
+            energy = torch.zeros(n_mol, device=dev)
+            middle = lambda: opt._advance(MIN_MIDDLE, opt.forces, energy, 0)
+            with torch.cuda.device(dev):
+                v = [_block(middle, 1, min(a.seconds, 0.5), sync) for _ in range(a.rounds)]
+            held = [int(opt.pairs.min()), int(opt.pairs.max())]
+            hist[str(h)] = {"ms_per_middle_phase": statistics.median(v), "min": min(v), "max": max(v), "pairs_held": held,
+                            "note": "eager launches back to back, not a graph replay: an upper bound of the cost inside the graph"}
+            hist[str(h)]["share_of_captured_step"] = hist[str(h)]["ms_per_middle_phase"] / entry["ms_per_step"]["captured_lbfgs_K10"]["median"]
+            del opt, middle
+        entry["lbfgs_launches_alone"] = hist
+        result["sizes"][name] = entry
+        print(name, json.dumps(entry), flush=True)
+    doc = {}
+    if os.path.exists(a.out):
+        with open(a.out) as fh:
+            doc = json.load(fh)
+    doc["bench"] = result
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+    print("wrote", a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--cell", action="store_true", help="the cell relaxation on the water box (profiles/minimize_cell.json)")
+    ap.add_argument("--lbfgs", action="store_true", help="FIRE against L-BFGS, captured and eager (profiles/minimize_lbfgs.json)")
+    ap.add_argument("--max-steps", type=int, default=300, help="--lbfgs: the most evaluations spent on reaching fmax = 0.05")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "minimize_cell.json" if a.cell else "minimize.json")
+        a.out = os.path.join(ROOT, "profiles", "minimize_lbfgs.json" if a.lbfgs else "minimize_cell.json" if a.cell else "minimize.json")
     if a.cell:
         return main_cell(a)
+    if a.lbfgs:
+        return main_lbfgs(a)
 
     import torch
 

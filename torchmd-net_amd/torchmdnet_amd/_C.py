@@ -195,6 +195,12 @@ def lib():
     L.tmdnet_min_reset_cell.argtypes = [vp, vp, i64, i64, u64, f64, f64, vp, vp, vp, vp, vp]
     L.tmdnet_min_advance_cell.argtypes = L.tmdnet_min_advance.argtypes + [vp, vp, vp, vp, vp, vp, C.POINTER(f64), i32, f64, vp, vp, vp]
     L.tmdnet_min_status_cell.argtypes = [vp, vp, C.POINTER(u64)]
+    L.tmdnet_lbfgs_workspace_bytes.argtypes = [i64, i64, i32, C.POINTER(sz)]
+    L.tmdnet_lbfgs_layout.argtypes = [i64, i64, i32, C.POINTER(i64)]
+    L.tmdnet_lbfgs_reset.argtypes = [vp, vp, u64]
+    L.tmdnet_lbfgs_advance.argtypes = [vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, f64, f64, f64, f64,
+                                       vp, vp, vp, vp, vp, vp, vp]
+    L.tmdnet_lbfgs_status.argtypes = [vp, vp, C.POINTER(u64)]
     L.tmdnet_neb_workspace_bytes.argtypes = [i64, i64, i64, C.POINTER(sz)]
     L.tmdnet_neb_reset.argtypes = [vp, vp, u64, f64, f64, i32]
     L.tmdnet_neb_advance.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, f64, i32, f64, f64, f64, f64, f64, f64,

@@ -1573,7 +1573,7 @@ class TorchMD_Net(nn.Module):
     def capture_minimize(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
                          q: Optional[Tensor] = None, num_systems: Optional[int] = None, steps_per_replay: int = 10,
                          fmax: float = 0.05, fire: Optional[dict] = None, fixed: Optional[Tensor] = None, warmup: int = 3,
-                         atom_weights=None, halo_exchange=None, cell: Optional[dict] = None):
+                         lbfgs: Optional[dict] = None, atom_weights=None, halo_exchange=None, cell: Optional[dict] = None):
         """Capture ``steps_per_replay`` steps of a FIRE geometry minimisation into ONE HIP graph (needs ``static_shapes=True``): per
         step the per-atom update, neighbour list + energy + forces, the per-molecule sums and the controller, all as HIP kernels
         between the evaluations (``tmdnet_min_advance``) - no host work between steps.  FIRE as ASE ships it, unit masses, one
@@ -1592,16 +1592,34 @@ class TorchMD_Net(nn.Module):
         for one molecule, [B,3,3] otherwise) and an architecture with a virial (not TensorNet2).  Then ``opt.box`` (the caller's tensor
         when it needed no conversion), ``opt.deform`` [B,3,3], ``opt.stress`` [K,B,3,3] = -W_s / V, ``opt.volume`` [K,B],
         ``opt.reset(pos=, box=)``; ``opt.fmax`` includes the cell rows.  A fixed atom follows the cell affinely.  ``cell=None`` is the
-        fixed-box path, unchanged."""
+        fixed-box path, unchanged.
+        ``lbfgs=dict(memory=100, alpha=70.0, max_step=0.2, damping=1.0)`` (``{}``: these defaults, ASE's) minimises with L-BFGS instead
+        of FIRE (``tmdnet_lbfgs_advance``): ASE's ``LBFGS`` without line search, one history per molecule, the step of every atom
+        clamped to ``max_step``; a pair enters the history only when s.y > 0.  The workspace holds 24 (memory + 1) bytes per atom and
+        24 (memory + 1)^2 per molecule: a batch of thousands of small molecules picks a smaller ``memory``.  Not together with ``fire``
+        (ValueError) or ``cell`` (NotImplementedError).  Returns a ``torchmdnet_amd.lbfgs.DeviceLBFGS``: ``opt(n)``, ``opt.run``,
+        ``opt.pos / forces / direction``, ``opt.epot / fmax / scale / accepted`` [K,B], ``opt.pairs / converged_at`` [B],
+        ``opt.check()``, ``opt.reset(pos=)``.  ``lbfgs=None`` is the FIRE path, unchanged."""
         from torchmdnet_amd.minimize import DeviceMinimizer, parse_cell, parse_fire
 
         if not float(fmax) > 0:
             raise ValueError(f"fmax must be positive, got {fmax}")
+        if lbfgs is not None:  # refused before anything is staged
+            from torchmdnet_amd.lbfgs import DeviceLBFGS, parse_lbfgs
+
+            parse_lbfgs(lbfgs)
+            if fire is not None:
+                raise ValueError("capture_minimize: lbfgs and fire exclude each other (one optimiser drives the minimisation)")
+            if cell is not None:
+                raise NotImplementedError("capture_minimize(lbfgs=...) has no HIP path with cell=...: the cell rows are not part of "
+                                          "the L-BFGS history; relax the cell with FIRE")
         parse_fire(fire)
         if fixed is not None and fixed.numel() != z.shape[0]:
             raise ValueError(f"fixed must have one entry per atom ({z.shape[0]}), got {fixed.numel()}")
         z, batch, box, q, n_mol, _ = self._capture_inputs("capture_minimize", "a minimisation needs", z, pos, batch, box, q, num_systems,
                                                           steps_per_replay, atom_weights, halo_exchange, box_moves=cell is not None)
+        if lbfgs is not None:
+            return DeviceLBFGS(self, z, pos, batch, box, q, n_mol, steps_per_replay, fmax, lbfgs, fixed, warmup)
         if cell is not None:  # refused before anything is allocated or captured
             parse_cell(cell)
             self._refuse_virial()
