@@ -522,6 +522,110 @@ typedef struct tmdnet_message_fold_args {
   int64_t slot_stride;
 } tmdnet_message_fold_args;
 int tmdnet_debug_message_fold(void* stream, const tmdnet_message_fold_args* args);
+/* One launch of a kernel only the TensorNet2 + ScalarPlusWeightedCoulomb path has (csrc/tn_tn2.hip), through its own launcher, on
+ * caller-built operands (additive as well: the ABI revision stays).  No model handle; for unit tests.  The graph is in the
+ * engine's form (tmdnet_debug_message) and is NOT validated: rowptr [N + 1], col / epair per entry (E = rowptr[N] entries), the
+ * adjacency symmetric, the columns of a row ascending, a self edge with pair id P in every row; counts [8] as the engine keeps
+ * them (counts[0] = P; counts[2] != 0: pair overflow, the edge kernels return without writing; counts[3] != 0: `batch` is not
+ * sorted, the per-molecule kernels scan all atoms and filter by `batch` instead of walking mstart[m] .. mend[m]); mstart / mend
+ * [B].  All float operands fp32, DEVICE memory.  With e = (i <- j) an entry of row i, j = col[e], p = epair[e], r the entry
+ * (j <- i), rows [.., 3 F] as [.., 3, F], type(c) = 0 (c = 0) | 1 (c = 1..3) | 2 (c = 4..8):
+ *   EDGE_REVERSE  erev[e] = r, eid[e] = e  [E];  pair_edge[p] = the entry with j < i of pair p  [P]
+ *   CP_FEAT       feat [N, 3, F] = [I ; |A|^2 ; |S|^2] of X [N, 9, F] (I = component 0)
+ *   CP_FEAT_BWD   G [N, 9, F] += (d feat / d X)^T g_feat
+ *   QEQ_FWD       out [N, 2 qd] = [r | f]:  Fu = sum_mol f^2 + 1e-6, dQ = Qmol[m] - sum_mol r (Qmol NULL: 0),
+ *                 charges [N, qd] = r + f^2 / Fu dQ,  FuQ [B, 2 qd] = [Fu | dQ]
+ *   QEQ_BWD       g_out [N, 2 qd] = [g_c - S1 | 2 f dQ / Fu (g_c - S1)],  S1 = sum_mol g_c f^2 / Fu   (Fu, dQ read from FuQ)
+ *   EDGE_PRE1     pre1 [E, F] = Ap[p] + Bt[i] + Cs[j], he1 = silu(pre1), Ce [E] = C[p]   (Ap [P + 1, F], C [P + 1], Bt / Cs [N, F])
+ *   EDGE_GW       g_w[e, k, f] = sum_{type(c) = k} gMi[i, c, f] Pn[j, c, f];  g_pre3 [E, 3 F] = g_w Ce[e] silu'(pre3);
+ *                 slots[a][e] = sum over k and the channels 64 a .. 64 a + 63 of g_w silu(pre3), a < *slot_arrays_out
+ *   EDGE_REDUCE   gB[i] = sum_{e in row i} g_pre1[e], gCs[i] = sum_{e in row i} g_pre1[r]  [N, F];  gAp[p] = g_pre1[e] + g_pre1[r]
+ *                 for the entry with j < i of pair p  [P, F] (rows of no such entry are not written)
+ *   PAIR_GD       gd[p] += sum_f gAp[p, f] dAp[p, f] + dC[p] sum_a (slots[a][e] + slots[a][r]), e = pair_edge[p], p < counts[0], p < P
+ *   COULOMB       ec[i] = sum_j F0 fc(d) g(d) sum_k wq[k] q[i, k] q[j, k] / sum_k wq[k] over the atoms j != i with batch[j] ==
+ *                 batch[i] (batch NULL: one molecule) and, for cut > 0, d < cut;  F0 = 7.199822675975274, fc = 1 - exp(1 -
+ *                 1 / (1 - u^2)), u = min(d / 4.6, 1 - 1e-6);  g = 1 / d (cut <= 0) or 1 / d + k_rf d^2 - c_rf (reaction field of
+ *                 eps_solvent);  d with the triclinic minimum image (z, y, x in turn) of `box` [3, 3] (box_mode 1) or
+ *                 box[batch[i]] (box_mode 2), none for box_mode 0;  an atom with batch outside 0 .. B - 1 gets ec = 0.
+ *                 With g_q != NULL also g_q [N, QC] = d (scale sum ec) / d q and fpos [N, 3] = - d (scale sum ec) / d pos.
+ * *slot_arrays_out (may be NULL) receives the number of slot arrays of EDGE_GW / PAIR_GD for this F (every op writes it when the
+ * call launches); every array has slot_stride >= E floats.
+ * TMDNET_ERR_INVALID, and no launch, outside the kernel's contract: an unknown op, N < 1, B < 1 (QEQ, COULOMB), P < 0, E < 0,
+ * F < 1 (the ops with channels), F > 1024 (EDGE_GW), qd < 1 or qd > 256 (QEQ), QC < 1 or QC > 64 (COULOMB), box_mode outside
+ * 0 .. 2 or without a box, fpos NULL with g_q given, slot_stride < E (EDGE_GW, PAIR_GD), a NULL graph array or operand the op
+ * reads or writes (Qmol, batch of COULOMB, g_q and fpos are optional). */
+#define TMDNET_TN2_EDGE_REVERSE 0
+#define TMDNET_TN2_CP_FEAT 1
+#define TMDNET_TN2_CP_FEAT_BWD 2
+#define TMDNET_TN2_QEQ_FWD 3
+#define TMDNET_TN2_QEQ_BWD 4
+#define TMDNET_TN2_EDGE_PRE1 5
+#define TMDNET_TN2_EDGE_GW 6
+#define TMDNET_TN2_EDGE_REDUCE 7
+#define TMDNET_TN2_PAIR_GD 8
+#define TMDNET_TN2_COULOMB 9
+typedef struct tmdnet_tn2_unit_args {
+  int32_t op;
+  int32_t N, B, F, P, E, qd, QC, box_mode;
+  float cut, eps_solvent, scale;
+  int64_t slot_stride;
+  int32_t* slot_arrays_out; /* HOST, optional */
+  /* graph */
+  const int32_t* rowptr; /* [N + 1] */
+  const int32_t* col;
+  const int32_t* epair;
+  const int32_t* counts; /* [8] */
+  const int32_t* mstart; /* [B] */
+  const int32_t* mend;   /* [B] */
+  const int64_t* batch;  /* [N] */
+  /* EDGE_REVERSE writes these; EDGE_REDUCE reads erev, PAIR_GD reads erev and pair_edge */
+  int32_t* erev;
+  int32_t* eid;
+  int32_t* pair_edge;
+  /* CP_FEAT, CP_FEAT_BWD */
+  const float* X;
+  const float* g_feat;
+  float* feat;
+  float* G;
+  /* QEQ_FWD, QEQ_BWD (FuQ: written by FWD, read by BWD) */
+  const float* out;
+  const float* Qmol;
+  const float* g_c;
+  float* charges; /* QEQ_FWD output; COULOMB input [N, QC] */
+  float* FuQ;
+  float* g_out;
+  /* EDGE_PRE1 (Ce: written here, read by EDGE_GW) */
+  const float* Ap;
+  const float* Bt;
+  const float* Cs;
+  const float* C;
+  float* pre1;
+  float* he1;
+  float* Ce;
+  /* EDGE_GW (slots: written here, read by PAIR_GD) */
+  const float* gMi;
+  const float* Pn;
+  const float* pre3;
+  float* g_pre3;
+  float* slots;
+  /* EDGE_REDUCE (gAp: written here, read by PAIR_GD) */
+  const float* g_pre1;
+  float* gB;
+  float* gCs;
+  float* gAp;
+  /* PAIR_GD */
+  const float* dAp;
+  const float* dC;
+  float* gd;
+  /* COULOMB */
+  const float* pos;
+  const float* box;
+  const float* wq;
+  float* ec;
+  float* g_q;
+  float* fpos;
+} tmdnet_tn2_unit_args;
+int tmdnet_debug_tn2(void* stream, const tmdnet_tn2_unit_args* args);
 
 /* ---- First-order parameter gradients (TensorNet, TensorNet2 and Equivariant Transformer handles; energy-only training).
  * Replaces what autograd does in the reference for `loss(E).backward()` over torchmdnet/models/tensornet.py:543-619, 729-814,

@@ -106,3 +106,110 @@ def test_tn2_oracle_batch_tables_static_and_properties(hip_lib):
         Es, Fs = replay(new)
         Er, Fr = model(zs, new.clone(), bs, q=qs)
         assert rel_err(Es, Er) < 1e-5 and rel_err(Fs, Fr) < 1e-5, step
+
+
+# ---- shapes the whole-model tests above leave out: molecules longer than one 64-lane round of the Coulomb kernel, an unsorted
+# batch, the reaction field through the cell list (kernel by kernel: tests/test_gpu_tn2_unit.py)
+TN2_SMALL = dict(W.TINY_ARGS, model="tensornet2", output_model="ScalarPlusWeightedCoulomb", num_layers=1, q_dim=4, q_weights=[1.0, 0.5],
+                 max_num_neighbors=128)
+RAGGED = (1, 2, 65, 130)
+
+
+def _oracle64(model, args, z, pos, batch, box=None, q=None):
+    """oracle/tn2_torch.py in float64 on the model's weights -> (E [B, 1], F [N, 3], charges [N, (L + 1) q_dim])"""
+    from oracle import tn2_torch as T2
+
+    sd = {k: (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu()) for k, v in model.state_dict().items()}
+    p = pos.double().clone().requires_grad_(True)
+    inter = {}
+    y = T2.energy(sd, T2.hparams_from_args(args), z, p, batch, None if box is None else box.double(), None if q is None else q.double(),
+                  inter=inter)
+    (dy,) = torch.autograd.grad(y.sum(), p)
+    return y.detach(), -dy, inter["charges"].detach()
+
+
+def _ragged_batch():
+    import numpy as np
+
+    zs, ps = zip(*[W.synthetic_molecule(700 + m, n) for m, n in enumerate(RAGGED)])
+    z, pos = torch.from_numpy(np.concatenate(zs)), torch.from_numpy(np.concatenate(ps))
+    batch = torch.repeat_interleave(torch.arange(len(RAGGED)), torch.tensor(RAGGED))
+    return z, pos, batch, torch.tensor([1.0, -1.0, 0.0, 2.0])
+
+
+def _per_molecule(got, ref, batch, what):
+    """every molecule on its own, relative to its own largest reference entry; a molecule whose reference vanishes (the force on
+    a lone atom) relative to the batch's largest"""
+    top = ref.abs().max().item()
+    for m in range(int(batch.max()) + 1):
+        sel = batch == m
+        scale = ref[sel].abs().max().item()
+        err = (got[sel].double() - ref[sel]).abs().max().item() / (scale if scale > 1e-6 * top else top)
+        assert err < REL, (what, m, err)
+
+
+def test_tn2_ragged_all_to_all_batch_and_permuted_batch(hip_lib):
+    """molecules of 1, 2, 65 and 130 atoms with total charges: the Coulomb kernel's second and partial third 64-lane round, the
+    equilibration with more atoms than groups; then the same atoms permuted (an unsorted `batch`: counts[3] = 1, every
+    per-molecule kernel scans all atoms and filters by `batch`)."""
+    from torchmdnet_amd.models.model import create_model
+
+    torch.manual_seed(31)
+    model = create_model(dict(TN2_SMALL), mean=torch.tensor(0.3), std=torch.tensor(1.5)).to("cuda")
+    z, pos, batch, q = _ragged_batch()
+    n, B, QC = z.shape[0], len(RAGGED), 2 * TN2_SMALL["q_dim"]
+    Er, Fr, chr_ = _oracle64(model, TN2_SMALL, z, pos, batch, q=q)
+    E, F = model(z.cuda(), pos.cuda(), batch.cuda(), q=q.cuda())
+    assert model.graph_counts()[2] == 0
+    chg = model.debug_tensor("charges", (n, QC)).cpu()
+    _per_molecule(chg, chr_, batch, "charges")
+    _per_molecule(E.cpu(), Er, torch.arange(B), "energy")
+    _per_molecule(F.cpu(), Fr, batch, "forces")
+    net = torch.zeros(B, 3).index_add(0, batch, F.cpu())
+    assert net.abs().max().item() < 1e-4 * F.abs().max().item() * max(RAGGED)
+    assert abs(chg[batch == 3][:, :4].sum(0) - 2.0).max().item() < 1e-4  # the charges of a molecule add up to its total charge
+    # the same atoms in another order
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(5))
+    assert bool((batch[perm][1:] < batch[perm][:-1]).any())
+    Ep, Fp = model(z[perm].cuda(), pos[perm].cuda(), batch[perm].cuda(), q=q.cuda())
+    assert model.graph_counts()[2] == 1, "the permuted batch was not taken as unsorted"
+    assert rel_err(Ep, E) < 1e-5 and rel_err(Fp.cpu(), F.cpu()[perm]) < 1e-5
+    _per_molecule(Ep.cpu(), Er, torch.arange(B), "energy, permuted")
+    _per_molecule(Fp.cpu(), Fr[perm], batch[perm], "forces, permuted")
+    _per_molecule(model.debug_tensor("charges", (n, QC)).cpu(), chr_[perm], batch[perm], "charges, permuted")
+
+
+@pytest.mark.parametrize("n_mol", [1, 2])
+def test_tn2_reaction_field_through_the_cell_list(hip_lib, n_mol):
+    """coulomb_cutoff = 6.0 on one periodic water box whose neighbours come from the cell list.  4 x 4 x 4 waters are a box of
+    12.4 A: the smallest this generator makes that is at least twice the Coulomb cutoff wide (two cells per axis).  With two
+    molecules sharing the box (every other water) the cell order interleaves them: counts[3] = 1, the Coulomb kernel filters by
+    the internal batch, and its forces come back to the caller's order through the permutation."""
+    from torchmdnet_amd.models.model import create_model
+
+    args = dict(TN2_SMALL, coulomb_cutoff=6.0)
+    torch.manual_seed(37)
+    model = create_model(dict(args)).to("cuda")
+    z, pos, box = W.water_box(n_side=4, seed=3)
+    n = z.shape[0]
+    assert float(box[0, 0]) >= 2 * args["coulomb_cutoff"] and W.water_box(n_side=3)[2][0, 0] < 2 * args["coulomb_cutoff"]
+    if n_mol == 2:  # even waters, then odd waters: `batch` is sorted for the caller, the molecules interleave in space
+        water = torch.arange(n) // 3
+        order = torch.cat([torch.nonzero(water % 2 == 0).flatten(), torch.nonzero(water % 2 == 1).flatten()])
+        z, pos = z[order], pos[order]
+        batch = (torch.arange(n) >= int((water % 2 == 0).sum())).long()
+        q = torch.tensor([1.0, -1.0])
+    else:
+        batch, q = torch.zeros(n, dtype=torch.long), torch.tensor([1.0])
+    Er, Fr, chr_ = _oracle64(model, args, z, pos, batch, box=box, q=q)
+    model.cell_list_min_atoms = 1
+    E, F = model(z.cuda(), pos.cuda(), batch.cuda(), box=box.cuda(), q=q.cuda())
+    assert model.cell_grid(n, n_mol)[3] == 1, "the cell list did not run"
+    assert model.graph_counts()[2] == (1 if n_mol == 2 else 0)
+    _per_molecule(E.cpu(), Er, torch.arange(n_mol), "energy")
+    _per_molecule(F.cpu(), Fr, batch, "forces")
+    # and brute force gives the same
+    model.cell_list_min_atoms = 10 ** 9
+    Eb, Fb = model(z.cuda(), pos.cuda(), batch.cuda(), box=box.cuda(), q=q.cuda())
+    assert model.cell_grid(n, n_mol)[3] == 0
+    assert rel_err(E, Eb) < 1e-5 and rel_err(F, Fb) < 1e-5

@@ -18,6 +18,7 @@ def test_library_loads_and_exports_every_declared_symbol(hip_lib):
     assert len(syms) >= 20 and "tmdnet_energy_forces" in syms and "tmdnet_build_graph" in syms
     assert "tmdnet_debug_message" in syms  # the sweeps' unit-test entry (tests/test_gpu_message.py)
     assert "tmdnet_debug_graph" in syms  # the graph's read-back entry (tests/test_gpu_graph.py)
+    assert "tmdnet_debug_tn2" in syms  # the TensorNet2 kernels' unit-test entry (tests/test_gpu_tn2_unit.py)
     assert hip_lib.tmdnet_version().decode().startswith("tmdnet_amd")
     # parameter table of the C side == state-dict keys of the Python side
     model = create_model(dict(W.TINY_ARGS))

@@ -564,3 +564,64 @@ int tn2_energy_forces(tmdnet_model* m, hipStream_t s, const Graph& g0, void* ws,
   m->tn2_last_chg = t.chg_all;
   return TMDNET_OK;
 }
+
+// ---- one kernel of tn_tn2.hip through its launcher, on the caller's operands (tests/test_gpu_tn2_unit.py)
+extern "C" int tmdnet_debug_tn2(void* stream, const tmdnet_tn2_unit_args* x) {
+  if (!x) return TMDNET_ERR_INVALID;
+  const int N = x->N, B = x->B, F = x->F, P = x->P, qd = x->qd, QC = x->QC;
+  const int64_t E = x->E;
+  if (N < 1 || P < 0 || E < 0) return TMDNET_ERR_INVALID;
+  const bool csr = x->rowptr && x->col && x->epair && x->counts;
+  const bool mols = x->counts && x->mstart && x->mend && B >= 1;
+  bool ok = false;
+  switch (x->op) {
+    case TMDNET_TN2_EDGE_REVERSE: ok = csr && x->erev && x->eid && x->pair_edge; break;
+    case TMDNET_TN2_CP_FEAT: ok = F >= 1 && x->X && x->feat; break;
+    case TMDNET_TN2_CP_FEAT_BWD: ok = F >= 1 && x->X && x->g_feat && x->G; break;
+    case TMDNET_TN2_QEQ_FWD: ok = mols && qd >= 1 && qd <= 256 && x->batch && x->out && x->charges && x->FuQ; break;
+    case TMDNET_TN2_QEQ_BWD: ok = mols && qd >= 1 && qd <= 256 && x->batch && x->out && x->FuQ && x->g_c && x->g_out; break;
+    case TMDNET_TN2_EDGE_PRE1: ok = csr && F >= 1 && x->Ap && x->Bt && x->Cs && x->C && x->pre1 && x->he1 && x->Ce; break;
+    case TMDNET_TN2_EDGE_GW:
+      ok = csr && F >= 1 && F <= 1024 && x->gMi && x->Pn && x->pre3 && x->Ce && x->g_pre3 && x->slots && x->slot_stride >= E;
+      break;
+    case TMDNET_TN2_EDGE_REDUCE: ok = csr && F >= 1 && x->g_pre1 && x->erev && x->gB && x->gCs && x->gAp; break;
+    case TMDNET_TN2_PAIR_GD:
+      ok = x->counts && F >= 1 && x->gAp && x->dAp && x->slots && x->pair_edge && x->erev && x->dC && x->gd && x->slot_stride >= E;
+      break;
+    case TMDNET_TN2_COULOMB:
+      ok = mols && QC >= 1 && QC <= 64 && x->box_mode >= 0 && x->box_mode <= 2 && (x->box_mode == 0 || x->box) && x->pos && x->charges &&
+           x->wq && x->ec && (!x->g_q || x->fpos);
+      break;
+    default: break;
+  }
+  if (!ok) return TMDNET_ERR_INVALID;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (hipGetLastError() != hipSuccess) return TMDNET_ERR_HIP;  // an earlier error: nothing launched, the out-field untouched
+  Graph g{};
+  g.rowptr = const_cast<int*>(x->rowptr);
+  g.col = const_cast<int*>(x->col);
+  g.epair = const_cast<int*>(x->epair);
+  g.counts = const_cast<int*>(x->counts);
+  g.mstart = const_cast<int*>(x->mstart);
+  g.mend = const_cast<int*>(x->mend);
+  const int nslots = F >= 1 ? tn2_gw_slots(F) : 0;
+  if (x->slot_arrays_out) *x->slot_arrays_out = nslots;
+  switch (x->op) {
+    case TMDNET_TN2_EDGE_REVERSE: launch_edge_reverse(g, N, x->erev, x->eid, x->pair_edge, s); break;
+    case TMDNET_TN2_CP_FEAT: launch_cp_feat(x->X, N, F, x->feat, s); break;
+    case TMDNET_TN2_CP_FEAT_BWD: launch_cp_feat_bwd(x->X, x->g_feat, N, F, x->G, s); break;
+    case TMDNET_TN2_QEQ_FWD: launch_qeq_fwd(g, x->out, x->Qmol, x->batch, N, B, qd, x->charges, x->FuQ, s); break;
+    case TMDNET_TN2_QEQ_BWD: launch_qeq_bwd(g, x->out, x->batch, N, B, qd, x->FuQ, x->g_c, x->g_out, s); break;
+    case TMDNET_TN2_EDGE_PRE1: launch_tn2_edge_pre1(g, N, F, x->Ap, x->Bt, x->Cs, x->C, x->pre1, x->he1, x->Ce, s); break;
+    case TMDNET_TN2_EDGE_GW: launch_tn2_edge_gw(g, N, F, x->gMi, x->Pn, x->pre3, x->Ce, x->g_pre3, x->slots, x->slot_stride, s); break;
+    case TMDNET_TN2_EDGE_REDUCE: launch_tn2_edge_reduce(g, N, F, x->g_pre1, x->erev, x->gB, x->gCs, x->gAp, s); break;
+    case TMDNET_TN2_PAIR_GD:
+      launch_tn2_pair_gd(g, P, F, x->gAp, x->dAp, x->slots, nslots, x->slot_stride, x->pair_edge, x->erev, x->dC, x->gd, s);
+      break;
+    default:
+      if (launch_coulomb(g, x->pos, x->batch, x->box, x->box_mode, N, B, QC, x->charges, x->wq, x->cut, x->eps_solvent, x->scale, x->ec,
+                         x->g_q, x->fpos, s))
+        return TMDNET_ERR_INVALID;
+  }
+  return hipGetLastError() == hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
+}

@@ -73,6 +73,20 @@ class MessageFoldArgs(C.Structure):
                                           "gMi", "gPn", "slots")] + [("slot_stride", C.c_int64)]
 
 
+class Tn2UnitArgs(C.Structure):
+    """tmdnet_tn2_unit_args (include/tmdnet_amd.h): one kernel of the TensorNet2 path on caller-built operands, tmdnet_debug_tn2."""
+    _fields_ = [(n, C.c_int32) for n in ("op", "N", "B", "F", "P", "E", "qd", "QC", "box_mode")] + \
+               [(n, C.c_float) for n in ("cut", "eps_solvent", "scale")] + [("slot_stride", C.c_int64)] + \
+               [("slot_arrays_out", C.POINTER(C.c_int32))] + \
+               [(n, C.c_void_p) for n in ("rowptr", "col", "epair", "counts", "mstart", "mend", "batch", "erev", "eid", "pair_edge",
+                                          "X", "g_feat", "feat", "G", "out", "Qmol", "g_c", "charges", "FuQ", "g_out",
+                                          "Ap", "Bt", "Cs", "C", "pre1", "he1", "Ce", "gMi", "Pn", "pre3", "g_pre3", "slots",
+                                          "g_pre1", "gB", "gCs", "gAp", "dAp", "dC", "gd", "pos", "box", "wq", "ec", "g_q", "fpos")]
+
+
+# ops of tmdnet_debug_tn2 (TMDNET_TN2_* in the header)
+(TN2_EDGE_REVERSE, TN2_CP_FEAT, TN2_CP_FEAT_BWD, TN2_QEQ_FWD, TN2_QEQ_BWD, TN2_EDGE_PRE1, TN2_EDGE_GW, TN2_EDGE_REDUCE, TN2_PAIR_GD,
+ TN2_COULOMB) = range(10)
 # sweeps and kernels of tmdnet_debug_message (TMDNET_MSG_* in the header)
 MSG_OP_FWD, MSG_OP_ADJ, MSG_OP_GD, MSG_OP_DUAL = range(4)
 (MSG_AUTO, MSG_FWD_ROW, MSG_FWD_SPLIT, MSG_FWD_TILE, MSG_ADJ_ROW, MSG_ADJ_SPLIT, MSG_GD_ROW, MSG_GD_SPLIT, MSG_GD_TILE, MSG_DUAL,
@@ -159,6 +173,7 @@ def lib():
     L.tmdnet_debug_tlin9.argtypes = [vp, i32, i32, i64, i64] + [vp] * 11 + [i32, vp, vp, vp, vp, C.POINTER(i64)]
     L.tmdnet_debug_message.argtypes = [vp, C.POINTER(MessageArgs), C.POINTER(i32), C.POINTER(i32)]
     L.tmdnet_debug_message_fold.argtypes = [vp, C.POINTER(MessageFoldArgs)]
+    L.tmdnet_debug_tn2.argtypes = [vp, C.POINTER(Tn2UnitArgs)]
     L.tmdnet_param_grad_count.argtypes = [vp]
     L.tmdnet_param_grad_entry.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64)]
     L.tmdnet_param_grad_entry.restype = C.c_char_p
