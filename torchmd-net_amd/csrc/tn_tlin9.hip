@@ -9,7 +9,9 @@
 // Here a block (8 waves, one per CU, persistent over its tiles) owns 32 ATOMS x all 9 components x 128 output channels:
 //   * staging (prologue): a thread holds the nine components of (atom, 2 input channels) of a DOUBLE chunk (32 channels = one
 //     128-byte line per row), so the per-(atom, channel) algebra runs in registers while the pair is split into its three bf16
-//     planes on the way to LDS; two register slots keep the next two double chunks in flight;
+//     planes on the way to LDS; two register slots keep the next two double chunks in flight (the second operand of the update
+//     adjoint has ONE slot, asked for a double chunk behind its partner: with two it was the one instance over 256 registers,
+//     76 bytes of scratch per lane reloaded inside the loops, 74 -> 60 us; tests/test_tlin9_build.py pins the report);
 //   * product: exact 3-way bf16 split, six MFMA products per fp32 product (tn_gemm_sb.hip); waves 0-3 own components 0-3,
 //     waves 4-7 components 4-8, each for one 32-column block: an accumulator row block = the 32 atoms of one component, so the
 //     nine components of (atom, column) sit at the same lane and element of nine accumulators.  Weights never touch LDS:
@@ -18,8 +20,11 @@
 //   * the two wave classes run the steps of a double chunk in rotated order (stage - multiply / multiply - stage), as two
 //     separate loops: the staging of one wave of a SIMD runs beside the products of the other;
 //   * epilogue: 8 atoms at a time go through LDS (aliasing two free chunk buffers) into (atom, 2 columns)-per-lane order - nine
-//     components in one lane, a wave = one atom = 512 contiguous bytes per component - the extra operands of the fused neighbour
-//     were requested before the dump.
+//     components in one lane, a wave = one atom = 512 contiguous bytes per component - ALL extra operands of the fused
+//     neighbour were requested before the dump, the gate adjoint's too (inside the pass they cost 4 of 104 us).  Asking for
+//     group G + 1's operands during group G's pass, into the accumulator registers the dump frees, fits (<= 255 registers, no
+//     scratch) and gains nothing: +-1 us on four variants, +2.5 us on the update; at 4.1-4.8 TB/s the operand-carrying
+//     variants stand at the kernel's memory-only rate, not on a round trip (profiles/tlin9_prefetch_notes.md).
 // Measured (C2, 9 x 16384 x 128 x 128, profiles/r04_notes.md): 50 us for the plain product (the grouped GEMM: 47), 70 us with the
 // update in the epilogue (was 47 + 43), 73 us with the normalisation adjoint (was 47 + 74).  What the kernel is NOT: a
 // streaming kernel - memory-only it runs at 5.1 TB/s, products-only in 23 us, together in 50: see the notes for the timeline.
@@ -123,10 +128,15 @@ __global__ __launch_bounds__(512, 2) void k_tlin9(Tl9Args a, int tiles_m, int ti
 
   // ---------------------------------------------------------------- staging: global -> register ring -> (algebra, split) -> LDS
   f2v sr[2][9];
-  f2v sr2[2][9];  // second operand (TL9_PRO_UPDBWD only; dead otherwise)
+  // second operand (TL9_PRO_UPDBWD only; dead otherwise): ONE slot, requested one double chunk later than its partner in sr.
+  // vmcnt order keeps the input prefetch one double chunk deep whatever the ring size (above), so the later request loses
+  // nothing, and a second slot (18 registers) was what pushed this variant over 256 registers into scratch
+  f2v sr2[9];
   float s_kap[2];
   auto load_dbl = [&](auto S_, int dd) __attribute__((always_inline)) {
     constexpr int S = decltype(S_)::value;
+    int d2 = dd > 0 ? dd - 1 : 0;  // second operand: of the double chunk before dd (the start-up asks for chunk 0 twice)
+    d2 = d2 < ndt ? d2 : ndt - 1;
     dd = dd < ndt ? dd : ndt - 1;  // past the end: re-request the last one (no branch around loads)
     const int ts = dd / nd, kd = dd - ts * nd;
     int m0, n0;
@@ -136,13 +146,19 @@ __global__ __launch_bounds__(512, 2) void k_tlin9(Tl9Args a, int tiles_m, int ti
     if (PRO == TL9_PRO_UPDBWD) s_kap[S] = a.kap ? a.kap[n] : 1.0f;
     const unsigned voff = (unsigned)((n - m0) * F9 + skp * 2);
     const float* p = a.A + (int64_t)m0 * F9 + kd * 32;  // wave-uniform
+    if (PRO == TL9_PRO_UPDBWD) {  // its slot was emptied by the stage_dbl just before this call; the next stage_dbl consumes it
+      const int ts2 = d2 / nd, kd2 = d2 - ts2 * nd;
+      int m2, n2_;
+      tile_of(ts2, m2, n2_);
+      int r2 = m2 + sa;
+      if (r2 >= N) r2 = N - 1;
+      const unsigned voff2 = (unsigned)((r2 - m2) * F9 + skp * 2);
+      const float* p2 = a.A2 + (int64_t)m2 * F9 + kd2 * 32;
+#pragma unroll
+      for (int c = 0; c < 9; ++c) sr2[c] = ldu2(p2 + c * F, voff2);
+    }
 #pragma unroll
     for (int c = 0; c < 9; ++c) sr[S][c] = ldu2(p + c * F, voff);
-    if (PRO == TL9_PRO_UPDBWD) {
-      const float* p2 = a.A2 + (int64_t)m0 * F9 + kd * 32;
-#pragma unroll
-      for (int c = 0; c < 9; ++c) sr2[S][c] = ldu2(p2 + c * F, voff);
-    }
   };
   // lanes with skp < 8 hold channels of the double chunk's first chunk, the others of its second: two of the four buffers
   const int st_off = (skp >> 3) * T9_STAGE + (skp & 3) * 4;
@@ -169,7 +185,7 @@ __global__ __launch_bounds__(512, 2) void k_tlin9(Tl9Args a, int tiles_m, int ti
 #pragma unroll
         for (int c = 0; c < 9; ++c) {
           gg[c] = sr[S][c][j];
-          d[c] = sr2[S][c][j];
+          d[c] = sr2[c][j];
         }
         t9_update_bwd(gg, d, s_kap[S], o);
 #pragma unroll
@@ -237,6 +253,7 @@ __global__ __launch_bounds__(512, 2) void k_tlin9(Tl9Args a, int tiles_m, int ti
   const unsigned cp2 = 2 * (tid & 63);
   const int F3 = 3 * F;
   f2v x0[9], x1[(EPI == TL9_EPI_NORMBWD || EPI == TL9_EPI_NORMBWD_GATE) ? 9 : 1], gt[3];
+  f2v ux[EPI == TL9_EPI_NORMBWD_GATE ? 9 : 1], ga2[EPI == TL9_EPI_NORMBWD_GATE ? 3 : 1];  // gate adjoint: UX, a2
   auto epi_loads = [&](int n, int n0) __attribute__((always_inline)) {  // operands of the fused neighbour for (atom n, 2 columns)
     const bool ok = n < N;
     const int64_t rowu = (int64_t)(ok ? n : 0) * F9 + n0;  // wave-uniform (a wave = one atom); lanes add cp2
@@ -254,6 +271,18 @@ __global__ __launch_bounds__(512, 2) void k_tlin9(Tl9Args a, int tiles_m, int ti
       for (int k = 0; k < 3; ++k) gt[k] = ldu2(a.e3 + (int64_t)(ok ? n : 0) * F3 + n0 + k * F, cp2);
     }
     if (EPI == TL9_EPI_EMBBWD) gt[0] = ldu2(a.e1 + (int64_t)(ok ? n : 0) * F + n0, cp2);
+    if (EPI == TL9_EPI_NORMBWD_GATE) {
+      // the gate adjoint's operands go out with the others, in their own registers: requested inside the pass (the gates and UX
+      // behind the normalisation adjoint, UX into the recycled x0, a2 in the last loop) they were two more round trips per group
+      // with nothing left to cover them
+      const int64_t r3 = (int64_t)(ok ? n : 0) * F3 + n0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) gt[k] = ldu2(a.e3 + r3 + k * F, cp2);
+#pragma unroll
+      for (int c = 0; c < 9; ++c) ux[c] = ldu2(a.e2 + rowu + c * F, cp2);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) ga2[k] = ldu2(a.e4 + r3 + k * F, cp2);
+    }
   };
   auto epi_pass = [&](int n, int n0, int ea) __attribute__((always_inline)) {  // the nine components of (atom n, 2 columns): LDS -> algebra -> stores
     const bool ok = n < N;
@@ -330,17 +359,13 @@ __global__ __launch_bounds__(512, 2) void k_tlin9(Tl9Args a, int tiles_m, int ti
         const int64_t r3 = (int64_t)(ok ? n : 0) * F3 + n0;
         f2v ga[3] = {(f2v)(0.f), (f2v)(0.f), (f2v)(0.f)};
 #pragma unroll
-        for (int k = 0; k < 3; ++k) gt[k] = ldu2(a.e3 + r3 + k * F, cp2);
-#pragma unroll
-        for (int c = 0; c < 9; ++c) x0[c] = ldu2(a.e2 + rowu + c * F, cp2);  // UX
-#pragma unroll
         for (int c = 0; c < 9; ++c) {
-          ga[type_of(c)] += v[c] * x0[c];
+          ga[type_of(c)] += v[c] * ux[c];
           if (ok) stu2(a.C + rowu + c * F, cp2, v[c] * gt[type_of(c)]);
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-          const f2v a2 = ldu2(a.e4 + r3 + k * F, cp2);
+          const f2v a2 = ga2[k];
           f2v o;
 #pragma unroll
           for (int j = 0; j < 2; ++j) o[j] = ga[k][j] * silu_grad(a2[j]);
