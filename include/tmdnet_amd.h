@@ -735,8 +735,9 @@ int tmdnet_md_advance(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws
 /* host[0] = steps completed (the device counter), host[1] = status (1: an evaluation overflowed; the state is that of step
  * host[0].  2: a barostat move was unusable, see tmdnet_md_barostat; step host[0] is complete but for that move.  3: a constraint
  * cluster did not converge, see tmdnet_md_advance_constrained.  4: a walker's collective variable, its gradient or its bias was not
- * finite, see tmdnet_md_bias; the state is half a step ahead of step host[0]).  Synchronises the stream.  Returns
- * TMDNET_ERR_OVERFLOW for status 1 and TMDNET_ERR_STATE for status 2, 3 and 4. */
+ * finite, see tmdnet_md_bias; the state is half a step ahead of step host[0].  5: a move of a global thermostat was unusable, see
+ * tmdnet_md_thermostat; step host[0] is complete but for that move).  Synchronises the stream.  Returns TMDNET_ERR_OVERFLOW for
+ * status 1 and TMDNET_ERR_STATE for status 2, 3 and 4, and for status 5 likewise. */
 int tmdnet_md_status(void* stream, void* md_ws, uint64_t host[2]);
 
 /* ---- Barostat of the device-resident MD loop (csrc/tn_md.hip; additive exports, the ABI revision stays 10) --------------------
@@ -817,6 +818,54 @@ int tmdnet_md_exchange(tmdnet_model* m, void* stream, void* graph_ws, void* md_w
                        int32_t ladder, int64_t exchange_every, float* vel, float* sigma, const float* epot_row, const double* beta,
                        const float* sigma_table, const float* scale_up, const float* scale_down, uint64_t seed, int32_t* slot,
                        int32_t* holder, int32_t* slot_log_row, uint8_t* accept_log_row, int64_t* counters);
+
+/* ---- Global thermostats of the device-resident MD loop (csrc/tn_md_thermo.hip; additive exports, the ABI revision stays 10) -----
+ * One thermostat per molecule (replica) that acts on the molecule's kinetic energy through ONE scale factor alpha per step and so
+ * leaves the relative motion of the atoms alone.  After the closing half of a step (tmdnet_md_advance with TMDNET_MD_CLOSE and no
+ * Langevin thermostat), per molecule m, in fp64 in the order written in csrc/tn_md_thermo_math.h, with K = ekin_row[m] / force_scale
+ * and N = ndof[m]:
+ *   TMDNET_THERMOSTAT_CSVR   stochastic velocity rescaling (Bussi, Donadio, Parrinello, J. Chem. Phys. 126, 014101, 2007):
+ *       c = exp(-dt / tau), r = (N kT / 2) / (N K), alpha^2 = (sqrt(c) + R1 sqrt(r (1 - c)))^2 + r (1 - c) S
+ *     R1 a standard normal and S chi-square with N - 1 degrees of freedom (2 Gamma((N - 1) / 2) for N - 1 even, 2 Gamma((N - 2) / 2)
+ *     + R2^2 for N - 1 odd; the gamma deviate is Marsaglia and Tsang's, at most 64 attempts).  reservoir -= (alpha^2 - 1) K.
+ *   TMDNET_THERMOSTAT_NHC    a Nose-Hoover chain of `chain` thermostats (Martyna, Klein, Tuckerman, J. Chem. Phys. 97, 2635, 1992)
+ *     with Q_1 = N kT tau^2 and Q_j = kT tau^2, propagated by `substeps` applications of the chain routine of Martyna, Tuckerman,
+ *     Tobias and Klein (Mol. Phys. 87, 1117, 1996) with h = dt / substeps; alpha is the accumulated scale.
+ *     reservoir = sum_j Q_j v_j^2 / 2 + N kT xi_1 + kT sum_{j >= 2} xi_j.
+ * alpha is rounded to fp32 once; then v <- v alpha for the atoms of m, ONE rounded fp32 product per component under the rounding
+ * contract above.  An atom of infinite mass (hk = 0) carries no kinetic energy and keeps its velocity bit for bit.  A molecule with
+ * ndof <= 0 or K = 0 is not scaled: alpha = 1, no random number, state untouched.  kT in the unit of E, tau in the unit of dt.
+ * Noise: Philox4x32-10, key = `seed`, counter = (step low, step high, molecule, 3 + 256 draw) with `step` the value the O step of
+ * this MD step would use; draw 0 gives R1 = xi_x and R2 = xi_y of the Box-Muller map above, draw j >= 1 is attempt j of the gamma
+ * deviate (x = xi_x, u from word 2).  Counter word 3 keeps the stream apart from the atoms' (0), the barostat's (1) and the
+ * exchange's (2).
+ * Enqueues two launches: one block that computes every molecule's move and, when all are usable, writes the factors, the reservoir,
+ * the chain and the log rows; then one thread per atom that scales v and, with open_next != 0, saves the scaled state and runs B, A
+ * of the next step on it (what TMDNET_MD_OPEN does).  A captured step with a global thermostat is therefore
+ *     evaluation;  tmdnet_md_advance(TMDNET_MD_CLOSE);  tmdnet_md_thermostat(open_next = another step follows)
+ * after one TMDNET_MD_OPEN at the start of the replay.  With constraints open_next = 0 and tmdnet_md_advance_constrained(OPEN)
+ * follows: a uniform scaling of a molecule's velocities keeps them on the constraints.
+ *   m, graph_ws   as in tmdnet_md_barostat.  graph_ws == NULL (m may be NULL): no overflow test.
+ *   thermo_ws     tmdnet_md_thermostat_workspace_bytes(n_mol, chain) bytes, zeroed by the caller before the first move and to
+ *                 reset the thermostat; after aligning the pointer up to 256 bytes: alpha fp32 [n_mol], then (each part rounded up
+ *                 to 256 bytes) the reservoir fp64 [n_mol] and the chain fp64 [n_mol, 2, chain] = (xi | v_xi).
+ *   forces, dt    read with open_next only;  hk [n_atoms] always (it tells the atoms of infinite mass);  pos   with open_next only.
+ *   batch         [n_atoms] int64 or NULL (one molecule).   ekin_row   [n_mol], the ekin_log_row of the CLOSE launch.
+ *   ndof          [n_mol] int32: the degrees of freedom of every molecule.
+ *   chain, substeps   NHC only (CSVR: ignored, its workspace is sized with chain = 0).
+ *   scale_log_row [n_mol] fp32 or NULL: alpha.   reservoir_log_row [n_mol] fp64 or NULL: the reservoir after the move, unit of E.
+ * A move is unusable when K, alpha or a chain value is not finite, alpha <= 0, or the gamma deviate used up its attempts: the status
+ * word becomes 5, no factor, reservoir, chain value or log row is written for ANY molecule, vel keeps its bits, and every later
+ * launch returns at once until tmdnet_md_reset.
+ * TMDNET_ERR_INVALID: an unknown kind, tau <= 0, kT <= 0, force_scale <= 0, NHC with chain outside 1..8 or substeps < 1, or a NULL
+ * md_ws / thermo_ws / vel / hk / ekin_row / ndof (with open_next: pos / forces). */
+#define TMDNET_THERMOSTAT_CSVR 0
+#define TMDNET_THERMOSTAT_NHC 1
+int tmdnet_md_thermostat_workspace_bytes(int64_t n_mol, int32_t chain, size_t* bytes);
+int tmdnet_md_thermostat(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, void* thermo_ws, int64_t n_atoms, int64_t n_mol,
+                         int32_t kind, int32_t open_next, float* pos, float* vel, const float* forces, const float* hk, float dt,
+                         const int64_t* batch, const float* ekin_row, const int32_t* ndof, double kT, double tau, int32_t chain,
+                         int32_t substeps, double force_scale, uint64_t seed, float* scale_log_row, double* reservoir_log_row);
 
 /* ---- Collective-variable restraints and metadynamics of the device-resident MD loop (csrc/tn_bias.hip; additive exports, the ABI
  * revision stays 10) ------------------------------------------------------------------------------------------------------------

@@ -58,7 +58,18 @@ one walker and 256 walkers in groups of 4):
       Verlet and a distance restraint (plus 1 000 one-dimensional hills per group) as eager torch ops, nothing read back.
 
 Same alternating blocks, median and min / max; records the ratios to (a) and the slope of the cost per step in the number of hills.
-Writes the key ``timing`` of profiles/md_bias.json (the other keys of that file are kept)."""
+Writes the key ``timing`` of profiles/md_bias.json (the other keys of that file are kept).
+
+``--global``: the global thermostats, K = 10, one system of 64, 256 and 1 024 atoms as above:
+
+  (a) ``a_eager_csvr``: the loop a caller builds on ``capture()`` - one graph launch per step, velocity Verlet, the kinetic energy
+      by a torch reduction and the stochastic-velocity-rescaling factor from torch's own normal and gamma deviates, all on the device,
+      nothing read back;
+  (b) ``b_K10_langevin``: ``capture_md`` with the Langevin thermostat (the yardstick), ``b_K10_csvr`` and ``b_K10_nose_hoover``:
+      ``capture_md_global`` at the same kT.
+
+Same alternating blocks, median and min / max; records the cost of both global thermostats over the Langevin loop and CSVR against
+the eager loop per size.  Writes profiles/md_global.json."""
 import argparse
 import json
 import os
@@ -537,6 +548,81 @@ def bias_main(a):
     print("wrote", out)
 
 
+def global_main(a):
+    import math
+
+    import torch
+
+    import __graft_entry__ as ge
+
+    ge.build_hip(verbose=False)
+    from torchmdnet_amd import workloads as W
+    from torchmdnet_amd.models.model import create_model
+
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)
+    dt, mass_amu, fs, kT, K = 1e-3, 12.0, 9.648533e-3, 0.0259, 10
+    tau = 1000.0 * dt
+    result = {"device": torch.cuda.get_device_name(dev), "model": "TensorNet F=128 L=2 (C2_ARGS), static_shapes", "steps_per_replay": K,
+              "seconds_per_block": a.seconds, "rounds": a.rounds, "dt_for_ns_per_day_fs": 1.0, "kT": kT, "tau": tau, "sizes": {}}
+    for n in a.sizes:
+        torch.manual_seed(0)
+        model = create_model(dict(W.C2_ARGS, static_shapes=True, max_num_neighbors=64 if n <= 64 else 128)).to(dev)
+        z, pos, batch = W.synthetic_batch(n_mol=1, n_atoms=n)
+        z, pos, batch = z.to(dev), pos.to(dev), batch.to(dev)
+        vel0 = torch.zeros_like(pos)
+        masses = torch.full((n,), mass_amu, device=dev)
+        hk = 0.5 * dt * fs / mass_amu
+        ndof = 3 * n
+        c = math.exp(-dt / tau)
+        shape = torch.full((), 0.5 * (ndof - 1), device=dev)  # S = 2 Gamma((N - 1) / 2): chi-square with N - 1 degrees of freedom
+
+        replay = model.capture(z, pos, batch)
+        vel = vel0.clone()
+        _, forces = replay(pos)
+
+        def a_eager_csvr():
+            vel.add_(forces, alpha=hk)
+            replay.pos.add_(vel, alpha=dt)
+            replay()
+            vel.add_(forces, alpha=hk)
+            ke = (vel * vel).sum() * (0.5 * mass_amu / fs)
+            g = (0.5 * kT * (1.0 - c)) / ke
+            r1 = torch.randn((), device=dev)
+            a2 = (math.sqrt(c) + r1 * torch.sqrt(g)) ** 2 + g * 2.0 * torch._standard_gamma(shape)
+            vel.mul_(torch.sqrt(a2))
+
+        legs = {"a_eager_csvr": (a_eager_csvr, 1)}
+        mds = [model.capture_md(z, pos, vel0, masses, dt, batch=batch, steps_per_replay=K, force_scale=fs,
+                                thermostat=dict(friction=0.01, kT=kT, seed=1))]
+        legs["b_K10_langevin"] = (mds[0], K)
+        for leg, th in (("b_K10_csvr", dict(kind="csvr", kT=kT, tau=tau, seed=1)), ("b_K10_nose_hoover", dict(kind="nose-hoover", kT=kT, tau=tau))):
+            md = model.capture_md_global(z, pos, vel0, masses, dt, batch=batch, steps_per_replay=K, force_scale=fs, thermostat=th)
+            mds.append(md)
+            legs[leg] = (md, K)
+        times = {k: [] for k in legs}
+        for _ in range(a.rounds):  # alternating blocks: every round visits every leg once
+            for k, (fn, spc) in legs.items():
+                times[k].append(_block(fn, spc, a.seconds, sync))
+        for md in mds:
+            md.check()  # raises if a trajectory overflowed or a move was unusable: its timings would be of a frozen loop
+        assert bool(torch.isfinite(vel).all())
+        entry = _summary(times)
+        entry["n_atoms"] = n
+        base = entry["b_K10_langevin"]["ms_per_step"]
+        entry["ratio_over_langevin"] = {k: entry[k]["ms_per_step"] / base for k in ("b_K10_csvr", "b_K10_nose_hoover")}
+        entry["ratio_csvr_over_eager"] = entry["b_K10_csvr"]["ms_per_step"] / entry["a_eager_csvr"]["ms_per_step"]
+        entry["b_K10_csvr_not_slower_than_eager"] = entry["b_K10_csvr"]["ms_per_step"] <= entry["a_eager_csvr"]["ms_per_step"]
+        result["sizes"][str(n)] = entry
+        print(n, json.dumps(entry), flush=True)
+        del replay, mds, legs
+    out = a.out if a.out else os.path.join(ROOT, "profiles", "md_global.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=2.0)
@@ -546,6 +632,7 @@ def main():
     ap.add_argument("--constraints", action="store_true", help="time the constrained loop instead (profiles/md_constraints.json)")
     ap.add_argument("--remd", action="store_true", help="time temperature replica exchange instead (key 'timing' of profiles/md_remd.json)")
     ap.add_argument("--bias", action="store_true", help="time restraints and metadynamics instead (key 'timing' of profiles/md_bias.json)")
+    ap.add_argument("--global", dest="global_", action="store_true", help="time the global thermostats instead (profiles/md_global.json)")
     ap.add_argument("--block-steps", type=int, default=100, help="--constraints: steps of one timed block (a multiple of 10)")
     ap.add_argument("--out", default=None, help="default: profiles/md_loop.json, with --npt profiles/md_npt.json, with --constraints "
                                                 "profiles/md_constraints.json")
@@ -558,6 +645,8 @@ def main():
         return remd_main(a)
     if a.bias:
         return bias_main(a)
+    if a.global_:
+        return global_main(a)
     a.out = a.out or os.path.join(ROOT, "profiles", "md_loop.json")
 
     import torch

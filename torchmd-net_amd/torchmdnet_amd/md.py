@@ -11,6 +11,9 @@ coupled constraints, still one launch between two evaluations.  ``TorchMD_Net.ca
 replicas of one system and exchanges their temperatures inside the graph (csrc/tn_remd.hip, ``tmdnet_md_exchange``).
 ``TorchMD_Net.capture_md_biased`` (``DeviceBiasedMD``) adds collective-variable restraints and metadynamics: one launch per step
 (csrc/tn_bias.hip, ``tmdnet_md_bias``) adds the bias force to the evaluation's forces before the integrator reads them.
+``TorchMD_Net.capture_md_global`` (``DeviceGlobalMD``) replaces the Langevin O step by a global thermostat per molecule - stochastic
+velocity rescaling or a Nose-Hoover chain - that scales all velocities of a molecule by one factor (csrc/tn_md_thermo.hip,
+``tmdnet_md_thermostat``: two launches between the closing and the opening half of a step).
 The capture sequence, the stale-graph guard, ``md(n)``, the status read-back and the skeleton of ``reset`` are those of every
 captured loop: ``torchmdnet_amd.captured``."""
 import ctypes as C
@@ -382,8 +385,9 @@ class DeviceMD(CapturedLoop):
         value that is not finite): that cluster is back at its saved state, the whole state is frozen and finite but is not a point
         of the trajectory - other clusters may be half a step ahead -, and ``reset(pos=, vel=)`` is required.  Raises a RuntimeError
         naming the bias (``DeviceBiasedMD``) when a walker's collective variable, its gradient or its bias was not finite: the state
-        is frozen, finite and half a step ahead of the last completed step, and ``reset(pos=, vel=)`` is required.  Returns the step
-        counter."""
+        is frozen, finite and half a step ahead of the last completed step, and ``reset(pos=, vel=)`` is required.  Raises a
+        RuntimeError naming the thermostat (``DeviceGlobalMD``) when a move of the global thermostat was unusable (a kinetic energy
+        that is not finite): the state is frozen at the closed step, before that move.  Returns the step counter."""
         rc, (step, status) = self._status(_C.lib().tmdnet_md_status, 2)
         if rc == _C.ERR_OVERFLOW:
             raise self._overflow(step)
@@ -401,6 +405,11 @@ class DeviceMD(CapturedLoop):
             raise RuntimeError(f"bias: a collective variable, its gradient or the bias of a walker was not finite after step {step} "
                                "(coincident atoms, a collinear angle or torsion, or a NaN position); the MD state is frozen and finite "
                                "but half a step ahead of that step: reset(pos=, vel=) is required")
+        if status == 5:
+            kind = (getattr(self, "global_thermostat", None) or {}).get("kind", "global")
+            raise RuntimeError(f"thermostat: the {kind} move after step {step} was unusable (a kinetic energy, a scale factor or a "
+                               "chain value that is not finite, or a scale factor that is not positive); the MD state is frozen "
+                               "before that move")
         if rc != _C.OK:
             raise RuntimeError(f"tmdnet_md_status failed (code {rc})")
         return step
@@ -828,3 +837,141 @@ class DeviceBiasedMD(DeviceMD):
             store[:, bs["dm"], :base] = new[1].to(store.device)
         self._hill_base = base
         return super().reset(pos, vel, step)
+
+
+# ---- global thermostats: stochastic velocity rescaling and Nose-Hoover chains (csrc/tn_md_thermo.hip) ---------------------------------
+THERMOSTAT_KINDS = {"csvr": 0, "nose-hoover": 1}  # name -> kind of tmdnet_md_thermostat
+MAX_CHAIN = 8
+_GLOBAL_KEYS = {"csvr": ("kind", "kT", "tau", "seed", "ndof"), "nose-hoover": ("kind", "kT", "tau", "chain", "substeps", "ndof")}
+
+
+def parse_global_thermostat(thermostat):
+    """``thermostat=dict(kind="csvr", kT=, tau=, seed=0, ndof=None)`` or ``dict(kind="nose-hoover", kT=, tau=, chain=3, substeps=2,
+    ndof=None)`` -> the same with every key present (``chain`` = 0 for CSVR).  ``ndof``: None, an int, or one int per molecule.
+    Raises ValueError."""
+    if thermostat is None:
+        raise ValueError("capture_md_global needs thermostat=dict(kind='csvr' | 'nose-hoover', kT=, tau=, ...); without one use capture_md")
+    t = dict(thermostat)
+    kind = t.get("kind")
+    if kind not in THERMOSTAT_KINDS:
+        raise ValueError(f"thermostat: kind must be one of {', '.join(THERMOSTAT_KINDS)}, got {kind!r}")
+    unknown = set(t) - set(_GLOBAL_KEYS[kind])
+    if unknown:
+        raise ValueError(f"thermostat: unknown keys {sorted(unknown)} for kind {kind!r} ({', '.join(_GLOBAL_KEYS[kind])})")
+    for key in ("kT", "tau"):
+        if key not in t:
+            raise ValueError(f"thermostat: '{key}' is required")
+    out = dict(kind=kind, kT=float(t["kT"]), tau=float(t["tau"]), seed=int(t.get("seed", 0)) & (2 ** 64 - 1), chain=0, substeps=1)
+    if not out["kT"] > 0 or not out["tau"] > 0 or not math.isfinite(out["kT"]) or not math.isfinite(out["tau"]):
+        raise ValueError(f"thermostat: kT and tau must be positive, got kT={out['kT']}, tau={out['tau']}")
+    if kind == "nose-hoover":
+        out["chain"], out["substeps"] = int(t.get("chain", 3)), int(t.get("substeps", 2))
+        if not 1 <= out["chain"] <= MAX_CHAIN:
+            raise ValueError(f"thermostat: chain must be 1..{MAX_CHAIN} thermostats, got {out['chain']}")
+        if out["substeps"] < 1:
+            raise ValueError(f"thermostat: substeps must be at least 1, got {out['substeps']}")
+    ndof = t.get("ndof")
+    if ndof is not None:
+        ndof = torch.as_tensor(ndof).detach().cpu().reshape(-1)
+        if ndof.dtype.is_floating_point or ndof.dtype == torch.bool:
+            raise ValueError(f"thermostat: ndof must be an integer or an integer tensor, got {ndof.dtype}")
+        ndof = ndof.to(torch.int64)
+        if ndof.numel() < 1 or int(ndof.min()) < 0 or int(ndof.max()) > 2 ** 31 - 1:
+            raise ValueError(f"thermostat: ndof must not be negative, got {ndof.tolist()[:8]}")
+    out["ndof"] = ndof
+    return out
+
+
+def stage_ndof(ndof, default, n_mol):
+    """The thermostat's ``ndof`` (``parse_global_thermostat``: None or a host int64 tensor of 1 or B entries) -> [B] int64 (host);
+    None: ``default``, the loop's own count.  Raises ValueError."""
+    if ndof is None:
+        return default.to(torch.int64).clone()
+    if ndof.numel() not in (1, int(n_mol)):
+        raise ValueError(f"thermostat: ndof must be one integer or one per molecule ({n_mol}), got {ndof.numel()}")
+    return ndof.expand(int(n_mol)).clone()
+
+
+def count_ndof(masses, batch, n_mol, constraints=None):
+    """[B] int64 (host): three degrees of freedom per atom of finite mass, minus the molecule's constraints - ``DeviceMD.ndof``
+    before there is a loop"""
+    if constraints is not None:
+        return constraints["ndof"]
+    free = 3 * torch.isfinite(torch.as_tensor(masses).detach().to(torch.float32)).to(torch.int64).cpu().reshape(-1)
+    return torch.zeros(int(n_mol), dtype=torch.int64).index_add_(0, batch.detach().cpu(), free)
+
+
+class DeviceGlobalMD(DeviceMD):
+    """The object ``TorchMD_Net.capture_md_global`` returns: ``DeviceMD`` without a Langevin thermostat, whose every step ends with the
+    move of a GLOBAL thermostat per molecule inside the graph (``tmdnet_md_thermostat``: stochastic velocity rescaling or a
+    Nose-Hoover chain; the scheme is documented in include/tmdnet_amd.h and DESIGN.md section 13): all velocities of a molecule are
+    multiplied by one factor alpha, so the relative motion of its atoms is left alone.  ``global_thermostat`` is the parsed dict,
+    ``thermostat_ndof`` [B] int64 (host) the degrees of freedom the thermostat counts.  Static tensors rewritten by every replay:
+    ``scale`` [K,B] float32, the factor applied after step k, and ``reservoir`` [K,B] float64, the energy the thermostat holds after
+    step k in the unit of ``epot``; ``ekin`` [K,B] stays what the closing half's reduction wrote, the kinetic energy BEFORE the
+    thermostat's move of that step.  ``chain`` [B,2,M] float64 is the live (xi, v_xi) of the Nose-Hoover chains (M = 0 for CSVR).
+    An atom of infinite mass is no degree of freedom and is not scaled."""
+
+    def __init__(self, model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, warmup, thermostat,
+                 constraints=None):
+        self.global_thermostat = thermostat
+        self._thermo_ready = False
+        super().__init__(model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, None, warmup, None,
+                         constraints)
+
+    def _stage_thermostat(self):
+        th, dev, K, B = self.global_thermostat, self.pos.device, self.steps_per_replay, self.n_mol
+        self.thermostat_ndof = stage_ndof(th["ndof"], self.ndof, B)
+        self._ndof32 = self.thermostat_ndof.to(torch.int32).to(dev).contiguous()
+        self.scale = torch.zeros((K, B), dtype=torch.float32, device=dev)
+        self.reservoir = torch.zeros((K, B), dtype=torch.float64, device=dev)
+        nbytes = C.c_size_t(0)
+        if _C.lib().tmdnet_md_thermostat_workspace_bytes(B, th["chain"], C.byref(nbytes)) != _C.OK:
+            raise ValueError(f"capture_md_global: {B} molecules with a chain of {th['chain']} are not a valid layout")
+        self._thermo_ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
+        # views into the workspace (256-aligned parts: alpha fp32 [B] | reservoir fp64 [B] | chain fp64 [B,2,M])
+        up = lambda n: (n + 255) & ~255
+        off = (-self._thermo_ws.data_ptr()) % 256
+        r0 = off + up(4 * B)
+        c0 = r0 + up(8 * B)
+        M = th["chain"]
+        self._reservoir_now = self._thermo_ws[r0:r0 + 8 * B].view(torch.float64)
+        self.chain = self._thermo_ws[c0:c0 + 16 * B * M].view(torch.float64).view(B, 2, M)
+        self._thermo_ready = True
+
+    def _start(self, step):
+        # the thermostat starts empty, at capture and at every reset: no energy held, chains at rest
+        if not self._thermo_ready:
+            self._stage_thermostat()
+        self._thermo_ws.zero_()
+
+    def _thermostat_move(self, open_next, forces, k):
+        st, dev, th = self._model._engine, self.pos.device, self.global_thermostat
+        rc = _C.lib().tmdnet_md_thermostat(st.handle, _stream_ptr(dev), _ptr(st.graph_ws), _ptr(self._ws), _ptr(self._thermo_ws),
+                                           self.n_atoms, self.n_mol, THERMOSTAT_KINDS[th["kind"]], int(open_next), _ptr(self.pos),
+                                           _ptr(self.vel), _ptr(forces), _ptr(self.hk), self.dt, _ptr(self.inputs[1]), _ptr(self.ekin[k]),
+                                           _ptr(self._ndof32), th["kT"], th["tau"], th["chain"], th["substeps"], self.force_scale,
+                                           th["seed"], _ptr(self.scale[k]), _ptr(self.reservoir[k]))
+        if rc != _C.OK:
+            raise RuntimeError(f"tmdnet_md_thermostat: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
+
+    def _capture_step(self, k, K, out):
+        # CLOSE (kick, kinetic energy, step counter), the thermostat, and the opening half of the next step: fused into the scaling
+        # launch, or with constraints the velocity projection and the constrained OPEN launch on the forces the closing half kept
+        self._advance(MD_CLOSE, out[1], out[0], k)
+        more = k + 1 < K
+        self._thermostat_move(more and self.constraints is None, out[1], k)
+        if self.constraints is not None:
+            # a uniform scaling keeps r.v_rel = 0, but multiplies the residual RATTLE left (within tol) by alpha: project again, which
+            # changes nothing in a cluster that is still within tol
+            self._advance(MD_PROJECT, None, None, k)
+            if more:
+                self._advance(MD_OPEN, self.forces, None, k)
+
+    def kinetic_after(self) -> Tensor:
+        """``scale``^2 ``ekin`` [K,B] float64: the kinetic energy after the thermostat's move of every step, unit of m v^2"""
+        return self.scale.double() ** 2 * self.ekin.double()
+
+    def conserved(self) -> Tensor:
+        """``epot + kinetic_after() / force_scale + reservoir`` [K,B] float64: the energy the thermostatted dynamics conserves"""
+        return self.epot.double() + self.kinetic_after() / self.force_scale + self.reservoir

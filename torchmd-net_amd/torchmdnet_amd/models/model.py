@@ -1504,6 +1504,37 @@ class TorchMD_Net(nn.Module):
         return DeviceMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
                         barostat, constraints)
 
+    def capture_md_global(self, z: Tensor, pos: Tensor, vel: Tensor, masses: Tensor, dt: float, batch: Optional[Tensor] = None,
+                          box: Optional[Tensor] = None, q: Optional[Tensor] = None, num_systems: Optional[int] = None,
+                          steps_per_replay: int = 10, force_scale: float = 1.0, warmup: int = 3, thermostat: Optional[dict] = None,
+                          constraints: Optional[dict] = None):
+        """``capture_md`` with a GLOBAL thermostat in place of the Langevin O step: after the closing kick of every step all
+        velocities of a molecule are multiplied by ONE factor alpha computed from the molecule's kinetic energy inside the graph
+        (``tmdnet_md_thermostat``: two launches), so the relative motion of the atoms - diffusion, vibrational spectra, relaxation
+        times - is not damped.  One thermostat per molecule: a batch of B molecules is B independent thermostatted systems.
+        ``thermostat=dict(kind="csvr", kT=, tau=, seed=0, ndof=None)``: stochastic velocity rescaling (Bussi, Donadio, Parrinello
+        2007), canonical, noise a function of (seed, step, molecule);
+        ``thermostat=dict(kind="nose-hoover", kT=, tau=, chain=3, substeps=2, ndof=None)``: a Nose-Hoover chain of 1..8 thermostats
+        (Martyna, Klein, Tuckerman 1992), deterministic, ``substeps`` applications of the chain routine per step.
+        ``kT`` in the unit of the energies, ``tau`` in the unit of ``dt``.  ``ndof`` (an int or [B]) defaults to ``md.ndof``: three per
+        atom of finite mass minus the constraints; pass it after removing the centre-of-mass momentum.  A molecule with ``ndof == 0``
+        or no kinetic energy is never scaled.  ``constraints=`` is the dict of ``capture_md_constrained``: a uniform scaling keeps
+        the velocities on the constraints; the opening half is then a launch of its own.
+        Returns a ``torchmdnet_amd.md.DeviceGlobalMD``: ``DeviceMD``'s surface plus ``scale`` [K,B], ``reservoir`` [K,B] float64,
+        ``chain`` [B,2,M], ``kinetic_after()`` and ``conserved()``; ``ekin`` is the kinetic energy BEFORE each step's move.
+        ``check()`` names the thermostat when a move was unusable (status 5); ``reset`` empties the thermostat.
+        Not offered, so not parameters of this method (follow-ups): a barostat (MTK NPT), a bias, replica exchange, atom weights
+        and the halo exchange.  Everything ``capture_md`` refuses is refused."""
+        from torchmdnet_amd.md import DeviceGlobalMD, count_ndof, parse_global_thermostat, prepare_constraints, stage_ndof
+
+        th = parse_global_thermostat(thermostat)  # everything below is refused before anything is allocated or captured
+        z, batch, box, q, n_mol, _ = self._capture_inputs("capture_md_global", "molecular dynamics needs", z, pos, batch, box, q,
+                                                          num_systems, steps_per_replay)
+        if constraints is not None:
+            constraints = prepare_constraints(constraints, pos, batch, masses, n_mol)
+        stage_ndof(th["ndof"], count_ndof(masses, batch, n_mol, constraints), n_mol)
+        return DeviceGlobalMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, warmup, th, constraints)
+
     def capture_remd(self, z: Tensor, pos: Tensor, vel: Optional[Tensor], masses: Tensor, dt: float, temperatures=None,
                      exchange_every: int = 100, box: Optional[Tensor] = None, q: Optional[Tensor] = None, steps_per_replay: int = 100,
                      force_scale: float = 1.0, thermostat: Optional[dict] = None, warmup: int = 3, atom_weights=None,
