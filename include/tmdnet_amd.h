@@ -1273,6 +1273,49 @@ int tmdnet_vib_finish(void* stream, void* vib_ws, size_t ws_bytes, int64_t n_ato
                       const float* H, const float* pos, const float* masses, const int64_t* free_idx, const int64_t* fstart,
                       const int64_t* mol_atoms, double* A, double* info);
 
+/* ---- pair priors: ZBL and D2 (csrc/tn_prior.hip, csrc/tn_prior_math.h) -------------------------------------------------------------
+ * Parameter-free pair potentials of pos, z, batch and box that the reference adds to y after the head (models/model.py:612-615,
+ * priors/zbl.py, priors/d2.py).  Here they are one separate pass BEHIND tmdnet_energy_forces / tmdnet_energy_forces_virial: it adds
+ * its energies, forces and virial to what the model's pass wrote.  Brute force inside every molecule, three launches on the caller's
+ * stream, no read-back, no synchronisation (capturable); no floating-point atomics, fixed summation order, bit-identical repeats.
+ *   ZBL   u = (2.30707755e-28 / energy_scale / distance_scale) phi(r distance_scale / a) C(r) Z_i Z_j / r for 0 < r < cutoff, C the
+ *         cosine cutoff, a = 0.8854 a_0 / (Z_i^0.23 + Z_j^0.23); r after the minimum image of the neighbour search when a box is given
+ *   D2    u = - sqrt(C6_i C6_j) / R^6 / (1 + e^{-20 (R / (Rr_i + Rr_j) - 1)}) / (energy_scale N_A), R = r distance_scale 1e9, for
+ *         0 < r < cutoff (a hard cutoff: no force term from it); never sees the box
+ * The tables are indexed by the species z[i] (the prior's atomic_number map is already applied by the caller), fp32, on the host. */
+#define TMDNET_PRIOR_ZBL 1
+#define TMDNET_PRIOR_D2 2
+#define TMDNET_PRIOR_MAX_MOLECULE_ATOMS 32768
+typedef struct {
+  int32_t flags;  /* TMDNET_PRIOR_ZBL | TMDNET_PRIOR_D2 */
+  int32_t max_z;  /* length of every table; a species outside [0, max_z) yields NaN */
+  double zbl_cutoff, zbl_distance_scale, zbl_energy_scale; /* cutoff in the caller's length unit; scales to metres and Joules */
+  double d2_cutoff, d2_distance_scale, d2_energy_scale;
+  const float* zbl_z;      /* [max_z] atomic number Z of species s (host) */
+  const float* zbl_z23;    /* [max_z] Z^0.23 */
+  const float* d2_sqrt_c6; /* [max_z] sqrt(C6) in sqrt(J/mol nm^6) */
+  const float* d2_rr;      /* [max_z] van der Waals radius in nm */
+} tmdnet_pair_priors;
+/* Copies the tables to the device (synchronous) and derives the unit constants in fp64.  NULL or flags == 0 clears the priors. */
+int tmdnet_set_pair_priors(tmdnet_model* m, const tmdnet_pair_priors* priors);
+/* Workspace of one pass: two int32 range counters per molecule and one row of 8 doubles per atom.  The caller ZEROES it before the first
+ * pass and again whenever n_atoms or n_mol differ from the previous pass on it; every pass leaves the counters at zero. */
+int tmdnet_pair_priors_workspace_bytes(const tmdnet_model* m, int64_t n_atoms, int64_t n_mol, size_t* bytes);
+/* ADDS the priors to energy [n_mol], forces [n_atoms, 3] (NULL: energies only) and virial [n_mol, 9] (NULL: none; the convention of
+ * tmdnet_energy_forces_virial).  pos, z, batch, box (box_mode 0: none, 1: one [3,3] box, 2: one per molecule) as given to
+ * tmdnet_build_graph, in the caller's atom order; the batch need not be sorted.  TMDNET_ERR_INVALID when atom_weights is not NULL or
+ * atom weights / a halo exchange are set on the handle (domain decomposition has no prior path), or when n_atoms exceeds
+ * TMDNET_PRIOR_MAX_MOLECULE_ATOMS per molecule on average (the caller checks the individual molecules);  TMDNET_ERR_STATE without
+ * priors set. */
+int tmdnet_pair_priors_add(tmdnet_model* m, void* stream, void* ws, size_t ws_bytes, int64_t n_atoms, int64_t n_mol, const float* pos,
+                           const int64_t* z, const int64_t* batch, const float* box, int32_t box_mode, const float* atom_weights,
+                           float* energy, float* forces, float* virial);
+/* Test entry: the same pass into ZEROED outputs (it zeroes them and the workspace's counters itself), plus the per-atom energies
+ * e_i = 1/2 sum_j u_ij as fp64 [n_atoms] (NULL: not returned).  forces and virial may be NULL. */
+int tmdnet_debug_prior(tmdnet_model* m, void* stream, void* ws, size_t ws_bytes, int64_t n_atoms, int64_t n_mol, const float* pos,
+                       const int64_t* z, const int64_t* batch, const float* box, int32_t box_mode, float* energy, float* forces,
+                       float* virial, double* e_atom);
+
 #ifdef __cplusplus
 }
 #endif

@@ -639,6 +639,7 @@ int tmdnet_destroy(tmdnet_model* m) {
   if (m->upd_ptrs) (void)hipFree(m->upd_ptrs);
   if (m->rb_img) (void)hipFree(m->rb_img);
   if (m->halo_rng) (void)hipFree(m->halo_rng);
+  if (m->prior_tab) (void)hipFree(m->prior_tab);
   delete m;
   return TMDNET_OK;
 }

@@ -13,6 +13,7 @@
 #include "../../include/tmdnet_amd.h"
 #include "tn_gemm.h"
 #include "tn_kernels.h"
+#include "tn_prior_math.h"
 #include "tn_train.h"
 
 using namespace tn;
@@ -235,6 +236,13 @@ struct tmdnet_model {
   int64_t lastN = 0, lastP = 0;
   bool has_last = false;
   const float* tn2_last_chg = nullptr;  // TensorNet2: [N, (L + 1) q_dim] charge channels of the last call (debug tensor "charges")
+  // pair priors (tmdnet_set_pair_priors, tn_prior.hip): TMDNET_PRIOR_* flags (0: none), the species tables [4][prior_max_z] on the
+  // device (Z, Z^0.23, sqrt C6, Rr) and the unit constants of each prior
+  int prior_flags = 0, prior_max_z = 0;
+  float* prior_tab = nullptr;
+  size_t prior_cap = 0;
+  tn_prior::ZblConst prior_zbl{};
+  tn_prior::D2Const prior_d2{};
 };
 
 

@@ -84,6 +84,16 @@ class Tn2UnitArgs(C.Structure):
                                           "g_pre1", "gB", "gCs", "gAp", "dAp", "dC", "gd", "pos", "box", "wq", "ec", "g_q", "fpos")]
 
 
+class PairPriors(C.Structure):
+    """tmdnet_pair_priors (include/tmdnet_amd.h): flags, unit scales and host tables of the ZBL / D2 pair priors."""
+    _fields_ = [("flags", C.c_int32), ("max_z", C.c_int32)] + \
+               [(n, C.c_double) for n in ("zbl_cutoff", "zbl_distance_scale", "zbl_energy_scale", "d2_cutoff", "d2_distance_scale",
+                                          "d2_energy_scale")] + \
+               [(n, C.c_void_p) for n in ("zbl_z", "zbl_z23", "d2_sqrt_c6", "d2_rr")]
+
+
+# flags of tmdnet_set_pair_priors and the brute-force limit of the pass (TMDNET_PRIOR_* in the header)
+PRIOR_ZBL, PRIOR_D2, PRIOR_MAX_MOLECULE_ATOMS = 1, 2, 32768
 # ops of tmdnet_debug_tn2 (TMDNET_TN2_* in the header)
 (TN2_EDGE_REVERSE, TN2_CP_FEAT, TN2_CP_FEAT_BWD, TN2_QEQ_FWD, TN2_QEQ_BWD, TN2_EDGE_PRE1, TN2_EDGE_GW, TN2_EDGE_REDUCE, TN2_PAIR_GD,
  TN2_COULOMB) = range(10)
@@ -228,6 +238,10 @@ def lib():
     L.tmdnet_vib_seed.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, vp, vp, f32, vp]
     L.tmdnet_vib_gather.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tmdnet_vib_finish.argtypes = [vp, vp, sz, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tmdnet_set_pair_priors.argtypes = [vp, C.POINTER(PairPriors)]
+    L.tmdnet_pair_priors_workspace_bytes.argtypes = [vp, i64, i64, C.POINTER(sz)]
+    L.tmdnet_pair_priors_add.argtypes = [vp, vp, vp, sz, i64, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.tmdnet_debug_prior.argtypes = [vp, vp, vp, sz, i64, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     for name in declared_symbols():
         fn = getattr(L, name)
         if fn.restype is C.c_int:

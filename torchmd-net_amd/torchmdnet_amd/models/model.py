@@ -56,7 +56,7 @@ _PROPERTY_ARGS = ("DipoleMoment", "ElectronicSpatialExtent", "VectorOutput")  # 
 
 def _create_model(args, prior_model=None, mean=None, std=None):
     """Supported on the HIP path: model in {"tensornet", "tensornet2", "equivariant-transformer"}, precision 32,
-    prior_model in {None, Atomref}."""
+    prior_model any of Atomref, ZBL, D2 (one of each pair prior)."""
     dtype = dtype_mapping[args["precision"]]
     if "box_vecs" not in args:
         args["box_vecs"] = None
@@ -260,7 +260,7 @@ def load_model(filepath, args=None, device="cpu", return_std=False, **kwargs):
 
 def create_prior_models(args, dataset=None):
     """Parse ``prior_model`` / ``prior_args`` exactly like the reference (model.py:377-448); only priors
-    that exist in torchmdnet_amd.priors can be instantiated (Atomref)."""
+    that exist in torchmdnet_amd.priors can be instantiated (Atomref, ZBL, D2)."""
     prior_models = []
     if args["prior_model"]:
         prior_model = args["prior_model"]
@@ -280,7 +280,11 @@ def create_prior_models(args, dataset=None):
             if not isinstance(pargs, list):
                 pargs = [pargs]
         for name, arg in zip(names, pargs):
-            if not hasattr(priors, name):
+            if name == "Coulomb":
+                raise NotImplementedError("prior model Coulomb has no MI355X-native path: it needs per-atom partial_charges through "
+                                          "extra_args, which the registered operator tmdnet::energy_forces does not carry "
+                                          f"(available: {priors.__all__})")
+            if name not in priors.__all__:
                 raise NotImplementedError(f"prior model {name} has no MI355X-native path (available: {priors.__all__})")
             prior_models.append(getattr(priors, name)(dataset=dataset, **arg))
     return prior_models
@@ -428,18 +432,25 @@ class _EnergyForceParamGrad(torch.autograd.Function):
         if has_e and not one_pass:
             add(model.parameter_gradients_of(z, pos, batch, box, q, n_mol, g_energy)[1], 1.0)
         g_pos = None
-        if g_energy is not None and not (one_pass and ctx.needs_input_grad[2] and getattr(model, "force_position_gradient", True)):
+        pos_hv = ctx.needs_input_grad[2] and getattr(model, "force_position_gradient", True)
+        if pos_hv and has_f and any(p is not None for p in model._pair_priors()):
+            # H v of the model alone would lack the ZBL / D2 term: the parameter gradients (which the priors do not enter) stay exact,
+            # pos.grad keeps the energy term's part only - said once, as for the difference-quotient orders below
+            pos_hv = False
+            if not getattr(model, "_warned_prior_pos_grad", False):
+                warnings.warn("torchmdnet_amd: with a ZBL / D2 prior, pos.grad of a loss that depends on the FORCES holds only the "
+                              "energy term's part (-g_E F): the pair priors have no second-derivative pass", stacklevel=2)
+                model._warned_prior_pos_grad = True
+        if g_energy is not None and not (one_pass and pos_hv):
             g_pos = -g_energy.reshape(-1)[batch].unsqueeze(1) * forces  # first order in pos (as tmdnet::energy_forces' backward)
         if has_f:
             v = g_forces.detach().to(torch.float32)
-            want_hv = ctx.needs_input_grad[2] and getattr(model, "force_position_gradient", True)
+            want_hv = pos_hv
             with_hv = analytic and want_hv
             if want_hv and not analytic and not getattr(model, "_warned_pos_grad", False):
                 # pos always requires grad here (the reference's side effect, model.py:584-585), so this cannot tell a caller who
                 # wants d loss / d pos from one who does not: say it once instead of silently returning a truncated gradient.
                 # (force_position_gradient = False is the caller's own choice: no warning then.)
-                import warnings
-
                 warnings.warn("torchmdnet_amd: pos.grad of a loss that depends on the FORCES holds only the energy term's part "
                               "(-g_E F): the difference-quotient force gradient (force_gradient_order 2 / 4) carries a graph to "
                               "the parameters only; the second derivative in the positions comes with the analytic pass "
@@ -493,8 +504,11 @@ class TorchMD_Net(nn.Module):
             prior_model = [prior_model]
         if prior_model is not None:
             for p in prior_model:
-                if not isinstance(p, priors.Atomref):
+                if not isinstance(p, (priors.Atomref, priors.ZBL, priors.D2)):
                     raise NotImplementedError(f"prior {type(p).__name__} has no MI355X-native path")
+            for kind in (priors.ZBL, priors.D2):  # the pair pass evaluates one prior of each kind
+                if sum(isinstance(p, kind) for p in prior_model) > 1:
+                    raise NotImplementedError(f"several {kind.__name__} priors in one model have no MI355X-native path")
         self.prior_model = None if prior_model is None else nn.ModuleList(prior_model).to(dtype=dtype)
         self.derivative = derivative
         mean = torch.scalar_tensor(0) if mean is None else mean
@@ -590,7 +604,7 @@ class TorchMD_Net(nn.Module):
     def _atomref_table(self) -> Optional[Tensor]:
         if self.prior_model is None:
             return None
-        tables = [p.atomref.weight.detach().reshape(-1) for p in self.prior_model if p.enable]
+        tables = [p.atomref.weight.detach().reshape(-1) for p in self._atomref_priors() if p.enable]
         if not tables:
             return None
         max_z = self.representation_model.max_z
@@ -599,6 +613,118 @@ class TorchMD_Net(nn.Module):
             n = min(max_z, t.numel())
             out[:n] += t[:n].float().cpu()
         return out
+
+    def _atomref_priors(self):
+        return [p for p in (self.prior_model or ()) if isinstance(p, priors.Atomref)]
+
+    def _pair_priors(self):
+        """(ZBL or None, D2 or None): the priors that the pair pass behind the engine call evaluates (csrc/tn_prior.hip)."""
+        zbl = d2 = None
+        for p in (self.prior_model or ()):
+            if isinstance(p, priors.ZBL):
+                zbl = p
+            elif isinstance(p, priors.D2):
+                d2 = p
+        return zbl, d2
+
+    def _stage_pair_priors(self, st):
+        """Upload the species tables and unit scales of the ZBL / D2 priors (``tmdnet_set_pair_priors``), or clear them."""
+        import numpy as np
+
+        L = _C.lib()
+        zbl, d2 = self._pair_priors()
+        st.pair_priors = zbl is not None or d2 is not None
+        if not st.pair_priors:
+            L.tmdnet_set_pair_priors(st.handle, None)
+            return
+        max_z = int(self.representation_model.max_z)
+        pp = _C.PairPriors()
+        pp.max_z = max_z
+        keep = []  # the host tables, alive until the call has copied them
+        host = lambda a: keep.append(np.ascontiguousarray(a, dtype=np.float32)) or keep[-1].ctypes.data
+        if zbl is not None:
+            pp.flags |= _C.PRIOR_ZBL
+            pp.zbl_cutoff, pp.zbl_distance_scale, pp.zbl_energy_scale = float(zbl.cutoff_distance), zbl.distance_scale, zbl.energy_scale
+            Z, Z23 = zbl.species_tables(max_z)
+            pp.zbl_z, pp.zbl_z23 = host(Z), host(Z23)
+        if d2 is not None:
+            pp.flags |= _C.PRIOR_D2
+            pp.d2_cutoff, pp.d2_distance_scale, pp.d2_energy_scale = float(d2.cutoff_distance), float(d2.distance_scale), float(d2.energy_scale)
+            sq, rr = d2.species_tables(max_z)
+            pp.d2_sqrt_c6, pp.d2_rr = host(sq), host(rr)
+        if L.tmdnet_set_pair_priors(st.handle, C.byref(pp)) != _C.OK:
+            raise RuntimeError(f"tmdnet_set_pair_priors: {L.tmdnet_last_error(st.handle).decode()}")
+
+    def _refuse_pair_priors(self, what):
+        """What the pair priors are not implemented for: raised before anything is set on the handle."""
+        if any(p is not None for p in self._pair_priors()):
+            raise NotImplementedError(f"the ZBL / D2 pair priors have no HIP path with {what}")
+
+    def _check_pair_prior_inputs(self, z, batch, n_mol):
+        """Host-side refusals of the pair pass that depend on the inputs: a D2 species without a table entry, and a molecule beyond
+        the brute-force limit.  Read back once per ``z`` / ``batch`` tensor and version (an MD loop keeps them: no synchronisation
+        per step), never during a capture."""
+        key = (z.data_ptr(), z._version, tuple(z.shape), batch.data_ptr(), batch._version, n_mol)
+        if getattr(self._engine, "prior_checked", None) == key or torch.cuda.is_current_stream_capturing():
+            return
+        d2 = self._pair_priors()[1]
+        if d2 is not None:
+            d2.check_species(z)
+        if z.shape[0] > priors.MAX_MOLECULE_ATOMS:
+            priors.check_molecule_size(int(torch.bincount(batch.reshape(-1).clamp(min=0)).max()))
+        self._engine.prior_checked = key
+
+    def _add_pair_priors(self, st, stream, n, n_mol, p32, z, batch, box, box_mode, energy, forces, virial):
+        """The pair pass behind an engine call: ADDS the ZBL / D2 energies, forces and virial on the same stream
+        (``tmdnet_pair_priors_add``: three launches, no read-back).  One zeroed workspace per (n, n_mol), as the pass wants it."""
+        L = _C.lib()
+        dev = p32.device
+        nbytes = C.c_size_t(0)
+        L.tmdnet_pair_priors_workspace_bytes(st.handle, n, n_mol, C.byref(nbytes))
+        pool = getattr(st, "prior_ws", None)
+        if pool is None:
+            pool = st.prior_ws = {}
+        ws = pool.get((n, n_mol))
+        if ws is None or ws.device != dev or ws.numel() < nbytes.value:
+            if len(pool) >= 16:  # bounded: a captured graph may hold the address of a workspace that goes, so it becomes stale
+                pool.clear()
+                st.generation += 1
+            ws = pool[(n, n_mol)] = torch.zeros(max(int(nbytes.value), 256), dtype=torch.uint8, device=dev)
+        rc = L.tmdnet_pair_priors_add(st.handle, stream, _ptr(ws), ws.numel(), n, n_mol, _ptr(p32), _ptr(z), _ptr(batch), _ptr(box),
+                                      box_mode, None, _ptr(energy), _ptr(forces), _ptr(virial))
+        if rc == _C.ERR_INVALID:
+            raise NotImplementedError(f"tmdnet_pair_priors_add: {L.tmdnet_last_error(st.handle).decode()}")
+        if rc != _C.OK:
+            raise RuntimeError(f"tmdnet_pair_priors_add: {L.tmdnet_last_error(st.handle).decode()} (code {rc})")
+
+    def debug_pair_priors(self, z, pos, batch, box=None, num_systems=None, want_virial=True):
+        """Test entry (``tmdnet_debug_prior``): the pair pass alone into zeroed outputs -> (E [B], F [N,3], W [B,3,3] or None,
+        e_atom [N] fp64), the per-atom energies e_i = 1/2 sum_j u_ij included."""
+        _require_cuda(pos, "TorchMD_Net.debug_pair_priors")
+        L = _C.lib()
+        dev = pos.device
+        with torch.cuda.device(dev):
+            st = self._sync_engine()
+            n = int(z.shape[0])
+            n_mol = int(num_systems) if num_systems is not None else (int(batch.max().item()) + 1 if n else 0)
+            p32 = pos.detach().to(torch.float32).contiguous()
+            z, batch = z.contiguous(), batch.to(torch.long).contiguous()
+            box_mode = 0
+            if box is not None:
+                box = box.detach().to(device=dev, dtype=torch.float32).contiguous()
+                box_mode = 1 if box.dim() == 2 else 2
+            nbytes = C.c_size_t(0)
+            L.tmdnet_pair_priors_workspace_bytes(st.handle, n, n_mol, C.byref(nbytes))
+            ws = torch.empty(max(int(nbytes.value), 256), dtype=torch.uint8, device=dev)
+            energy = torch.empty(n_mol, dtype=torch.float32, device=dev)
+            forces = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            virial = torch.empty((n_mol, 3, 3), dtype=torch.float32, device=dev) if want_virial else None
+            e_atom = torch.empty(n, dtype=torch.float64, device=dev)
+            rc = L.tmdnet_debug_prior(st.handle, _stream_ptr(dev), _ptr(ws), ws.numel(), n, n_mol, _ptr(p32), _ptr(z), _ptr(batch), _ptr(box),
+                                      box_mode, _ptr(energy), _ptr(forces), _ptr(virial), _ptr(e_atom))
+            if rc != _C.OK:
+                raise RuntimeError(f"tmdnet_debug_prior: {L.tmdnet_last_error(st.handle).decode()} (code {rc})")
+        return energy, forces, virial, e_atom
 
     def _apply(self, fn, recurse=True):
         # .to() / .cuda() / .float() replace buffers by new tensor objects: drop the cached tensor list of _fingerprint
@@ -638,7 +764,8 @@ class TorchMD_Net(nn.Module):
         fp = [getattr(st, "index_epoch", 0)]
         fp.extend((t._version, t.data_ptr()) for _, _, t in idx[0])
         if self.prior_model is not None:
-            fp.append(tuple(p.enable for p in self.prior_model))
+            # Atomref: its switch; ZBL / D2: every argument the engine's copy depends on (they are plain attributes, not tensors)
+            fp.append(tuple(p.enable if isinstance(p, priors.Atomref) else p.engine_key() for p in self.prior_model))
         return tuple(fp)
 
     @property
@@ -713,6 +840,7 @@ class TorchMD_Net(nn.Module):
             L.tmdnet_set_option(handle, b"pair_rows_bf16", PAIR_STORAGE[self.pair_storage])
         for name, value in getattr(st, "options", {}).items():
             L.tmdnet_set_option(handle, name.encode(), value)
+        self._stage_pair_priors(st)
         st.fingerprint = fp
         # state for the device-side update of the next training step: the fingerprint this upload corresponds to and the
         # state-dict key of every fingerprinted tensor (None: not in the state dict)
@@ -794,6 +922,9 @@ class TorchMD_Net(nn.Module):
         ge [n_mol] = d loss / d E (one-pass training, tmdnet_loss_param_grads): the gradients of  S = s - sum_m ge_m E_m  instead, so
         that the whole gradient of loss(E, F) is minus the result (parameters) and minus H v' (positions); an Atomref prior's table,
         which the engine does not hold, is added here."""
+        if want_hv:  # H v of the model alone would lack the priors' second derivative
+            self._refuse_pair_priors("second derivatives with respect to the positions (want_hv=True, a force loss's pos.grad); "
+                                     "set force_position_gradient = False, or take hessian(method='central')")
         if self._is_et():
             q = None  # TorchMD_ET.forward ignores q
         L = _C.lib()
@@ -803,7 +934,7 @@ class TorchMD_Net(nn.Module):
             stream = _stream_ptr(dev)
             n = int(z.shape[0])
             p32 = pos.detach().to(torch.float32).contiguous()
-            v32 = v.detach().to(device=dev, dtype=torch.float32).contiguous()
+            v32 =v.detach().to(device=dev, dtype=torch.float32).contiguous()
             assert v32.shape == p32.shape
             z = z.contiguous()
             batch = batch.to(torch.long).contiguous()
@@ -849,7 +980,7 @@ class TorchMD_Net(nn.Module):
                 ent[name] = flat[off.value: off.value + numel.value]
             grads = self._et_grads(ent) if self._is_et() else (self._tn2_grads(ent) if self._is_tn2() else self._tensornet_grads(ent))
             if ge32 is not None and self.prior_model is not None:  # d S / d atomref[z] = - sum of ge[molecule] over the atoms of species z
-                for pr in self.prior_model:
+                for pr in self._atomref_priors():
                     if pr.enable:
                         w = pr.atomref.weight
                         grads[w] = (-scale) * torch.zeros(w.shape[0], dtype=torch.float32, device=dev).index_add_(0, z, ge32[batch]).view_as(w)
@@ -918,6 +1049,8 @@ class TorchMD_Net(nn.Module):
                                                  None, _ptr(energy), None)
                 if rc != _C.OK:
                     raise RuntimeError(f"tmdnet_energy_param_grads: {L.tmdnet_last_error(st.handle).decode()} (code {rc})")
+                if getattr(st, "pair_priors", False):  # this energy does not come through energy_and_forces: the priors are added here
+                    self._add_pair_priors(st, stream, n, n_mol, p32, z, batch, box, box_mode, energy, None, None)
                 st.ws_epoch = getattr(st, "ws_epoch", 0) + 1
                 token["epoch"] = st.ws_epoch
         return energy, token
@@ -943,6 +1076,10 @@ class TorchMD_Net(nn.Module):
                                              _ptr(ge), None if kept else _ptr(token["energy"]), _ptr(flat))
             if rc != _C.OK:
                 raise RuntimeError(f"tmdnet_energy_param_grads: {L.tmdnet_last_error(st.handle).decode()} (code {rc})")
+            if not kept and getattr(st, "pair_priors", False):  # the energies were written by this call: the priors are added here
+                tb = token["box"]
+                self._add_pair_priors(st, stream, n, n_mol, token["pos"], z, batch, tb, 0 if tb is None else (1 if tb.dim() == 2 else 2),
+                                      token["energy"], None, None)
             st.ws_epoch = getattr(st, "ws_epoch", 0) + 1
             ent = {}
             for i in range(L.tmdnet_param_grad_count(st.handle)):
@@ -951,7 +1088,7 @@ class TorchMD_Net(nn.Module):
                 ent[name] = flat[off.value: off.value + numel.value]
             grads = self._et_grads(ent) if self._is_et() else (self._tn2_grads(ent) if self._is_tn2() else self._tensornet_grads(ent))
             if self.prior_model is not None:  # Atomref: E_m += sum_i atomref[z_i]
-                for pr in self.prior_model:
+                for pr in self._atomref_priors():
                     if pr.enable:
                         w = pr.atomref.weight
                         grads[w] = torch.zeros(w.shape[0], dtype=torch.float32, device=dev).index_add_(0, z, ge[batch]).view_as(w)
@@ -1080,7 +1217,9 @@ class TorchMD_Net(nn.Module):
         (n_x, n_y, n_z) fixes the neighbour search's grid (``tmdnet_set_cell_grid``; default: from the box on the device).
         ``want_virial=True`` (TensorNet and Equivariant Transformer, scalar head) returns a third element W [n_mol,3,3], the virial
         W_m[a][b] = -dE_m/d eps_ab under pos -> pos (I + eps), box -> box (I + eps) (``tmdnet_energy_forces_virial``); E and F are
-        bit-identical to the two-element call."""
+        bit-identical to the two-element call.  A model with a ZBL / D2 prior runs the pair pass behind the model's
+        (``tmdnet_pair_priors_add``: three more launches on the same stream, E, F and W added in place; ``want_forces=False`` adds the
+        energy only); without one nothing else is launched.  Pair priors refuse ``atom_weights`` and ``halo_exchange``."""
         _require_cuda(pos, "TorchMD_Net.forward")
         L = _C.lib()
         dev = pos.device
@@ -1094,6 +1233,8 @@ class TorchMD_Net(nn.Module):
         if want_virial:
             self._refuse_virial(atom_weights, halo_exchange)
             want_forces = True  # the virial is a by-product of the force pass
+        if self.prior_model is not None and (atom_weights is not None or halo_exchange is not None):
+            self._refuse_pair_priors("atom weights or the halo exchange (domain decomposition)")
         if self._head_kind() != _C.HEAD_SCALAR:
             if atom_weights is not None or halo_exchange is not None:
                 raise NotImplementedError(f"{type(self.output_model).__name__}: atom weights and the halo exchange have no HIP path "
@@ -1116,6 +1257,8 @@ class TorchMD_Net(nn.Module):
                 q = q.detach().to(device=dev, dtype=torch.float32).contiguous()
                 if q.numel() != n_mol:
                     raise ValueError(f"q must have one entry per molecule ({n_mol}), got {q.numel()}")
+            if getattr(st, "pair_priors", False):
+                self._check_pair_prior_inputs(z, batch, n_mol)
             # neighbour strategy: O(N) cell list for one large system - periodic (grid computed on the device from the box of
             # THIS call: nothing about the box is cached on the host) or not (fictitious box around the bounding box, as the
             # reference's cell strategy, models/utils.py:206-212) -, brute force inside each molecule otherwise
@@ -1203,6 +1346,10 @@ class TorchMD_Net(nn.Module):
                 else:
                     rc = L.tmdnet_energy_forces(st.handle, stream, _ptr(st.graph_ws), _ptr(st.fwd_ws), st.fwd_ws.numel(), n, n_mol,
                                                 n_pairs, _ptr(z), _ptr(batch), _ptr(q), int(want_forces), _ptr(energy), _ptr(forces))
+                if rc == _C.OK and getattr(st, "pair_priors", False):
+                    # ZBL / D2: one pair pass behind the model's, which adds to its outputs (same stream: ordered, capturable)
+                    self._add_pair_priors(st, stream, n, n_mol, p32, z, batch, box, box_mode, energy, forces,
+                                          virial if want_virial else None)
             finally:  # also when the graph phase raised: the handle must not keep a callback or weights that are about to be freed
                 if halo_exchange is not None:
                     L.tmdnet_set_halo_exchange(st.handle, _C.HALO_EXCHANGE_FN(), None)

@@ -100,6 +100,8 @@ def compute_hessian(model, z, pos, batch, box, q, method, delta, fixed, replicas
                                   "has a property head")
     if method == "analytic" and atom_weights is not None:
         raise NotImplementedError("hessian(method='analytic') has no HIP path with atom weights: the second-order pass takes none")
+    if method == "analytic":  # the second-order pass knows the model only; method="central" sees the priors through energy_and_forces
+        model._refuse_pair_priors("hessian(method='analytic'); take method='central'")
     bh, fh, n_mol = check_request(z, pos, batch, q, method, delta, fixed, replicas)
     if atom_weights is not None and atom_weights.numel() != z.shape[0]:
         raise ValueError(f"atom_weights must have one entry per atom ({z.shape[0]}), got {atom_weights.numel()}")
