@@ -1316,6 +1316,64 @@ int tmdnet_debug_prior(tmdnet_model* m, void* stream, void* ws, size_t ws_bytes,
                        const int64_t* z, const int64_t* batch, const float* box, int32_t box_mode, float* energy, float* forces,
                        float* virial, double* e_atom);
 
+/* ---- committee of models (csrc/tn_committee.hip, csrc/tn_committee_math.h; additive exports, the ABI revision stays 10) -----------
+ * M members, 2 <= M <= TMDNET_COMMITTEE_MAX_MEMBERS, have each written their energies E_k [n_mol] and forces F_k [n_atoms, 3] (fp32,
+ * the caller's atom order) - by tmdnet_energy_forces on the same stream, or by anything else.  One pass reduces them:
+ *   mean_m = (1 / M) sum_k E_k,m        std_m = sqrt(sum_k (E_k,m - mean_m)^2 / (M - 1))    (unbiased: torch.std)
+ *   the same per force component;  d_i = sqrt(sum_c std_i,c^2), a d_i that is not finite is +inf;
+ *   D_m = max_{i in m} d_i and a_m the smallest atom index that attains it; a molecule without atoms has D_m = 0, a_m = -1.
+ * Two passes over the M values (the mean, then the squared differences), sums, division and square roots in fp64 in member order,
+ * every output rounded to fp32 once.  Two launches, no read-back, nothing allocated, capturable; the molecule maximum is a 64-bit
+ * integer atomicMax, so repeats are bit-identical and `batch` need not be sorted (entries outside [0, n_mol) join no molecule).
+ * The gate compares as !(D_m <= threshold): a NaN never passes as certain. */
+#define TMDNET_COMMITTEE_MAX_MEMBERS 16
+#define TMDNET_COMMITTEE_FLAG 1 /* record the first step at which !(D_m <= flag_above), per molecule; the trajectory goes on */
+#define TMDNET_COMMITTEE_STOP 2 /* latch status 6 in md_ws after the step at which any molecule has !(D_m <= stop_above) */
+typedef struct {
+  int32_t flags;           /* TMDNET_COMMITTEE_FLAG | TMDNET_COMMITTEE_STOP; 0: no gate, md_ws only freezes the pass with the loop */
+  float flag_above;        /* thresholds on D_m, in the unit of the forces; not NaN */
+  float stop_above;
+  void* md_ws;             /* the loop's tmdnet_md_workspace_bytes state: status word and step counter; required with flags != 0 */
+  int64_t* flagged_at;     /* [n_mol], -1 before: the step (1 = the first after tmdnet_md_reset(0)) molecule m was first flagged at */
+  float* flagged_dev;      /* [n_mol] D_m of that step */
+  int64_t* flagged_atom;   /* [n_mol] a_m of that step */
+  float* flagged_pos;      /* [n_atoms, 3]: the molecule's atoms at that step; rows of unflagged molecules are not written */
+} tmdnet_committee_gate;
+/* Workspace of the pass: a 256-byte header (the stop word and the record of a stop), one 64-bit word and one int32 per molecule.
+ * The caller ZEROES it once (or calls tmdnet_committee_reset); every pass leaves the per-molecule words at zero. */
+int tmdnet_committee_workspace_bytes(int64_t n_atoms, int64_t n_mol, size_t* bytes);
+/* Enqueues a memset of the whole workspace: words, decisions and the record of a stop. */
+int tmdnet_committee_reset(void* stream, void* ws, int64_t n_mol);
+/* The pass.  energies / forces_in: HOST arrays of n_members device pointers, read during the call and passed to the kernels by value
+ * (no pointer table in device memory).  Outputs: energy, energy_std, max_deviation [n_mol], max_atom [n_mol] int64, forces,
+ * forces_std [n_atoms, 3], deviation [n_atoms].
+ *   members, graph_ws   both NULL, or HOST arrays of the n_members handles and the graph workspaces of the evaluations before this
+ *                 call (static shapes): the overflow flags of members 1.. are folded into member 0's, which is the flag the
+ *                 integrator reads when it is given member 0's handle and workspace; an overflowed evaluation logs and decides nothing.
+ *   gate          NULL, or the gate of a captured MD step: with its md_ws a frozen loop (status != 0) leaves every output alone;
+ *                 with TMDNET_COMMITTEE_FLAG the molecule's thread records flagged_at / flagged_dev / flagged_atom, with
+ *                 TMDNET_COMMITTEE_STOP it enters the stop word.  The step is md_ws's counter + 1: call this BEFORE the closing launch.
+ * TMDNET_ERR_INVALID before any launch: n_members outside 2..16, a NULL array or entry, negative or oversized counts, only one of
+ * members / graph_ws, unknown gate flags, gate flags without md_ws, TMDNET_COMMITTEE_FLAG without its four buffers, a NaN threshold.
+ * TMDNET_ERR_WORKSPACE: ws_bytes too small. */
+int tmdnet_committee_reduce(void* stream, void* ws, size_t ws_bytes, int32_t n_members, const float* const* energies,
+                            const float* const* forces_in, int64_t n_atoms, int64_t n_mol, const int64_t* batch, float* energy,
+                            float* forces, float* energy_std, float* forces_std, float* deviation, float* max_deviation,
+                            int64_t* max_atom, tmdnet_model* const* members, void* const* graph_ws, const tmdnet_committee_gate* gate);
+/* The gate's second half, one launch AFTER the closing launch of the step (tmdnet_md_advance TMDNET_MD_CLOSE with the committee's
+ * forces and energy; it does not move positions): copies the atoms of the molecules flagged at this step from pos into
+ * gate->flagged_pos, and turns a stop word into status 6 of gate->md_ws - from there every launch of the loop returns at once, as
+ * after an overflow - and the record {step, molecule, atom, D}: the molecule of the largest D_m (the smallest index among equals)
+ * and max_atom[molecule], the row the pass wrote for this step.  The frozen state is the completed step: pos, vel and forces_keep of
+ * that step, the counter at that step.  tmdnet_md_status answers TMDNET_ERR_STATE with host[1] = 6.  gate->flags == 0: no launch.
+ * A step is then: M evaluations, tmdnet_committee_reduce, TMDNET_MD_CLOSE, tmdnet_committee_latch, and TMDNET_MD_OPEN on
+ * forces_keep when another step follows - TMDNET_MD_MIDDLE is CLOSE then OPEN on the same values, so the split changes no bit. */
+int tmdnet_committee_latch(void* stream, void* ws, int64_t n_atoms, int64_t n_mol, const int64_t* batch, const float* pos,
+                           const int64_t* max_atom, const tmdnet_committee_gate* gate);
+/* host[0] = 1 when a stop was latched since the last reset, then host[1] = step, host[2] = molecule, host[3] = atom, host[4] = the
+ * bits of D (fp32) in the low word.  Synchronises the stream. */
+int tmdnet_committee_status(void* stream, void* ws, uint64_t host[5]);
+
 #ifdef __cplusplus
 }
 #endif

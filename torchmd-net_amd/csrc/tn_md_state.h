@@ -15,7 +15,8 @@ constexpr size_t kHeaderBytes = 256;
 
 struct MdState {  // views into the caller's workspace
   uint32_t* head;  // [0] step lo, [1] step hi, [2] status (sticky, 1 = an evaluation overflowed, 2 = an unusable barostat move,
-                   // 3 = a constraint cluster did not converge, 4 = a bias that was not finite, 5 = an unusable thermostat move)
+                   // 3 = a constraint cluster did not converge, 4 = a bias that was not finite, 5 = an unusable thermostat move,
+                   // 6 = the gate of a committee stopped the loop at a completed step: tn_committee.hip)
   float* x_keep;   // [N, 3] positions at the last completed step
   float* v_keep;   // [N, 3]
   float* part;     // [N]    0.5 m v^2 per atom, caller's order

@@ -92,8 +92,16 @@ class PairPriors(C.Structure):
                [(n, C.c_void_p) for n in ("zbl_z", "zbl_z23", "d2_sqrt_c6", "d2_rr")]
 
 
+class CommitteeGate(C.Structure):
+    """tmdnet_committee_gate (include/tmdnet_amd.h): thresholds, the loop's MD workspace and the buffers of the flagged molecules."""
+    _fields_ = [("flags", C.c_int32), ("flag_above", C.c_float), ("stop_above", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("md_ws", "flagged_at", "flagged_dev", "flagged_atom", "flagged_pos")]
+
+
 # flags of tmdnet_set_pair_priors and the brute-force limit of the pass (TMDNET_PRIOR_* in the header)
 PRIOR_ZBL, PRIOR_D2, PRIOR_MAX_MOLECULE_ATOMS = 1, 2, 32768
+# limit and gate flags of the committee pass (TMDNET_COMMITTEE_* in the header)
+COMMITTEE_MAX_MEMBERS, COMMITTEE_FLAG, COMMITTEE_STOP = 16, 1, 2
 # ops of tmdnet_debug_tn2 (TMDNET_TN2_* in the header)
 (TN2_EDGE_REVERSE, TN2_CP_FEAT, TN2_CP_FEAT_BWD, TN2_QEQ_FWD, TN2_QEQ_BWD, TN2_EDGE_PRE1, TN2_EDGE_GW, TN2_EDGE_REDUCE, TN2_PAIR_GD,
  TN2_COULOMB) = range(10)
@@ -242,6 +250,12 @@ def lib():
     L.tmdnet_pair_priors_workspace_bytes.argtypes = [vp, i64, i64, C.POINTER(sz)]
     L.tmdnet_pair_priors_add.argtypes = [vp, vp, vp, sz, i64, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.tmdnet_debug_prior.argtypes = [vp, vp, vp, sz, i64, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.tmdnet_committee_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
+    L.tmdnet_committee_reset.argtypes = [vp, vp, i64]
+    L.tmdnet_committee_reduce.argtypes = [vp, vp, sz, i32, C.POINTER(vp), C.POINTER(vp), i64, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                          C.POINTER(vp), C.POINTER(vp), C.POINTER(CommitteeGate)]
+    L.tmdnet_committee_latch.argtypes = [vp, vp, i64, i64, vp, vp, vp, C.POINTER(CommitteeGate)]
+    L.tmdnet_committee_status.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
     for name in declared_symbols():
         fn = getattr(L, name)
         if fn.restype is C.c_int:

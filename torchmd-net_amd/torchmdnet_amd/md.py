@@ -14,6 +14,8 @@ replicas of one system and exchanges their temperatures inside the graph (csrc/t
 ``TorchMD_Net.capture_md_global`` (``DeviceGlobalMD``) replaces the Langevin O step by a global thermostat per molecule - stochastic
 velocity rescaling or a Nose-Hoover chain - that scales all velocities of a molecule by one factor (csrc/tn_md_thermo.hip,
 ``tmdnet_md_thermostat``: two launches between the closing and the opening half of a step).
+``Ensemble.capture_md`` (``torchmdnet_amd.committee.DeviceCommitteeMD``) drives the loop with the mean force of a committee of models
+and gates it on the members' disagreement inside the graph (csrc/tn_committee.hip).
 The capture sequence, the stale-graph guard, ``md(n)``, the status read-back and the skeleton of ``reset`` are those of every
 captured loop: ``torchmdnet_amd.captured``."""
 import ctypes as C

@@ -1981,3 +1981,51 @@ class Ensemble(torch.nn.ModuleList):
         if self.return_std:
             return torch.mean(y, axis=0), torch.mean(f, axis=0), torch.std(y, axis=0), torch.std(f, axis=0)
         return torch.mean(y, axis=0), torch.mean(f, axis=0)
+
+    # ---------------------------------------------------------------- the committee on the device (torchmdnet_amd/committee.py)
+    def committee(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
+                  q: Optional[Tensor] = None, num_systems: Optional[int] = None, atom_weights=None, halo_exchange=None):
+        """Every member's ``energy_and_forces`` on the current stream, one after the other (each with its own architecture, cutoff,
+        priors and box), then ONE pass on the device (``tmdnet_committee_reduce``, two launches): -> the named result
+        ``committee.CommitteeResult(energy [B], forces [N,3], energy_std [B], forces_std [N,3], deviation [N], max_deviation [B],
+        max_atom [B] int64)``: mean and unbiased standard deviation over the members (fp64 sums in two passes, rounded once - unlike
+        ``forward``'s fp32 ``torch.std``, which is kept as it is), ``deviation[i] = sqrt(sum_c forces_std[i,c]^2)`` (+inf when not
+        finite), and per molecule its maximum and the smallest atom index that attains it (0 and -1 without atoms).  2 to 16 members
+        on one device, scalar heads, no training models; ``atom_weights`` / ``halo_exchange`` are accepted only to be refused."""
+        from torchmdnet_amd import committee
+
+        return committee.committee(self, z, pos, batch, box, q, num_systems, atom_weights, halo_exchange)
+
+    def capture(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None,
+                q: Optional[Tensor] = None, num_systems: Optional[int] = None, warmup: int = 3, atom_weights=None, halo_exchange=None):
+        """``committee`` captured into ONE HIP graph (every member needs ``static_shapes=True``): the members in member order on the
+        capturing stream, then the pass.  Returns ``replay(pos=None)`` -> the same named result in static buffers; ``replay.pos`` are
+        the positions the graph reads (write them in place to skip the copy), ``replay.inputs`` the staged inputs per member,
+        ``replay.graph`` the graph, ``replay.member_outputs`` the members' own static (E, F).  A parameter change or device move of
+        any member after the capture makes the next replay raise."""
+        from torchmdnet_amd import committee
+
+        return committee.capture(self, z, pos, batch, box, q, num_systems, warmup, atom_weights, halo_exchange)
+
+    def capture_md(self, z: Tensor, pos: Tensor, vel: Tensor, masses: Tensor, dt: float, batch: Optional[Tensor] = None,
+                   box: Optional[Tensor] = None, q: Optional[Tensor] = None, num_systems: Optional[int] = None,
+                   steps_per_replay: int = 10, force_scale: float = 1.0, thermostat: Optional[dict] = None, warmup: int = 3,
+                   gate: Optional[dict] = None, atom_weights=None, halo_exchange=None, barostat=None, constraints=None, bias=None,
+                   temperatures=None):
+        """``TorchMD_Net.capture_md`` driven by the committee: ``steps_per_replay`` MD steps in one HIP graph, every step with the M
+        members' evaluations, the committee pass and the integrator on the MEAN forces; ``epot`` is the mean energy.  Returns a
+        ``torchmdnet_amd.committee.DeviceCommitteeMD``: ``DeviceMD``'s surface plus the logs ``energy_std / deviation /
+        deviation_atom`` [K,B] and the gate's state.
+        ``gate=dict(flag_above=None | float, stop_above=None | float)``, thresholds on the molecule's largest force deviation D_m in
+        the unit of the forces, compared as ``not (D_m <= threshold)`` so that a NaN never passes as certain.  ``flag_above``: the
+        first time a molecule exceeds it, ``flagged_at[m]`` becomes the step and the molecule's atoms are copied into
+        ``flagged_pos`` (with ``flagged_dev / flagged_atom``); the trajectory goes on.  ``stop_above``: the step is completed with
+        the committee mean, then the loop freezes (status 6): ``stopped`` -> (step, molecule, atom, value), ``check()`` does not
+        raise, ``run(max_steps)`` replays until stopped, ``reset(pos, vel, step, flags="keep" | "clear")`` starts again.  An overflowed
+        neighbour list in any member freezes the loop at the last completed step and ``check()`` raises the reference's error.
+        In this version the thermostat is None or Langevin (``dict(friction=, kT=, seed=)``); a global thermostat, ``barostat``,
+        ``constraints``, ``bias``, replica exchange (``temperatures``), ``atom_weights`` and ``halo_exchange`` are refused."""
+        from torchmdnet_amd import committee
+
+        return committee.capture_md(self, z, pos, vel, masses, dt, batch, box, q, num_systems, steps_per_replay, force_scale,
+                                    thermostat, warmup, gate, atom_weights, halo_exchange, barostat, constraints, bias, temperatures)
