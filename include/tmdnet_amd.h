@@ -733,7 +733,8 @@ int tmdnet_md_advance(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws
                       const float* sigma, float dt, float c1, float c2, uint64_t seed, const int64_t* batch, float* forces_keep,
                       float* epot_log_row, float* ekin_log_row);
 /* host[0] = steps completed (the device counter), host[1] = status (1: an evaluation overflowed; the state is that of step
- * host[0].  2: a barostat move was unusable, see tmdnet_md_barostat; step host[0] is complete but for that move.  3: a constraint
+ * host[0].  2: a barostat move was unusable, see tmdnet_md_barostat and tmdnet_md_barostat_cell; step host[0] is complete but for
+ * that move.  3: a constraint
  * cluster did not converge, see tmdnet_md_advance_constrained.  4: a walker's collective variable, its gradient or its bias was not
  * finite, see tmdnet_md_bias; the state is half a step ahead of step host[0].  5: a move of a global thermostat was unusable, see
  * tmdnet_md_thermostat; step host[0] is complete but for that move).  Synchronises the stream.  Returns TMDNET_ERR_OVERFLOW for
@@ -777,6 +778,59 @@ int tmdnet_md_barostat(tmdnet_model* m, void* stream, void* graph_ws, void* md_w
                        float* box, int32_t box_mode, const float* virial, const float* ekin_row, double pressure, double kT,
                        double compressibility, double tau, double force_scale, uint64_t seed, float* volume_log_row,
                        float* pressure_log_row, float* scale_log_row);
+
+/* ---- Anisotropic cell rescaling of the device-resident MD loop (csrc/tn_md_cell.hip; additive exports, the ABI revision stays 10)
+ * The barostat above with a 3 x 3 matrix in the exponent, so that the SHAPE of the cell fluctuates: the anisotropic stochastic cell
+ * rescaling of Bernetti and Bussi (J. Chem. Phys. 153, 114107, 2020), one barostat per molecule, first order.  After the closing
+ * half of a step (tmdnet_md_advance with TMDNET_MD_CLOSE), per molecule m, in fp64, row vectors, h = box_m:
+ *     V   = |det h|                                  Kt = sum over the atoms of m of 0.5 mass v_a v_b / force_scale      (3 x 3)
+ *     P   = (2 Kt + W_m) / V                         (W of tmdnet_energy_forces_virial as returned, not symmetrised)
+ *     a   = compressibility dt / tau                 D_f = -(a / 3) (P0 I - P) + sqrt(2 kT a / (3 V)) Xi     (Xi: 9 standard normals)
+ *     D   = Pi(D_f)       mu = exp(D)       nu = exp(-D^T)                                                   (matrix exponentials)
+ * Pi projects onto the coupling's subspace (Frobenius-orthogonally):
+ *   TMDNET_CELL_ANISOTROPIC      the identity: all nine entries
+ *   TMDNET_CELL_DIAGONAL         the three diagonal entries; the off-diagonal ones are 0
+ *   TMDNET_CELL_SEMI_ISOTROPIC   diagonal, and the two entries other than `axis` are replaced by their mean
+ * Written in the exponent the Ito term of exp cancels the paper's + kT / V, so the drift is -(a / 3) (P0 - P) alone; tr D is
+ * distributed as the d of tmdnet_md_barostat in every mode.  kT = 0 is anisotropic weak coupling.  The matrix exponential scales D
+ * by 2^-s to a max-row-sum norm <= 2^-4, sums the Taylor series to degree 8 and squares s times; nu is the same routine on -D^T.
+ * Lower-triangular box (ANISOTROPIC only): h mu = L Q by Gram-Schmidt on its rows, top down, q2 = q0 x q1 (L lower triangular with a
+ * positive diagonal), and the whole system is rotated by Q^T:  box <- L,  x <- x (mu Q^T),  v <- v (nu Q^T),  F <- F Q^T  for the
+ * forces of the last evaluation (the opening kick of the next step and forces_keep; the energy is invariant).  In the two diagonal
+ * modes Q = I: box <- h mu, the matrices are diagonal (scalar exponentials) and the forces are not touched.  The forces are NOT
+ * evaluated again after the move, as for tmdnet_md_barostat.
+ * Rounding: Mx = mu Q^T, Mv = nu Q^T, Mf = Q^T and the new box are rounded to fp32 ONCE; every per-atom component is then
+ * ((x0 M0b) + (x1 M1b)) + (x2 M2b), each product and each sum one rounded fp32 operation in that order under the contract above
+ * (ONE product x_b M_bb in the diagonal modes).
+ * Noise: row r of Xi is the Box-Muller triple of one Philox4x32-10 call, key = `seed`, counter = (step low, step high, molecule,
+ * 4 + r) with `step` the value the O step of this MD step used.  Counter word 3: 0 the atoms, 1 tmdnet_md_barostat, 2
+ * tmdnet_md_exchange, 3 + 256 draw tmdnet_md_thermostat, 4 / 5 / 6 the three rows of Xi.
+ * Enqueues three launches (four when a molecule averages more than 1 024 atoms): the kinetic tensor per molecule, read from vel and
+ * mass and summed in fp64 in a fixed order without floating-point atomics (bit-identical repeats); one block that computes every
+ * molecule's move and, when all are usable, writes the matrices, the boxes and the log rows; one thread per atom that applies the
+ * matrices and, with open_next != 0, saves the scaled state and runs B, A of the next step on it.  A captured step is therefore
+ *     evaluation with the virial;  tmdnet_md_advance(TMDNET_MD_CLOSE);  tmdnet_md_barostat_cell(open_next = another step follows)
+ *   m, graph_ws, batch, box, box_mode, virial, hk, dt   as in tmdnet_md_barostat.
+ *   cell_ws       tmdnet_md_barostat_cell_workspace_bytes(n_atoms, n_mol) bytes of scratch.  After aligning the pointer up to 256
+ *                 bytes it starts with the matrices [n_mol, 27] fp32: Mx | Mv | Mf of every molecule, row-major 3 x 3 each.
+ *   mass          [n_atoms]: an atom of infinite mass contributes nothing to Kt.
+ *   forces        the forces of this step's evaluation; read with open_next only.
+ *   forces_keep   [n_atoms, 3] or NULL, in / out (ANISOTROPIC only): with open_next the rotated `forces` are stored here; without,
+ *                 it is rotated in place.  The diagonal modes leave it alone.
+ *   volume_log_row [n_mol], pressure_log_row [n_mol, 9], scale_log_row [n_mol, 9], each or NULL: V before the move, P and Mx as fp32.
+ * A move is unusable when V = 0, anything on the way to the matrices and the new box is not finite (a NaN in the virial), or
+ * det (h mu) <= 0 (a left-handed box): the status word becomes 2, box, pos, vel, forces_keep and the log rows keep their bits, and
+ * every later launch returns at once until tmdnet_md_reset.
+ * TMDNET_ERR_INVALID: what tmdnet_md_barostat refuses, a NULL mass, a coupling other than the three above, or an axis outside 0..2. */
+#define TMDNET_CELL_ANISOTROPIC 0
+#define TMDNET_CELL_DIAGONAL 1
+#define TMDNET_CELL_SEMI_ISOTROPIC 2
+int tmdnet_md_barostat_cell_workspace_bytes(int64_t n_atoms, int64_t n_mol, size_t* bytes);
+int tmdnet_md_barostat_cell(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, void* cell_ws, int64_t n_atoms, int64_t n_mol,
+                            int32_t open_next, float* pos, float* vel, const float* forces, const float* hk, const float* mass, float dt,
+                            const int64_t* batch, float* box, int32_t box_mode, const float* virial, double pressure, double kT,
+                            double compressibility, double tau, double force_scale, uint64_t seed, int32_t coupling, int32_t axis,
+                            float* forces_keep, float* volume_log_row, float* pressure_log_row, float* scale_log_row);
 
 /* ---- Temperature replica exchange of the device-resident MD loop (csrc/tn_remd.hip; additive exports, the ABI revision stays 10) -
  * Parallel tempering inside the captured graph.  n_mol = G * ladder replicas of ONE system (n = n_atoms / n_mol atoms each, replica

@@ -22,6 +22,17 @@ holds it with a cutoff of margin (same atoms, same pairs):
 same alternating blocks, median and min / max.  The coupling is weak enough that the box stays where it is (the random-weight
 potential is no force field).  Records the NPT / NVT ratio and NPT against the eager loop per size; writes profiles/md_npt.json.
 
+``--npt-cell``: the anisotropic cell barostat, on the two systems of ``--npt`` with its thermostat and barostat parameters:
+
+  (a) ``a_eager_cell``: the loop a caller builds on ``capture(virial=True)`` - one graph launch per step, Langevin integrator and an
+      anisotropic stochastic-cell-rescaling move as eager torch ops (kinetic tensor, two fp32 matrix exponentials, a QR of the new
+      box, the rotation of positions, velocities and forces), nothing read back;
+  (b) ``b_K10_isotropic``: ``capture_md(thermostat=, barostat=)`` with K = 10, the isotropic loop as it was;
+      ``b_K10_cell_anisotropic`` / ``b_K10_cell_semi_isotropic``: ``capture_md_cell`` with K = 10,
+
+same alternating blocks, median and min / max.  Records what the cell barostat costs over the isotropic one (microseconds per step
+and ratio) and against the eager loop; writes profiles/md_npt_cell.json.
+
 ``--constraints``: the constrained loop, on the 192-atom water box (rigid water: three coupled constraints per molecule) and on the
 64-atom molecule above (its X-H bonds, ``md.hydrogen_pairs``), in a state where the atoms move so that the iterations have work to
 do: dt = 2 fs, thermal velocities (300 K), and ``force_scale`` such that the random-weight model's largest initial force counts as
@@ -189,6 +200,105 @@ def npt_main(a):
         print(name, json.dumps(entry), flush=True)
         del replay, mds, legs
     out = a.out if a.out else os.path.join(ROOT, "profiles", "md_npt.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
+def npt_cell_main(a):
+    import math
+
+    import torch
+
+    import __graft_entry__ as ge
+
+    ge.build_hip(verbose=False)
+    from torchmdnet_amd import workloads as W
+    from torchmdnet_amd.models.model import create_model
+
+    dev = torch.device("cuda", 0)
+    sync = lambda: torch.cuda.synchronize(dev)
+    dt, mass_amu, fs, kT, friction, K = 1e-3, 12.0, 9.648533e-3, 0.0259, 0.01, 10
+    baro = dict(pressure=0.0, tau=1000.0 * dt, compressibility=1e-6, kT=kT, seed=2)
+    result = {"device": torch.cuda.get_device_name(dev), "model": "TensorNet F=128 L=2 (C2_ARGS), static_shapes", "steps_per_replay": K,
+              "seconds_per_block": a.seconds, "rounds": a.rounds, "dt_for_ns_per_day_fs": 1.0, "barostat": baro, "sizes": {}}
+    eye = torch.eye(3, device=dev)
+    for name in ("water192", "synthetic1024"):
+        torch.manual_seed(0)
+        model = create_model(dict(W.C2_ARGS, static_shapes=True, max_num_neighbors=128)).to(dev)
+        if name == "water192":
+            z, pos, box = W.water_box(n_side=4)
+        else:
+            z, pos, _ = W.synthetic_batch(n_mol=1, n_atoms=1024)
+            cut = float(W.C2_ARGS["cutoff_upper"])
+            pos = pos - pos.min(0).values + cut
+            box = torch.eye(3) * (float(pos.max()) + cut)
+        z, pos, box = z.to(dev), pos.to(dev).float().contiguous(), box.to(dev).float().contiguous()
+        n = int(z.shape[0])
+        batch = torch.zeros_like(z)
+        vel0 = torch.zeros_like(pos)
+        masses = torch.full((n,), mass_amu, device=dev)
+        th = dict(friction=friction, kT=kT, seed=1)
+        hk = 0.5 * dt * fs / mass_amu
+        c1 = math.exp(-friction * dt)
+        c2s = math.sqrt(1.0 - c1 * c1) * math.sqrt(kT * fs / mass_amu)
+        acoef = baro["compressibility"] * dt / baro["tau"]
+
+        ebox = box.clone()
+        replay = model.capture(z, pos, batch, ebox, virial=True)
+        vel = vel0.clone()
+        _, forces, virial = replay(pos)
+
+        def a_eager_cell():  # the anisotropic move as a caller writes it in torch: fp32 matrix exponentials and a QR of the new box
+            vel.add_(forces, alpha=hk)
+            replay.pos.add_(vel, alpha=dt)
+            replay()
+            vel.add_(forces, alpha=hk)
+            vel.mul_(c1).add_(torch.randn_like(vel), alpha=c2s)
+            kt = (vel.t() @ vel) * (0.5 * mass_amu / fs)
+            vol = torch.linalg.det(ebox).abs()
+            p = (2.0 * kt + virial[0]) / vol
+            d = (p - baro["pressure"] * eye) * (acoef / 3.0) + torch.sqrt(2.0 * kT * acoef / (3.0 * vol)) * torch.randn((3, 3), device=dev)
+            mu, nu = torch.linalg.matrix_exp(d), torch.linalg.matrix_exp(-d.t())
+            q, r = torch.linalg.qr((ebox @ mu).t())  # h mu = r^T q^T: lower triangular times a rotation
+            sign = torch.sign(torch.diagonal(r))
+            q = q * sign
+            ebox.copy_((r * sign[:, None]).t())
+            torch.matmul(replay.pos @ mu, q, out=replay.pos)
+            torch.matmul(vel @ nu, q, out=vel)
+            forces.copy_(forces @ q)  # the next opening kick reads them in the rotated frame
+
+        legs = {"a_eager_cell": (a_eager_cell, 1)}
+        iso = model.capture_md(z, pos, vel0, masses, dt, batch=batch, box=box.clone(), steps_per_replay=K, force_scale=fs, thermostat=th,
+                               barostat=baro)
+        legs["b_K10_isotropic"] = (iso, K)
+        mds = [iso]
+        for leg, coupling in (("b_K10_cell_anisotropic", "anisotropic"), ("b_K10_cell_semi_isotropic", "semi-isotropic")):
+            md = model.capture_md_cell(z, pos, vel0, masses, dt, batch=batch, box=box.clone(), steps_per_replay=K, force_scale=fs,
+                                       thermostat=th, barostat=dict(baro, coupling=coupling))
+            mds.append(md)
+            legs[leg] = (md, K)
+        times = {k: [] for k in legs}
+        for _ in range(a.rounds):  # alternating blocks: every round visits every leg once
+            for k, (fn, spc) in legs.items():
+                times[k].append(_block(fn, spc, a.seconds, sync))
+        for md in mds:
+            md.check()  # raises if a trajectory overflowed or a move was unusable: its timings would be of a frozen loop
+        entry = _summary(times)
+        entry["n_atoms"] = n
+        entry["volume_ratio_end"] = {"eager": float(torch.linalg.det(ebox).abs() / torch.linalg.det(box).abs()),
+                                     "capture_md_cell": float(torch.linalg.det(mds[1].box).abs() / torch.linalg.det(box).abs())}
+        iso_ms = entry["b_K10_isotropic"]["ms_per_step"]
+        for leg in ("b_K10_cell_anisotropic", "b_K10_cell_semi_isotropic"):
+            entry[leg]["us_per_step_over_isotropic"] = 1e3 * (entry[leg]["ms_per_step"] - iso_ms)
+            entry[leg]["ratio_over_isotropic"] = entry[leg]["ms_per_step"] / iso_ms
+            entry[leg]["ratio_over_eager_cell"] = entry[leg]["ms_per_step"] / entry["a_eager_cell"]["ms_per_step"]
+        entry["cell_not_slower_than_eager"] = entry["b_K10_cell_anisotropic"]["ms_per_step"] <= entry["a_eager_cell"]["ms_per_step"]
+        result["sizes"][name] = entry
+        print(name, json.dumps(entry), flush=True)
+        del replay, mds, legs
+    out = a.out if a.out else os.path.join(ROOT, "profiles", "md_npt_cell.json")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(result, fh, indent=1)
@@ -629,6 +739,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--sizes", type=int, nargs="+", default=[64, 256, 1024])
     ap.add_argument("--npt", action="store_true", help="time the constant-pressure loop instead (profiles/md_npt.json)")
+    ap.add_argument("--npt-cell", action="store_true", help="time the anisotropic cell barostat instead (profiles/md_npt_cell.json)")
     ap.add_argument("--constraints", action="store_true", help="time the constrained loop instead (profiles/md_constraints.json)")
     ap.add_argument("--remd", action="store_true", help="time temperature replica exchange instead (key 'timing' of profiles/md_remd.json)")
     ap.add_argument("--bias", action="store_true", help="time restraints and metadynamics instead (key 'timing' of profiles/md_bias.json)")
@@ -639,6 +750,8 @@ def main():
     a = ap.parse_args()
     if a.npt:
         return npt_main(a)
+    if a.npt_cell:
+        return npt_cell_main(a)
     if a.constraints:
         return constraints_main(a)
     if a.remd:

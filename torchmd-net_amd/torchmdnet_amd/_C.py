@@ -210,6 +210,9 @@ def lib():
     L.tmdnet_md_barostat_workspace_bytes.argtypes = [i64, C.POINTER(sz)]
     L.tmdnet_md_barostat.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, f64, f64, f64, f64, f64,
                                      u64, vp, vp, vp]
+    L.tmdnet_md_barostat_cell_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
+    L.tmdnet_md_barostat_cell.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, f64, f64, f64, f64,
+                                          f64, u64, i32, i32, vp, vp, vp, vp]
     L.tmdnet_md_thermostat_workspace_bytes.argtypes = [i64, i32, C.POINTER(sz)]
     L.tmdnet_md_thermostat.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, f64, f64, i32, i32, f64, u64,
                                        vp, vp]

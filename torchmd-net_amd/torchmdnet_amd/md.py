@@ -14,6 +14,9 @@ replicas of one system and exchanges their temperatures inside the graph (csrc/t
 ``TorchMD_Net.capture_md_global`` (``DeviceGlobalMD``) replaces the Langevin O step by a global thermostat per molecule - stochastic
 velocity rescaling or a Nose-Hoover chain - that scales all velocities of a molecule by one factor (csrc/tn_md_thermo.hip,
 ``tmdnet_md_thermostat``: two launches between the closing and the opening half of a step).
+``TorchMD_Net.capture_md_cell`` (``DeviceCellMD``) lets the SHAPE of the cell fluctuate: the barostat's exponent is a 3 x 3 matrix
+(anisotropic, diagonal or semi-isotropic coupling; csrc/tn_md_cell.hip, ``tmdnet_md_barostat_cell``: three launches after the closing
+half), and in anisotropic mode the box is kept lower triangular by rotating positions, velocities and forces with it.
 ``Ensemble.capture_md`` (``torchmdnet_amd.committee.DeviceCommitteeMD``) drives the loop with the mean force of a committee of models
 and gates it on the members' disagreement inside the graph (csrc/tn_committee.hip).
 The capture sequence, the stale-graph guard, ``md(n)``, the status read-back and the skeleton of ``reset`` are those of every
@@ -39,6 +42,8 @@ FORCE_SCALE_EV_A_AMU_FS = 9.648533e-3
 BAR_IN_EV_PER_A3 = 6.2415091e-7
 
 _BAROSTAT_KEYS = ("pressure", "tau", "compressibility", "kT", "seed")
+#: ``coupling`` of the cell barostat -> TMDNET_CELL_* of include/tmdnet_amd.h
+CELL_COUPLINGS = {"anisotropic": 0, "diagonal": 1, "semi-isotropic": 2}
 _CONSTRAINT_KEYS = ("pairs", "lengths", "tol", "max_iter")
 
 
@@ -62,6 +67,25 @@ def parse_barostat(barostat, thermostat):
     out["seed"] = int(b["seed"]) & (2 ** 64 - 1)
     if not out["tau"] > 0 or not out["compressibility"] > 0 or not out["kT"] >= 0:
         raise ValueError(f"barostat: tau and compressibility must be positive and kT must not be negative, got {out}")
+    return out
+
+
+def parse_cell_barostat(barostat, thermostat):
+    """``barostat=dict(pressure=, tau=, compressibility=, kT=, seed=, coupling="anisotropic", axis=2)`` of ``capture_md_cell`` -> the same
+    with every key present: ``parse_barostat`` for the first five, ``coupling`` one of ``CELL_COUPLINGS`` and ``axis`` 0, 1 or 2 (the
+    axis that moves on its own in "semi-isotropic" mode; ignored by the other two).  Raises ValueError."""
+    if barostat is None:
+        raise ValueError("capture_md_cell needs barostat=dict(pressure=, tau=, compressibility=, kT=, ...); without one use capture_md")
+    b = dict(barostat)
+    coupling, axis = b.pop("coupling", "anisotropic"), b.pop("axis", 2)
+    out = parse_barostat(b, thermostat)
+    if not all(math.isfinite(out[k]) for k in ("pressure", "tau", "compressibility", "kT")):
+        raise ValueError(f"barostat: pressure, tau, compressibility and kT must be finite, got {out}")
+    if coupling not in CELL_COUPLINGS:
+        raise ValueError(f"barostat: coupling must be one of {', '.join(CELL_COUPLINGS)}, got {coupling!r}")
+    if isinstance(axis, bool) or not isinstance(axis, int) or not 0 <= axis <= 2:
+        raise ValueError(f"barostat: axis must be 0, 1 or 2, got {axis!r}")
+    out.update(coupling=coupling, axis=axis)
     return out
 
 
@@ -449,6 +473,74 @@ class DeviceMD(CapturedLoop):
         if self.constraints is not None:
             self.check()
         return self
+
+
+class DeviceCellMD(DeviceMD):
+    """The object ``TorchMD_Net.capture_md_cell`` returns: ``DeviceMD`` whose every step ends with an anisotropic, diagonal or
+    semi-isotropic stochastic-cell-rescaling move per molecule inside the graph (``tmdnet_md_barostat_cell``, csrc/tn_md_cell.hip; the
+    scheme is documented in include/tmdnet_amd.h and DESIGN.md section 13), so the cell's shape fluctuates and not only its volume.
+    ``cell_barostat`` is the parsed dict.  ``box`` is the static box the graph reads AND writes (the caller's own object when it needed
+    no conversion); in "anisotropic" mode it is lower triangular after every move, the whole system having been rotated with it:
+    ``forces`` are the forces of the last evaluation in the frame of ``pos``.  Logs of the last replay's steps: ``volume`` [K,B]
+    (before the move), ``pressure_tensor`` [K,B,3,3] and ``scale`` [K,B,3,3], the fp32 matrix Mx that took the positions through the
+    move (x <- x Mx).  The minimum image is exact only while the off-diagonal entries of the box stay below half the diagonal ones, as
+    for any triclinic box: there is no lattice reduction."""
+
+    _capture_name = "capture_md_cell"
+
+    def __init__(self, model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup, barostat):
+        self.cell_barostat = barostat
+        self._cell_ready = False
+        super().__init__(model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup)
+
+    def _stage_cell(self):
+        dev, K, B = self.pos.device, self.steps_per_replay, self.n_mol
+        self.volume = torch.zeros((K, B), dtype=torch.float32, device=dev)
+        self.pressure_tensor = torch.zeros((K, B, 3, 3), dtype=torch.float32, device=dev)
+        self.scale = torch.zeros((K, B, 3, 3), dtype=torch.float32, device=dev)
+        nbytes = C.c_size_t(0)
+        if _C.lib().tmdnet_md_barostat_cell_workspace_bytes(self.n_atoms, B, C.byref(nbytes)) != _C.OK:
+            raise ValueError(f"capture_md_cell: {self.n_atoms} atoms in {B} molecules are not a valid layout")
+        self._cell_ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
+        self._cell_ready = True
+
+    def _start(self, step):
+        if not self._cell_ready:
+            self._stage_cell()
+
+    def _evaluate(self):
+        z, batch, box, q = self.inputs
+        return self._model.energy_and_forces(z, self.pos, batch, box, q, self.n_mol, want_forces=True, want_virial=True)
+
+    def matrices(self):
+        """-> (Mx, Mv, Mf) [B,3,3] float32 clones of the last move's matrices, from the scratch of ``tmdnet_md_barostat_cell``"""
+        off = (-self._cell_ws.data_ptr()) % 256
+        M = self._cell_ws[off:off + 108 * self.n_mol].view(torch.float32).view(self.n_mol, 3, 3, 3)
+        return M[:, 0].clone(), M[:, 1].clone(), M[:, 2].clone()
+
+    def _cell_move(self, open_next, forces, virial, k):
+        st, dev, b = self._model._engine, self.pos.device, self.cell_barostat
+        rc = _C.lib().tmdnet_md_barostat_cell(
+            st.handle, _stream_ptr(dev), _ptr(st.graph_ws), _ptr(self._ws), _ptr(self._cell_ws), self.n_atoms, self.n_mol, int(open_next),
+            _ptr(self.pos), _ptr(self.vel), _ptr(forces), _ptr(self.hk), _ptr(self.masses), self.dt, _ptr(self.inputs[1]), _ptr(self.box),
+            1 if self.box.dim() == 2 else 2, _ptr(virial), b["pressure"], b["kT"], b["compressibility"], b["tau"], self.force_scale,
+            b["seed"], CELL_COUPLINGS[b["coupling"]], b["axis"], _ptr(self.forces), _ptr(self.volume[k]), _ptr(self.pressure_tensor[k]),
+            _ptr(self.scale[k]))
+        if rc != _C.OK:
+            raise RuntimeError(f"tmdnet_md_barostat_cell: {_C.lib().tmdnet_last_error(st.handle).decode()} (code {rc})")
+
+    def _capture_step(self, k, K, out):
+        # the closing half (kick, O step, step counter), then the move: the kinetic tensor is reduced from the closed velocities
+        self._advance(MD_CLOSE, out[1], out[0], k)
+        self._cell_move(k + 1 < K, out[1], out[2], k)
+
+    def check(self) -> int:
+        """``DeviceMD.check``; an unusable move of the cell barostat (status 2) is reported under its own name"""
+        step, status = self._status(_C.lib().tmdnet_md_status, 2)[1]
+        if status == 2:
+            raise RuntimeError(f"cell barostat ({self.cell_barostat['coupling']}): the move after step {step} was unusable (zero volume, a "
+                               "NaN in the virial or the kinetic tensor, or a left-handed box); the MD state is frozen before that move")
+        return super().check()
 
 
 def geometric_ladder(kT_min, kT_max, R):

@@ -1682,6 +1682,41 @@ class TorchMD_Net(nn.Module):
         stage_ndof(th["ndof"], count_ndof(masses, batch, n_mol, constraints), n_mol)
         return DeviceGlobalMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, warmup, th, constraints)
 
+    def capture_md_cell(self, z: Tensor, pos: Tensor, vel: Tensor, masses: Tensor, dt: float, batch: Optional[Tensor] = None,
+                        box: Optional[Tensor] = None, q: Optional[Tensor] = None, num_systems: Optional[int] = None,
+                        steps_per_replay: int = 10, force_scale: float = 1.0, thermostat: Optional[dict] = None, warmup: int = 3,
+                        barostat: Optional[dict] = None):
+        """``capture_md`` at constant pressure with a cell whose SHAPE fluctuates (crystals, slabs, membranes, solid-solid
+        transitions): after every step an anisotropic stochastic-cell-rescaling move per molecule (Bernetti and Bussi 2020, written in
+        the exponent) multiplies ``md.box`` and the positions by a 3 x 3 matrix mu = exp(D) and the velocities by exp(-D^T) inside the
+        graph (``tmdnet_md_barostat_cell``: three launches after the closing half), from the full virial of that step's evaluation and
+        the kinetic tensor.  ``barostat=dict(pressure=, tau=, compressibility=, kT=, seed=, coupling=, axis=2)``: the keys of
+        ``capture_md``'s barostat with their units and defaults, plus ``coupling``:
+        ``"anisotropic"`` (default) all nine entries of D; the box is kept lower triangular by rotating the whole system (positions,
+        velocities and the forces of the last evaluation) with it;
+        ``"diagonal"`` the three box lengths move independently, the angles stay;
+        ``"semi-isotropic"`` ``axis`` moves on its own and the other two lengths share one strain (slabs and membranes).
+        The target is hydrostatic (``pressure`` times the identity); ``kT=0`` is anisotropic weak coupling.  ``thermostat`` is the
+        Langevin dict of ``capture_md`` or None.  Needs a box per molecule ([3,3] for one molecule, [B,3,3] otherwise) and an
+        architecture with a virial (TensorNet, Equivariant Transformer; scalar head).  There is no lattice reduction: the minimum image
+        is exact only while the box's off-diagonal entries stay below half its diagonal ones.
+        Returns a ``torchmdnet_amd.md.DeviceCellMD``: ``DeviceMD``'s surface plus ``md.box``, ``md.volume`` [K,B],
+        ``md.pressure_tensor`` [K,B,3,3], ``md.scale`` [K,B,3,3] and ``md.reset(pos=, vel=, box=)``; ``md.check()`` names the cell barostat
+        when a move was unusable.  Not offered, so not parameters of this method: constraints, a bias, replica exchange, global
+        thermostats, atom weights and the halo exchange."""
+        from torchmdnet_amd.md import DeviceCellMD, parse_cell_barostat
+
+        baro = parse_cell_barostat(barostat, thermostat)  # everything below is refused before anything is allocated or captured
+        self._refuse_virial()
+        z, batch, box, q, n_mol, _ = self._capture_inputs("capture_md_cell", "molecular dynamics needs", z, pos, batch, box, q, num_systems,
+                                                          steps_per_replay, box_moves=True)
+        if box is None:
+            raise ValueError("capture_md_cell needs a box: the barostat moves it")
+        if box.dim() == 2 and n_mol > 1:
+            raise NotImplementedError("capture_md_cell has one barostat per molecule: give every molecule its own box "
+                                      f"[{n_mol},3,3], not one shared [3,3] box")
+        return DeviceCellMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup, baro)
+
     def capture_remd(self, z: Tensor, pos: Tensor, vel: Optional[Tensor], masses: Tensor, dt: float, temperatures=None,
                      exchange_every: int = 100, box: Optional[Tensor] = None, q: Optional[Tensor] = None, steps_per_replay: int = 100,
                      force_scale: float = 1.0, thermostat: Optional[dict] = None, warmup: int = 3, atom_weights=None,
