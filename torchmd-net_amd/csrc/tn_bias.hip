@@ -20,8 +20,6 @@
 // closing launch then restores the state and latches status 1).  A walker that meets a value that is not finite leaves its forces
 // alone, deposits nothing, writes no log row and stores status 4 (every writer stores the same constant); the closing launch, next
 // in stream order, then returns at once, so the state stays where the opening half left it.
-#include <string>
-
 #include "tmdnet_amd.h"
 #include "tn_bias_math.h"
 #include "tn_common.h"
@@ -58,6 +56,18 @@ struct BiasArgs {
   MdState st;
 };
 
+struct BiasWs {  // views into the caller's bias workspace
+  uint64_t* head;  // [0] step0, [1] hill_base
+  double* hills;   // [G, dm + 1, H] (dm > 0 only)
+};
+
+inline BiasWs bias_layout(LoopCarver& c, int64_t G, int dm, int64_t H) {
+  BiasWs w;
+  w.head = c.take<uint64_t>(kHeaderBytes / sizeof(uint64_t));
+  w.hills = c.take<double>(dm > 0 ? (size_t)G * (size_t)(dm + 1) * (size_t)H : 0);
+  return w;
+}
+
 __device__ __forceinline__ void load3(const float* pos, int64_t i, int N, double x[3]) {
   const bool ok = i >= 0 && i < N;  // an index outside the batch reads nothing: the CV is not finite, the walker reports status 4
 #pragma unroll
@@ -85,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void k_md_bias(BiasArgs a) {
   }
   __syncthreads();
   if (sh_frozen) return;
-  const uint64_t n = (uint64_t)a.st.head[0] | ((uint64_t)a.st.head[1] << 32);
+  const uint64_t n = loop_step(a.st.head);
   const int64_t start = a.mol_start[b];
   if (t < a.D) {
     const int kind = a.cv_kind[t];
@@ -212,16 +222,15 @@ extern "C" {
 int tmdnet_md_bias_workspace_bytes(int64_t n_mol, int32_t n_cv, int32_t n_metad_cv, int32_t walkers_per_group, int64_t capacity,
                                    size_t* bytes) {
   if (!bytes || !bias_layout_ok(n_mol, n_cv, n_metad_cv, walkers_per_group, capacity)) return TMDNET_ERR_INVALID;
-  const size_t G = (size_t)(n_mol / walkers_per_group);
-  const size_t hills = n_metad_cv > 0 ? G * (size_t)(n_metad_cv + 1) * (size_t)capacity * sizeof(double) : 0;
-  *bytes = kHeaderBytes + align256(hills) + 256;  // the header, the hills, and room to align the caller's pointer
+  *bytes = layout_bytes([&](LoopCarver& c) { bias_layout(c, n_mol / walkers_per_group, n_metad_cv, capacity); });
   return TMDNET_OK;
 }
 
 int tmdnet_md_bias_reset(void* stream, void* bias_ws, uint64_t step0, uint64_t hill_base) {
   if (!bias_ws) return TMDNET_ERR_INVALID;
-  uint64_t* head = reinterpret_cast<uint64_t*>(align256(reinterpret_cast<size_t>(bias_ws)));
-  hipLaunchKernelGGL(k_md_bias_reset, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), head, step0, hill_base);
+  LoopCarver c(bias_ws);
+  hipLaunchKernelGGL(k_md_bias_reset, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), bias_layout(c, 0, 0, 0).head, step0,
+                     hill_base);
   return hipGetLastError() == hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
 }
 
@@ -273,20 +282,18 @@ int tmdnet_md_bias(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, v
   a.gamma = bias_factor;
   a.pace = dm > 0 ? (uint64_t)pace : 1u;
   a.H = capacity;
-  char* p = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(bias_ws)));
-  a.head = reinterpret_cast<uint64_t*>(p);
-  a.hills = reinterpret_cast<double*>(p + kHeaderBytes);
+  LoopCarver c(bias_ws);
+  const BiasWs w = bias_layout(c, n_mol / walkers_per_group, dm, capacity);
+  a.head = w.head;
+  a.hills = w.hills;
   a.cv_row = cv_log_row;
   a.res_row = restraint_log_row;
   a.bias_row = bias_log_row;
   a.force_row = force_log_row;
-  a.counts = nullptr;
+  a.counts = loop_graph(m, graph_ws, n_atoms, n_mol).counts;
   a.st = carve_md(md_ws, n_atoms, n_mol);
-  if (graph_ws) a.counts = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr).counts;
   hipLaunchKernelGGL(k_md_bias, dim3(a.B), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_md_bias: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
-  return TMDNET_OK;
+  return loop_launch_result(m, "tmdnet_md_bias");
 }
 
 }  // extern "C"

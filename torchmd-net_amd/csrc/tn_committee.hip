@@ -42,21 +42,22 @@ struct CommitteeWs {  // views into the caller's workspace
   int32_t* flag_now;  // [B] 1: the molecule was flagged by the pass before this latch
 };
 
-inline size_t committee_bytes(int64_t B) {
+inline CommitteeWs committee_layout(LoopCarver& c, int64_t B) {
   const size_t b = (size_t)(B > 0 ? B : 0);
-  return kHeaderBytes + align256(b * sizeof(uint64_t)) + align256(b * sizeof(int32_t)) + 256;  // room to align the caller's pointer
+  CommitteeWs w;
+  w.head = c.take<uint64_t>(kHeaderBytes / sizeof(uint64_t));
+  w.packed = c.take<uint64_t>(b);
+  w.flag_now = c.take<int32_t>(b);
+  return w;
+}
+
+inline size_t committee_bytes(int64_t B) {
+  return layout_bytes([&](LoopCarver& c) { committee_layout(c, B); });
 }
 
 inline CommitteeWs carve_committee(void* ws, int64_t B) {
-  char* p = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(ws)));
-  const size_t b = (size_t)(B > 0 ? B : 0);
-  CommitteeWs c;
-  c.head = reinterpret_cast<uint64_t*>(p);
-  p += kHeaderBytes;
-  c.packed = reinterpret_cast<uint64_t*>(p);
-  p += align256(b * sizeof(uint64_t));
-  c.flag_now = reinterpret_cast<int32_t*>(p);
-  return c;
+  LoopCarver c(ws);
+  return committee_layout(c, B);
 }
 
 struct CommitteeArgs {
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(kThreads) void k_committee_mols(CommitteeArgs a) {
   int now = 0;
   if ((a.flags & TMDNET_COMMITTEE_FLAG) && a.flagged_at[m] < 0 && tn_committee::gate_fires(D, a.flag_above)) {
     // the step this evaluation closes: the counter is advanced by the closing launch, after this one
-    const uint64_t step = ((uint64_t)a.md_head[0] | ((uint64_t)a.md_head[1] << 32)) + 1;
+    const uint64_t step = loop_step(a.md_head) + 1;
     a.flagged_at[m] = (int64_t)step;
     a.flagged_dev[m] = D;
     a.flagged_atom[m] = at;
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void k_committee_latch(LatchArgs a) {
         tn_committee::unpack(w, &D, &mol);
         a.md_head[2] = 6u;  // (no other thread of this launch reads the status word)
         a.ws.head[1] = 1;
-        a.ws.head[2] = (uint64_t)a.md_head[0] | ((uint64_t)a.md_head[1] << 32);
+        a.ws.head[2] = loop_step(a.md_head);
         a.ws.head[3] = (uint64_t)mol;
         a.ws.head[4] = (uint64_t)a.max_atom[mol];
         a.ws.head[5] = tn_committee::float_bits(D);
@@ -299,7 +300,7 @@ int tmdnet_committee_reduce(void* stream, void* ws, size_t ws_bytes, int32_t n_m
     a.f[k] = forces[j];
     a.counts[k] = nullptr;
     if (members) {
-      int* c = carve_graph(graph_ws[j], n_atoms, n_mol, (int64_t)members[j]->hp.max_num_neighbors * n_atoms, nullptr).counts;
+      int* c = loop_graph(members[j], graph_ws[j], n_atoms, n_mol).counts;
       a.counts[k] = c;
       if (k == 0) a.counts0 = c;
     }

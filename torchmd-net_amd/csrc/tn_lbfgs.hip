@@ -26,20 +26,18 @@
 // spare slot; a sum that is not finite latches status 2 before anything of that step is written.  From then on every launch
 // returns at once until tmdnet_lbfgs_reset.  Nothing allocates or synchronises; everything is capturable.
 #include <cmath>
-#include <string>
 
 #include "tmdnet_amd.h"
 #include "tn_common.h"
 #include "tn_lbfgs_math.h"
+#include "tn_loop.h"
 #include "tn_model.h"
 
 namespace tn {
 
 namespace {
 
-constexpr int kLbThreads = 256;
 constexpr int kLbDotsThreads = 1024;  // sixteen waves share the h + 1 tasks of a slice
-constexpr size_t kLbHeaderBytes = 256;
 constexpr int kLbCtlWaves = 4;  // molecules per block of the controller
 
 // doubles of LDS per wave of the controller: delta [2 M1 + 1], av [M1] and the ring order as M1 int32 (<= 57 504 B per block at memory 512)
@@ -65,30 +63,22 @@ struct LbState {  // views into the caller's workspace
   float* ringY;     // [M1, N, 3]
 };
 
-inline size_t lb_align256(size_t n) { return (n + 255) & ~size_t(255); }
-
-int lb_slices(int64_t N, int64_t B) {
-  if (B <= 0 || N <= 1024 * B) return 1;
-  const int64_t s = (N + 1024 * B - 1) / (1024 * B);
-  return (int)(s > 256 ? 256 : s);
-}
-
 // the byte offsets of the sixteen arrays behind the 256-aligned base, then the total
 void lb_layout(int64_t N, int64_t B, int64_t memory, size_t off[17]) {
   const size_t n = (size_t)(N > 0 ? N : 0), b = (size_t)(B > 0 ? B : 0), M1 = (size_t)memory + 1, NP = 6 * M1 + 4;
-  const size_t S = (size_t)lb_slices(N, B);
-  const size_t sizes[16] = {kLbHeaderBytes, b * 4,          b * 8,      b * M1 * 4, b * M1 * M1 * 8, b * M1 * M1 * 8, b * M1 * M1 * 8, b * (2 * M1 + 1) * 8,
+  const size_t S = (size_t)mol_slices(N, B);
+  const size_t sizes[16] = {kHeaderBytes, b * 4,          b * 8,      b * M1 * 4, b * M1 * M1 * 8, b * M1 * M1 * 8, b * M1 * M1 * 8, b * (2 * M1 + 1) * 8,
                             b * NP * 8,     b * S * NP * 8, b * S * 8,  n * 12,     n * 12,          M1 * n * 12,     M1 * n * 12,     b * 4};
   size_t at = 0;
   for (int k = 0; k < 16; ++k) {
     off[k] = at;
-    at += lb_align256(sizes[k]);
+    at += align256(sizes[k]);
   }
   off[16] = at;
 }
 
 LbState carve_lb(void* ws, int64_t N, int64_t B, int64_t memory) {
-  char* p = reinterpret_cast<char*>(lb_align256(reinterpret_cast<size_t>(ws)));
+  char* p = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(ws)));
   size_t off[17];
   lb_layout(N, B, memory, off);
   LbState st;
@@ -111,31 +101,6 @@ LbState carve_lb(void* ws, int64_t N, int64_t B, int64_t memory) {
   return st;
 }
 
-__device__ __forceinline__ uint64_t lb_step(const LbState& st) { return (uint64_t)st.head[0] | ((uint64_t)st.head[1] << 32); }
-
-struct LbRange {  // the atoms slice s of molecule m strides, and whether they are filtered by `batch`
-  int i0, i1;
-  bool filter;
-};
-
-__device__ __forceinline__ LbRange lb_range(const int* counts, const int* mstart, const int* mend, int N, int S, const int64_t* batch, int m,
-                                            int s) {
-  LbRange r;
-  r.filter = counts ? counts[3] != 0 : batch != nullptr;
-  int a = 0, b = N;
-  if (counts && !r.filter) {
-    a = mstart[m];
-    b = mend[m];
-    a = a < 0 ? 0 : a;
-    b = b > N ? N : b;
-    b = b < a ? a : b;
-  }
-  const int64_t len = b - a;
-  r.i0 = a + (int)(len * s / S);
-  r.i1 = a + (int)(len * (s + 1) / S);
-  return r;
-}
-
 // grid (B, S): slice s of molecule m -> part[m, s, :].  Task t = 0 .. h - 1: the six sums against the pair at ring position t; the
 // last task: the candidate against itself (it also stores the candidate), ff and fmax2.  Wave w takes the tasks w, w + 16, ...
 __global__ __launch_bounds__(kLbDotsThreads) void k_lbfgs_dots(LbState st, const int* __restrict__ counts, const int* __restrict__ mstart,
@@ -155,7 +120,7 @@ __global__ __launch_bounds__(kLbDotsThreads) void k_lbfgs_dots(LbState st, const
   const bool moved = !fresh && st.conv[m] < 0;  // a move preceded this evaluation: there is a candidate
   const int h = moved ? st.h[m] : 0;
   const int32_t* order = st.order + (int64_t)m * M1;
-  const LbRange r = lb_range(counts, mstart, mend, N, S, batch, m, s);
+  const SliceRange r = mol_slice_range(counts, mstart, mend, N, S, batch, m, s);
   const int NP = 6 * M1 + 4;
   double* out = st.part + ((int64_t)m * S + s) * NP;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -166,7 +131,7 @@ __global__ __launch_bounds__(kLbDotsThreads) void k_lbfgs_dots(LbState st, const
     float* Ya = st.ringY + (int64_t)a * N * 3;
     double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int i = r.i0 + lane; i < r.i1; i += 64) {
-      if (r.filter && batch && batch[i] != m) continue;  // (no batch vector: one molecule)
+      if (slice_skips(r, batch, i, m)) continue;
       const int fx = fixed && fixed[i];
       float x[3], xp[3], f[3], fp[3], g[3], sc[3] = {0.f, 0.f, 0.f}, yc[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -214,13 +179,7 @@ __global__ __launch_bounds__(kLbDotsThreads) void k_lbfgs_dots(LbState st, const
         acc[7] = t_ff > acc[7] ? t_ff : acc[7];
       }
     }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-#pragma unroll
-      for (int k = 0; k < 7; ++k) acc[k] += __shfl_xor(acc[k], o, 64);
-      const double other = __shfl_xor(acc[7], o, 64);
-      acc[7] = other > acc[7] ? other : acc[7];
-    }
+    wave_reduce<8, 1u << 7>(acc);  // (per wave, not per block: a wave owns its task)
     if (lane == 0) {
       if (moved) {
         acc[2] = last ? acc[1] : acc[2];  // (y_c.s_c is s_c.y_c)
@@ -278,7 +237,7 @@ __global__ __launch_bounds__(64 * kLbCtlWaves) void k_lbfgs_control(LbCtlArgs a)
     return;
   }
   const bool fresh = st.head[7] != 0;
-  const uint64_t step = ((uint64_t)st.head[4] | ((uint64_t)st.head[5] << 32)) + (fresh ? 0 : 1);
+  const uint64_t step = loop_step(st.head + 4) + (fresh ? 0 : 1);
   const int M1 = a.p.memory + 1, NP = 6 * M1 + 4;
   int flag = 0;
   for (int m = threadIdx.x; m < a.B; m += blockDim.x) {
@@ -353,28 +312,27 @@ __global__ __launch_bounds__(64 * kLbCtlWaves) void k_lbfgs_control(LbCtlArgs a)
     }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    st.head[0] = (uint32_t)step;
-    st.head[1] = (uint32_t)(step >> 32);
+    loop_set_step(st.head, step);
     st.head[3] = 0u;
   }
 }
 
 // grid (B, S): the direction of every atom of slice s of molecule m from the coefficients, and the slice maximum of |p_i|^2
-__global__ __launch_bounds__(kLbThreads) void k_lbfgs_direction(LbState st, const int* __restrict__ counts, const int* __restrict__ mstart,
+__global__ __launch_bounds__(kThreads) void k_lbfgs_direction(LbState st, const int* __restrict__ counts, const int* __restrict__ mstart,
                                                                 const int* __restrict__ mend, int N, int B, int S, int M1,
                                                                 const int64_t* __restrict__ batch, const float* __restrict__ forces,
                                                                 const uint8_t* __restrict__ fixed, float* __restrict__ direction) {
-  __shared__ double sh[kLbThreads / 64];
+  __shared__ double sh[1][kThreads / 64];
   if (st.head[2]) return;  // frozen (an overflow: the controller has just latched it)
   const int m = blockIdx.x, s = blockIdx.y;
   if (st.conv[m] >= 0) return;  // converged: it never moves again
   const int h = st.h[m];
   const int32_t* order = st.order + (int64_t)m * M1;
   const double* delta = st.delta + (int64_t)m * (2 * M1 + 1);
-  const LbRange r = lb_range(counts, mstart, mend, N, S, batch, m, s);
-  double mx = 0.0;
-  for (int i = r.i0 + (int)threadIdx.x; i < r.i1; i += kLbThreads) {
-    if (r.filter && batch && batch[i] != m) continue;
+  const SliceRange r = mol_slice_range(counts, mstart, mend, N, S, batch, m, s);
+  double mx[1] = {0.0};
+  for (int i = r.i0 + (int)threadIdx.x; i < r.i1; i += kThreads) {
+    if (slice_skips(r, batch, i, m)) continue;
     float f[3], p[3] = {0.f, 0.f, 0.f};
     if (!(fixed && fixed[i])) {
 #pragma unroll
@@ -384,19 +342,10 @@ __global__ __launch_bounds__(kLbThreads) void k_lbfgs_direction(LbState st, cons
 #pragma unroll
     for (int d = 0; d < 3; ++d) direction[i * 3 + d] = p[d];
     const double n2 = tn_lbfgs::dot3w(p, p);
-    mx = n2 > mx ? n2 : mx;
+    mx[0] = n2 > mx[0] ? n2 : mx[0];
   }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double other = __shfl_xor(mx, o, 64);
-    mx = other > mx ? other : mx;
-  }
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kLbThreads / 64; ++w) mx = sh[w] > mx ? sh[w] : mx;
-    st.dmax[(int64_t)m * S + s] = mx;
-  }
+  block_reduce_waves<1, 1u>(mx, sh);
+  if (threadIdx.x == 0) st.dmax[(int64_t)m * S + s] = block_reduce_row(sh[0], true);
 }
 
 struct LbAtomArgs {
@@ -422,8 +371,8 @@ __device__ __forceinline__ float lb_scale(const LbAtomArgs& a, int64_t m) {
 // controller): keep the forces of the evaluation, or, when it overflowed, go back to the positions the last move saved.  MOVE: save
 // x and F, then x <- x + c p.
 template <bool ACCEPT, bool MOVE>
-__global__ __launch_bounds__(kLbThreads) void k_lbfgs_move(LbAtomArgs a) {
-  const int i = blockIdx.x * kLbThreads + threadIdx.x;
+__global__ __launch_bounds__(kThreads) void k_lbfgs_move(LbAtomArgs a) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
   const uint32_t status = a.st.head[2], fresh = a.st.head[3];
   if (status) {
     // the evaluation before this launch overflowed (the controller has just latched it): back to the last completed step.  A
@@ -463,8 +412,7 @@ __global__ __launch_bounds__(kLbThreads) void k_lbfgs_move(LbAtomArgs a) {
 
 __global__ void k_lbfgs_reset(LbState st, uint64_t step0) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    st.head[0] = (uint32_t)step0;
-    st.head[1] = (uint32_t)(step0 >> 32);
+    loop_set_step(st.head, step0);
     st.head[2] = 0u;
     st.head[3] = 1u;
     st.head[8] = 0u;
@@ -520,19 +468,12 @@ int tmdnet_lbfgs_advance(tmdnet_model* m, void* stream, void* graph_ws, void* lb
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int N = (int)n_atoms, B = (int)n_mol, M1 = memory + 1;
   const LbState st = carve_lb(lbfgs_ws, n_atoms, n_mol, memory);
-  const int* counts = nullptr;
-  const int* mstart = nullptr;
-  const int* mend = nullptr;
-  if (graph_ws) {
-    const Graph g = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr);
-    counts = g.counts;
-    mstart = g.mstart;
-    mend = g.mend;
-  }
-  const dim3 block(kLbThreads);
-  const int S = lb_slices(n_atoms, n_mol);
+  const LoopGraph g = loop_graph(m, graph_ws, n_atoms, n_mol);
+  const int* counts = g.counts;
+  const dim3 block(kThreads);
+  const int S = mol_slices(n_atoms, n_mol);
   if (phase != TMDNET_MIN_OPEN) {
-    hipLaunchKernelGGL(k_lbfgs_dots, dim3(B, S), dim3(kLbDotsThreads), 0, s, st, counts, mstart, mend, N, B, S, M1, batch, pos, forces, fixed);
+    hipLaunchKernelGGL(k_lbfgs_dots, dim3(B, S), dim3(kLbDotsThreads), 0, s, st, counts, g.mstart, g.mend, N, B, S, M1, batch, pos, forces, fixed);
     LbCtlArgs c;
     c.B = B;
     c.S = S;
@@ -553,7 +494,7 @@ int tmdnet_lbfgs_advance(tmdnet_model* m, void* stream, void* graph_ws, void* lb
     c.st = st;
     const size_t per_wave = lb_ctl_doubles(M1) * sizeof(double);
     hipLaunchKernelGGL(k_lbfgs_control, dim3((B + kLbCtlWaves - 1) / kLbCtlWaves), dim3(64 * kLbCtlWaves), per_wave * kLbCtlWaves, s, c);
-    hipLaunchKernelGGL(k_lbfgs_direction, dim3(B, S), block, 0, s, st, counts, mstart, mend, N, B, S, M1, batch, forces, fixed, direction);
+    hipLaunchKernelGGL(k_lbfgs_direction, dim3(B, S), block, 0, s, st, counts, g.mstart, g.mend, N, B, S, M1, batch, forces, fixed, direction);
   }
   {
     LbAtomArgs a;
@@ -571,7 +512,7 @@ int tmdnet_lbfgs_advance(tmdnet_model* m, void* stream, void* graph_ws, void* lb
     a.counts = counts;
     a.st = st;
     const int threads = N > B ? N : B;
-    const dim3 grid((threads + kLbThreads - 1) / kLbThreads);
+    const dim3 grid((threads + kThreads - 1) / kThreads);
     if (phase == TMDNET_MIN_OPEN)
       hipLaunchKernelGGL((k_lbfgs_move<false, true>), grid, block, 0, s, a);
     else if (phase == TMDNET_MIN_MIDDLE)
@@ -579,9 +520,7 @@ int tmdnet_lbfgs_advance(tmdnet_model* m, void* stream, void* graph_ws, void* lb
     else
       hipLaunchKernelGGL((k_lbfgs_move<true, false>), grid, block, 0, s, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_lbfgs_advance: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
-  return TMDNET_OK;
+  return loop_launch_result(m, "tmdnet_lbfgs_advance");
 }
 
 int tmdnet_lbfgs_status(void* stream, void* lbfgs_ws, uint64_t host[3]) {
@@ -590,7 +529,7 @@ int tmdnet_lbfgs_status(void* stream, void* lbfgs_ws, uint64_t host[3]) {
   uint32_t head[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (hipMemcpyAsync(head, carve_lb(lbfgs_ws, 0, 0, 1).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
   if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = (uint64_t)head[0] | ((uint64_t)head[1] << 32);
+  host[0] = loop_step(head);
   host[1] = head[2];
   host[2] = head[2] == 2 ? head[8] : 0;
   return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;

@@ -27,8 +27,6 @@
 // when S > 1.  The terms are stored in the CALLER's atom order, which is the order of mstart..mend whenever those ranges are
 // valid; when they are not (Graph::counts[3]: unsorted batch, or molecules interleaved by the cell list), or without a graph
 // workspace, a slice is a range of all atoms filtered by `batch`.
-#include <string>
-
 #include "tmdnet_amd.h"
 #include "tn_common.h"
 #include "tn_md_math.h"
@@ -78,21 +76,16 @@ __global__ __launch_bounds__(kThreads) void k_md_atoms(MdArgs a) {
   }
   const float hk = a.hk[i];
   if (CLOSE) {
-    const uint64_t step = (uint64_t)a.st.head[0] | ((uint64_t)a.st.head[1] << 32);
-    a.st.part[i] = tn_md::close_step(v, f, hk, a.mass[i], a.thermostat, a.c1, a.c2, a.thermostat ? a.sigma[i] : 0.f, a.seed, step,
-                                     (uint32_t)i);
+    a.st.part[i] = tn_md::close_step(v, f, hk, a.mass[i], a.thermostat, a.c1, a.c2, a.thermostat ? a.sigma[i] : 0.f, a.seed,
+                                     loop_step(a.st.head), (uint32_t)i);
     if (a.forces_keep)
 #pragma unroll
       for (int d = 0; d < 3; ++d) a.forces_keep[i * 3 + d] = f[d];
   }
   if (OPEN) {
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      x[d] = a.pos[i * 3 + d];
-      a.st.x_keep[i * 3 + d] = x[d];
-      a.st.v_keep[i * 3 + d] = v[d];
-    }
-    tn_md::open_step(x, v, f, hk, a.dt);
+    for (int d = 0; d < 3; ++d) x[d] = a.pos[i * 3 + d];
+    md_save_and_open(a.st, i, x, v, f, hk, a.dt);
 #pragma unroll
     for (int d = 0; d < 3; ++d) a.pos[i * 3 + d] = x[d];
   }
@@ -102,8 +95,7 @@ __global__ __launch_bounds__(kThreads) void k_md_atoms(MdArgs a) {
 
 __global__ void k_md_reset(MdState st, uint64_t step0) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    st.head[0] = (uint32_t)step0;
-    st.head[1] = (uint32_t)(step0 >> 32);
+    loop_set_step(st.head, step0);
     st.head[2] = 0u;
   }
 }
@@ -124,33 +116,19 @@ struct BaroArgs {
   MdState st;
 };
 
-// ONE block, after the closing launch and its kinetic-energy reduction (which has latched an overflow and advanced the step
-// counter).  Pass 1: every molecule's move, and whether any of them is unusable; pass 2, only when none is: the factors for
-// k_md_scale, the box and the log rows.  Otherwise the status word becomes 2 and nothing else is written.  A molecule belongs to
-// one thread in both passes, and the move is a function of what pass 1 read, so pass 2 evaluates it again instead of keeping it.
+// ONE block, after the closing launch and its kinetic-energy reduction: per_molecule_move (tn_loop.h) with status 2.  Pass 2 writes
+// the factors for k_md_scale, the box and the log rows; the move is a function of what pass 1 read, so pass 2 evaluates it again
+// instead of keeping it.
 __global__ __launch_bounds__(kThreads) void k_md_baro(BaroArgs a) {
-  __shared__ int bad;
-  if (a.st.head[2]) return;                // frozen
-  if (a.counts && a.counts[2]) return;     // (k_md_ke_reduce has latched it: the box stays that of the last completed step)
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  // the counter was advanced by the reduction: the O step of this MD step used the value before
-  const uint64_t step = ((uint64_t)a.st.head[0] | ((uint64_t)a.st.head[1] << 32)) - 1;
-  int flag = 0;
   double V, P;
   float mu, nu;
-  for (int m = threadIdx.x; m < a.B; m += kThreads)
-    flag |= tn_md::baro_move(a.box + 9 * (int64_t)m, a.virial + 9 * (int64_t)m, a.ekin[m], a.force_scale, a.P0, a.kT, a.a, a.seed, step,
-                             (uint32_t)m, &V, &P, &mu, &nu);
-  if (flag) bad = 1;  // (every writer stores the same value)
-  __syncthreads();
-  if (bad) {
-    if (threadIdx.x == 0) a.st.head[2] = 2u;
-    return;
-  }
-  for (int m = threadIdx.x; m < a.B; m += kThreads) {
+  const auto move = [&](int m, uint64_t step) {
+    return tn_md::baro_move(a.box + 9 * (int64_t)m, a.virial + 9 * (int64_t)m, a.ekin[m], a.force_scale, a.P0, a.kT, a.a, a.seed, step,
+                            (uint32_t)m, &V, &P, &mu, &nu);
+  };
+  per_molecule_move(a.st, a.counts, a.B, 2u, move, [&](int m, uint64_t step) {
     float* box = a.box + 9 * (int64_t)m;
-    tn_md::baro_move(box, a.virial + 9 * (int64_t)m, a.ekin[m], a.force_scale, a.P0, a.kT, a.a, a.seed, step, (uint32_t)m, &V, &P, &mu, &nu);
+    move(m, step);
     a.factors[m] = mu;
     a.factors[a.B + m] = nu;
 #pragma unroll
@@ -158,8 +136,11 @@ __global__ __launch_bounds__(kThreads) void k_md_baro(BaroArgs a) {
     if (a.volume_row) a.volume_row[m] = (float)V;
     if (a.pressure_row) a.pressure_row[m] = (float)P;
     if (a.scale_row) a.scale_row[m] = mu;
-  }
+  });
 }
+
+// the barostat's scratch: mu32 | nu32
+inline float* baro_layout(LoopCarver& c, int64_t B) { return c.take<float>((size_t)B * 2); }
 
 struct ScaleArgs {
   int N, B;
@@ -194,12 +175,8 @@ __global__ __launch_bounds__(kThreads) void k_md_scale(ScaleArgs a) {
   if (OPEN) {
     float f[3];
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      f[d] = a.forces[i * 3 + d];
-      a.st.x_keep[i * 3 + d] = x[d];
-      a.st.v_keep[i * 3 + d] = v[d];
-    }
-    tn_md::open_step(x, v, f, a.hk[i], a.dt);
+    for (int d = 0; d < 3; ++d) f[d] = a.forces[i * 3 + d];
+    md_save_and_open(a.st, i, x, v, f, a.hk[i], a.dt);
   }
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
@@ -253,16 +230,9 @@ int tmdnet_md_advance(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws
   a.c2 = c2;
   a.seed = seed;
   a.thermostat = sigma != nullptr;
-  a.counts = nullptr;
+  const LoopGraph g = loop_graph(m, graph_ws, n_atoms, n_mol);
+  a.counts = g.counts;
   a.st = carve_md(md_ws, n_atoms, n_mol);
-  const int* mstart = nullptr;
-  const int* mend = nullptr;
-  if (graph_ws) {
-    const Graph g = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr);
-    a.counts = g.counts;
-    mstart = g.mstart;
-    mend = g.mend;
-  }
   const dim3 grid((N + kThreads - 1) / kThreads), block(kThreads);
   if (phase == TMDNET_MD_OPEN)
     hipLaunchKernelGGL((k_md_atoms<false, true>), grid, block, 0, s, a);
@@ -271,21 +241,19 @@ int tmdnet_md_advance(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws
   else
     hipLaunchKernelGGL((k_md_atoms<true, false>), grid, block, 0, s, a);
   if (phase != TMDNET_MD_OPEN) {
-    const int S = ke_slices(n_atoms, n_mol);
+    const int S = mol_slices(n_atoms, n_mol);
     float* out = S == 1 ? ekin_log_row : a.st.slices;
-    hipLaunchKernelGGL(k_md_ke_reduce<false>, dim3(B, S), block, 0, s, a.st, a.counts, mstart, mend, N, B, S, batch, energy, epot_log_row, out,
-                       nullptr);
+    hipLaunchKernelGGL(k_md_ke_reduce<false>, dim3(B, S), block, 0, s, a.st, g.counts, g.mstart, g.mend, N, B, S, batch, energy, epot_log_row,
+                       out, nullptr);
     if (S > 1 && ekin_log_row)
       hipLaunchKernelGGL(k_md_ke_finish, dim3((B + kThreads - 1) / kThreads), block, 0, s, a.st, a.counts, B, S, ekin_log_row);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_md_advance: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
-  return TMDNET_OK;
+  return loop_launch_result(m, "tmdnet_md_advance");
 }
 
 int tmdnet_md_barostat_workspace_bytes(int64_t n_mol, size_t* bytes) {
   if (!bytes || n_mol < 0 || n_mol > INT32_MAX / 16) return TMDNET_ERR_INVALID;
-  *bytes = align256((size_t)n_mol * 2 * sizeof(float)) + 256;  // mu32 | nu32, and room to align the caller's pointer
+  *bytes = layout_bytes([&](LoopCarver& c) { baro_layout(c, n_mol); });
   return TMDNET_OK;
 }
 
@@ -314,13 +282,13 @@ int tmdnet_md_barostat(tmdnet_model* m, void* stream, void* graph_ws, void* md_w
   b.a = compressibility * (double)dt / tau;
   b.force_scale = force_scale;
   b.seed = seed;
-  b.factors = reinterpret_cast<float*>(align256(reinterpret_cast<size_t>(baro_ws)));
+  LoopCarver c(baro_ws);
+  b.factors = baro_layout(c, n_mol);
   b.volume_row = volume_log_row;
   b.pressure_row = pressure_log_row;
   b.scale_row = scale_log_row;
-  b.counts = nullptr;
+  b.counts = loop_graph(m, graph_ws, n_atoms, n_mol).counts;
   b.st = carve_md(md_ws, n_atoms, n_mol);
-  if (graph_ws) b.counts = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr).counts;
   hipLaunchKernelGGL(k_md_baro, dim3(1), dim3(kThreads), 0, s, b);
   if (N > 0) {
     ScaleArgs a;
@@ -340,9 +308,7 @@ int tmdnet_md_barostat(tmdnet_model* m, void* stream, void* graph_ws, void* md_w
     else
       hipLaunchKernelGGL((k_md_scale<false>), grid, block, 0, s, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_md_barostat: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
-  return TMDNET_OK;
+  return loop_launch_result(m, "tmdnet_md_barostat");
 }
 
 int tmdnet_md_status(void* stream, void* md_ws, uint64_t host[2]) {
@@ -351,7 +317,7 @@ int tmdnet_md_status(void* stream, void* md_ws, uint64_t host[2]) {
   uint32_t head[3] = {0, 0, 0};
   if (hipMemcpyAsync(head, carve_md(md_ws, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
   if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = (uint64_t)head[0] | ((uint64_t)head[1] << 32);
+  host[0] = loop_step(head);
   host[1] = head[2];
   return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
 }

@@ -12,8 +12,6 @@
 //
 // All of them return at once on the status word or on the overflow flag of this step's evaluation (the CLOSE launch before has
 // latched it), so box, positions and velocities stay those of the last completed step.
-#include <string>
-
 #include "tmdnet_amd.h"
 #include "tn_common.h"
 #include "tn_md_cell_math.h"
@@ -30,28 +28,22 @@ struct CellWs {  // views into the caller's scratch
   double* slices;  // [B, S, 6] (S > 1 only)
 };
 
-inline size_t cell_bytes(int64_t N, int64_t B) {
-  const int S = ke_slices(N, B);
-  size_t t = align256((size_t)B * 27 * sizeof(float)) + align256((size_t)B * 6 * sizeof(double));
-  if (S > 1) t += align256((size_t)B * S * 6 * sizeof(double));
-  return t + 256;  // room to align the caller's pointer
-}
-
-inline CellWs carve_cell(void* ws, int64_t B) {
-  char* p = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(ws)));
+inline CellWs cell_layout(LoopCarver& c, int64_t N, int64_t B) {
+  const int S = mol_slices(N, B);
   CellWs w;
-  w.M = reinterpret_cast<float*>(p);
-  p += align256((size_t)B * 27 * sizeof(float));
-  w.kt = reinterpret_cast<double*>(p);
-  p += align256((size_t)B * 6 * sizeof(double));
-  w.slices = reinterpret_cast<double*>(p);
+  w.M = c.take<float>((size_t)B * 27);
+  w.kt = c.take<double>((size_t)B * 6);
+  w.slices = c.take<double>(S > 1 ? (size_t)B * S * 6 : 0);
   return w;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
+inline size_t cell_bytes(int64_t N, int64_t B) {
+  return layout_bytes([&](LoopCarver& c) { cell_layout(c, N, B); });
+}
+
+inline CellWs carve_cell(void* ws, int64_t N, int64_t B) {
+  LoopCarver c(ws);
+  return cell_layout(c, N, B);
 }
 
 // grid (B, S), after the closing launch and its reduction: slice s of molecule m -> out[(m S + s) 6 ..]
@@ -59,37 +51,22 @@ __global__ __launch_bounds__(kThreads) void k_md_ktensor_reduce(MdState st, cons
                                                                 const int* __restrict__ mend, int N, int S,
                                                                 const int64_t* __restrict__ batch, const float* __restrict__ vel,
                                                                 const float* __restrict__ mass, double* __restrict__ out) {
-  __shared__ double sh[4][6];
+  __shared__ double sh[6][kThreads / 64];
   if (st.head[2]) return;
   if (counts && counts[2]) return;
   const int m = blockIdx.x, s = blockIdx.y;
-  const bool filter = counts ? counts[3] != 0 : batch != nullptr;
-  int a = 0, b = N;
-  if (counts && !filter) {
-    a = mstart[m];
-    b = mend[m];
-  }
-  const int64_t len = b - a;
-  const int i0 = a + (int)(len * s / S), i1 = a + (int)(len * (s + 1) / S);
+  const SliceRange r = mol_slice_range(counts, mstart, mend, N, S, batch, m, s);
   double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int i = i0 + (int)threadIdx.x; i < i1; i += kThreads) {
-    if (filter && batch && batch[i] != m) continue;  // (no batch vector: one molecule)
+  for (int i = r.i0 + (int)threadIdx.x; i < r.i1; i += kThreads) {
+    if (slice_skips(r, batch, i, m)) continue;
     const float v[3] = {vel[i * 3], vel[i * 3 + 1], vel[i * 3 + 2]};
     double t[6];
     tn_md::cell_ktensor_term(mass[i], v, t);
 #pragma unroll
     for (int c = 0; c < 6; ++c) acc[c] += t[c];
   }
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    const double w = wave_sum_f64(acc[c]);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][c] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int c = threadIdx.x;
-    out[((int64_t)m * S + s) * 6 + c] = ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c];
-  }
+  block_reduce_waves<6, 0u>(acc, sh);
+  if (threadIdx.x < 6) out[((int64_t)m * S + s) * 6 + threadIdx.x] = block_reduce_row(sh[threadIdx.x], false);
 }
 
 // one thread per entry of a molecule's tensor: the slice sums in slice order
@@ -119,35 +96,18 @@ struct CellArgs {
   MdState st;
 };
 
-// ONE block.  Pass 1: every molecule's move, and whether any of them is unusable; pass 2, only when none is: the matrices for
-// k_md_cell_scale, the box and the log rows.  Otherwise the status word becomes 2 and nothing else is written.  A molecule belongs
-// to one thread in both passes, and the move is a function of what pass 1 read: with up to one molecule per thread pass 2 writes what
-// pass 1 left in the thread's registers, with more it evaluates the move again instead of keeping every one of them.
+// ONE block: per_molecule_move (tn_loop.h) with status 2.  Pass 2 writes the matrices for k_md_cell_scale, the box and the log rows:
+// with up to one molecule per thread what pass 1 left in the thread's registers, with more it evaluates the move again instead of
+// keeping every one of them.
 __global__ __launch_bounds__(kThreads) void k_md_cell_move(CellArgs a) {
-  __shared__ int bad;
-  if (a.st.head[2]) return;             // frozen
-  if (a.counts && a.counts[2]) return;  // (k_md_ke_reduce has latched it: the box stays that of the last completed step)
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  // the counter was advanced by the closing launch's reduction: the O step of this MD step used the value before
-  const uint64_t step = ((uint64_t)a.st.head[0] | ((uint64_t)a.st.head[1] << 32)) - 1;
-  int flag = 0;
   tn_md::CellMove mv;
-  for (int m = threadIdx.x; m < a.B; m += kThreads)
-    flag |= tn_md::cell_move(a.box + 9 * (int64_t)m, a.virial + 9 * (int64_t)m, a.kt + 6 * (int64_t)m, a.force_scale, a.P0, a.kT, a.a,
-                             a.seed, step, (uint32_t)m, a.coupling, a.axis, &mv);
-  if (flag) bad = 1;  // (every writer stores the same value)
-  __syncthreads();
-  if (bad) {
-    if (threadIdx.x == 0) a.st.head[2] = 2u;
-    return;
-  }
-  const bool again = a.B > kThreads;  // up to one molecule per thread: pass 1 left its move in this thread's registers
-  for (int m = threadIdx.x; m < a.B; m += kThreads) {
+  const auto move = [&](int m, uint64_t step) {
+    return tn_md::cell_move(a.box + 9 * (int64_t)m, a.virial + 9 * (int64_t)m, a.kt + 6 * (int64_t)m, a.force_scale, a.P0, a.kT, a.a, a.seed,
+                            step, (uint32_t)m, a.coupling, a.axis, &mv);
+  };
+  per_molecule_move(a.st, a.counts, a.B, 2u, move, [&](int m, uint64_t step) {
     float* box = a.box + 9 * (int64_t)m;
-    if (again)
-      tn_md::cell_move(box, a.virial + 9 * (int64_t)m, a.kt + 6 * (int64_t)m, a.force_scale, a.P0, a.kT, a.a, a.seed, step, (uint32_t)m,
-                       a.coupling, a.axis, &mv);
+    if (a.B > kThreads) move(m, step);
 #pragma unroll
     for (int i = 0; i < 27; ++i) a.M[27 * (int64_t)m + i] = mv.M[i];
 #pragma unroll
@@ -159,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_md_cell_move(CellArgs a) {
     if (a.scale_row)
 #pragma unroll
       for (int i = 0; i < 9; ++i) a.scale_row[9 * (int64_t)m + i] = mv.M[i];
-  }
+  });
 }
 
 struct CellScaleArgs {
@@ -212,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void k_md_cell_scale(CellScaleArgs a) {
         for (int d = 0; d < 3; ++d) a.forces_keep[i * 3 + d] = f[d];
     }
   }
-  if (OPEN) {
+  if (OPEN) {  // the opening half written out, not md_save_and_open: hk read after the saves keeps the rotating kernel's registers down
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       a.st.x_keep[i * 3 + d] = x[d];
@@ -260,19 +220,12 @@ int tmdnet_md_barostat_cell(tmdnet_model* m, void* stream, void* graph_ws, void*
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int N = (int)n_atoms, B = (int)n_mol;
   const MdState st = carve_md(md_ws, n_atoms, n_mol);
-  const CellWs w = carve_cell(cell_ws, n_mol);
-  const int* counts = nullptr;
-  const int* mstart = nullptr;
-  const int* mend = nullptr;
-  if (graph_ws) {
-    const Graph g = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr);
-    counts = g.counts;
-    mstart = g.mstart;
-    mend = g.mend;
-  }
+  const CellWs w = carve_cell(cell_ws, n_atoms, n_mol);
+  const LoopGraph g = loop_graph(m, graph_ws, n_atoms, n_mol);
+  const int* counts = g.counts;
   const dim3 block(kThreads);
-  const int S = ke_slices(n_atoms, n_mol);
-  hipLaunchKernelGGL(k_md_ktensor_reduce, dim3(B, S), block, 0, s, st, counts, mstart, mend, N, S, batch, vel, mass, S == 1 ? w.kt : w.slices);
+  const int S = mol_slices(n_atoms, n_mol);
+  hipLaunchKernelGGL(k_md_ktensor_reduce, dim3(B, S), block, 0, s, st, counts, g.mstart, g.mend, N, S, batch, vel, mass, S == 1 ? w.kt : w.slices);
   if (S > 1) hipLaunchKernelGGL(k_md_ktensor_finish, dim3((B * 6 + kThreads - 1) / kThreads), block, 0, s, st, counts, B, S, w.slices, w.kt);
   CellArgs c;
   c.B = B;
@@ -317,9 +270,7 @@ int tmdnet_md_barostat_cell(tmdnet_model* m, void* stream, void* graph_ws, void*
     else
       hipLaunchKernelGGL((k_md_cell_scale<false, false>), grid, block, 0, s, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_md_barostat_cell: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
-  return TMDNET_OK;
+  return loop_launch_result(m, "tmdnet_md_barostat_cell");
 }
 
 }  // extern "C"

@@ -25,8 +25,6 @@
 // the same launch may be setting it: which clusters of a FAILING launch still complete their half step depends on the scheduling,
 // so the frozen state after a failure (finite, not a point of the trajectory) is not reproducible from run to run; the bit-identical
 // repeats hold for runs in which no cluster fails.  The overflow protocol of tn_md.hip is unchanged.
-#include <string>
-
 #include "tmdnet_amd.h"
 #include "tn_common.h"
 #include "tn_md_cons_math.h"
@@ -39,6 +37,9 @@ namespace tn {
 namespace {
 
 constexpr int kGroup = tn_md_cons::kMaxAtoms;
+
+// the constraint workspace: the word a cluster ORs when it gives up
+inline uint32_t* cons_layout(LoopCarver& c) { return c.take<uint32_t>(1); }
 
 struct ConsArgs {
   int N, n_clusters, n_cons;
@@ -179,10 +180,9 @@ __global__ __launch_bounds__(kThreads) void k_md_clusters(ConsArgs a) {
       for (int d = 0; d < 3; ++d) x[d] = a.pos[i * 3 + d];
   if (CLOSE) {
     float ke = 0.f;
-    if (on) {
-      const uint64_t step = (uint64_t)a.st.head[0] | ((uint64_t)a.st.head[1] << 32);
-      ke = tn_md::close_step(v, f, hk, m, a.thermostat, a.c1, a.c2, a.thermostat ? a.sigma[i] : 0.f, a.seed, step, (uint32_t)i);
-    }
+    if (on)
+      ke = tn_md::close_step(v, f, hk, m, a.thermostat, a.c1, a.c2, a.thermostat ? a.sigma[i] : 0.f, a.seed, loop_step(a.st.head),
+                             (uint32_t)i);
     if (bound) {
       const double x64[3] = {(double)x[0], (double)x[1], (double)x[2]};
       double v64[3] = {(double)v[0], (double)v[1], (double)v[2]};
@@ -213,14 +213,7 @@ __global__ __launch_bounds__(kThreads) void k_md_clusters(ConsArgs a) {
   }
   if (OPEN) {
     const double k64[3] = {(double)x[0], (double)x[1], (double)x[2]};
-    if (on) {
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        a.st.x_keep[i * 3 + d] = x[d];
-        a.st.v_keep[i * 3 + d] = v[d];
-      }
-      tn_md::open_step(x, v, f, hk, a.dt);
-    }
+    if (on) md_save_and_open(a.st, i, x, v, f, hk, a.dt);
     if (bound) {
       double x64[3] = {(double)x[0], (double)x[1], (double)x[2]};
       int ok = group_shake(a, c0, c1, l, x64, k64, w);
@@ -256,7 +249,7 @@ int tmdnet_md_constraints_workspace_bytes(int64_t n_atoms, int64_t n_clusters, i
   if (!bytes || n_atoms < 0 || n_atoms > INT32_MAX / 4 || n_clusters < 0 || n_clusters > INT32_MAX / 16 || n_constraints < 0 ||
       n_constraints > (int64_t)tn_md_cons::kMaxCons * n_clusters)
     return TMDNET_ERR_INVALID;
-  *bytes = 256 + 256;  // the fail word, and room to align the caller's pointer
+  *bytes = layout_bytes([](LoopCarver& c) { cons_layout(c); });
   return TMDNET_OK;
 }
 
@@ -296,23 +289,17 @@ int tmdnet_md_advance_constrained(tmdnet_model* m, void* stream, void* graph_ws,
   a.c2 = c2;
   a.seed = seed;
   a.thermostat = sigma != nullptr;
-  a.counts = nullptr;
   a.cl_atoms = cluster_atoms;
   a.cl_off = cluster_offsets;
   a.cons_ab = constraint_ends;
   a.cons_d2 = constraint_d2;
   a.tol = tol;
   a.max_iter = max_iter;
-  a.fail = reinterpret_cast<uint32_t*>(align256(reinterpret_cast<size_t>(cons_ws)));
+  LoopCarver c(cons_ws);
+  a.fail = cons_layout(c);
   a.st = carve_md(md_ws, n_atoms, n_mol);
-  const int* mstart = nullptr;
-  const int* mend = nullptr;
-  if (graph_ws) {
-    const Graph g = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr);
-    a.counts = g.counts;
-    mstart = g.mstart;
-    mend = g.mend;
-  }
+  const LoopGraph g = loop_graph(m, graph_ws, n_atoms, n_mol);
+  a.counts = g.counts;
   const int64_t lanes = n_clusters * kGroup;
   const dim3 grid((unsigned)((lanes + kThreads - 1) / kThreads)), block(kThreads);
   if (phase == TMDNET_MD_OPEN)
@@ -326,17 +313,14 @@ int tmdnet_md_advance_constrained(tmdnet_model* m, void* stream, void* graph_ws,
     hipLaunchKernelGGL(k_md_cons_latch, dim3(1), dim3(64), 0, s, a.st, a.fail);
   }
   if (phase == TMDNET_MD_MIDDLE || phase == TMDNET_MD_CLOSE) {
-    const int S = ke_slices(n_atoms, n_mol);
+    const int S = mol_slices(n_atoms, n_mol);
     float* out = S == 1 ? ekin_log_row : a.st.slices;
-    hipLaunchKernelGGL(k_md_ke_reduce<true>, dim3(B, S), block, 0, s, a.st, a.counts, mstart, mend, N, B, S, batch, energy, epot_log_row,
+    hipLaunchKernelGGL(k_md_ke_reduce<true>, dim3(B, S), block, 0, s, a.st, g.counts, g.mstart, g.mend, N, B, S, batch, energy, epot_log_row,
                        out, a.fail);
     if (S > 1 && ekin_log_row)
       hipLaunchKernelGGL(k_md_ke_finish, dim3((B + kThreads - 1) / kThreads), block, 0, s, a.st, a.counts, B, S, ekin_log_row);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_md_advance_constrained: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
-  return TMDNET_OK;
+  return loop_launch_result(m, "tmdnet_md_advance_constrained");
 }
 
 }  // extern "C"

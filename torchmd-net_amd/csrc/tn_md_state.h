@@ -1,17 +1,16 @@
-// State and kinetic-energy reduction of the device-resident MD loop, shared by the integrator launches of tn_md.hip (one thread per
-// atom) and tn_md_cons.hip (one group of lanes per constraint cluster): the layout of the caller's workspace and the kernels that
-// follow a closing launch.  Everything sits in an unnamed namespace: each of the two files gets its own copy.
+// State and kinetic-energy reduction of the device-resident MD loop, shared by everything that acts on its workspace: the
+// integrator launches of tn_md.hip (one thread per atom) and tn_md_cons.hip (one group of lanes per constraint cluster), the
+// barostats, thermostats, replica exchange, bias and committee gate.  The layout of the caller's workspace and the kernels that
+// follow a closing launch.  Everything sits in an unnamed namespace: every file that includes this header gets its own copy.
 #pragma once
 #include <stdint.h>
 
 #include "tn_common.h"
+#include "tn_loop.h"
 
 namespace tn {
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr size_t kHeaderBytes = 256;
 
 struct MdState {  // views into the caller's workspace
   uint32_t* head;  // [0] step lo, [1] step hi, [2] status (sticky, 1 = an evaluation overflowed, 2 = an unusable barostat move,
@@ -23,44 +22,25 @@ struct MdState {  // views into the caller's workspace
   float* slices;   // [B, S] (S > 1 only)
 };
 
-inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
-
-inline int ke_slices(int64_t N, int64_t B) {
-  if (B <= 0 || N <= 1024 * B) return 1;
-  const int64_t s = (N + 1024 * B - 1) / (1024 * B);
-  return (int)(s > 256 ? 256 : s);
-}
-
-inline size_t md_bytes(int64_t N, int64_t B) {
-  const int S = ke_slices(N, B);
-  const size_t n = (size_t)(N > 0 ? N : 0);
-  size_t t = kHeaderBytes + 2 * align256(n * 3 * sizeof(float)) + align256(n * sizeof(float));
-  if (S > 1) t += align256((size_t)B * S * sizeof(float));
-  return t + 256;  // room to align the caller's pointer
-}
-
-inline MdState carve_md(void* ws, int64_t N, int64_t B) {
-  char* p = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(ws)));
+inline MdState md_layout(LoopCarver& c, int64_t N, int64_t B) {
+  const int S = mol_slices(N, B);
   const size_t n = (size_t)(N > 0 ? N : 0);
   MdState st;
-  st.head = reinterpret_cast<uint32_t*>(p);
-  p += kHeaderBytes;
-  st.x_keep = reinterpret_cast<float*>(p);
-  p += align256(n * 3 * sizeof(float));
-  st.v_keep = reinterpret_cast<float*>(p);
-  p += align256(n * 3 * sizeof(float));
-  st.part = reinterpret_cast<float*>(p);
-  p += align256(n * sizeof(float));
-  st.slices = reinterpret_cast<float*>(p);
+  st.head = c.take<uint32_t>(kHeaderBytes / sizeof(uint32_t));
+  st.x_keep = c.take<float>(n * 3);
+  st.v_keep = c.take<float>(n * 3);
+  st.part = c.take<float>(n);
+  st.slices = c.take<float>(S > 1 ? (size_t)B * S : 0);
   return st;
 }
 
-// sum over the block in a fixed order (lanes by the wave tree, waves in turn), result in every thread
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+inline size_t md_bytes(int64_t N, int64_t B) {
+  return layout_bytes([&](LoopCarver& c) { md_layout(c, N, B); });
+}
+
+inline MdState carve_md(void* ws, int64_t N, int64_t B) {
+  LoopCarver c(ws);
+  return md_layout(c, N, B);
 }
 
 // grid (B, S), after a closing launch: slice s of molecule m -> out[m * S + s] (S == 1: the log row itself).  Block (0, 0) also
@@ -74,7 +54,7 @@ __global__ __launch_bounds__(kThreads) void k_md_ke_reduce(MdState st, const int
                                                            const int64_t* __restrict__ batch, const float* __restrict__ energy,
                                                            float* __restrict__ epot_row, float* __restrict__ out,
                                                            const uint32_t* __restrict__ fail) {
-  __shared__ float sh[4];
+  __shared__ float sh[1][kThreads / 64];
   if (st.head[2]) return;
   const int m = blockIdx.x, s = blockIdx.y;
   const bool first = m == 0 && s == 0 && threadIdx.x == 0;
@@ -86,17 +66,10 @@ __global__ __launch_bounds__(kThreads) void k_md_ke_reduce(MdState st, const int
     if (first) st.head[2] = 3u;
     return;
   }
-  const bool filter = counts ? counts[3] != 0 : batch != nullptr;
-  int a = 0, b = N;
-  if (counts && !filter) {
-    a = mstart[m];
-    b = mend[m];
-  }
-  const int64_t len = b - a;
-  const int i0 = a + (int)(len * s / S), i1 = a + (int)(len * (s + 1) / S);
+  const SliceRange r = mol_slice_range(counts, mstart, mend, N, S, batch, m, s);
   float v = 0.f;
-  for (int i = i0 + (int)threadIdx.x; i < i1; i += kThreads) {
-    if (filter && batch && batch[i] != m) continue;  // (no batch vector: one molecule)
+  for (int i = r.i0 + (int)threadIdx.x; i < r.i1; i += kThreads) {
+    if (slice_skips(r, batch, i, m)) continue;
     v += st.part[i];
   }
   v = block_sum(v, sh);
@@ -104,11 +77,7 @@ __global__ __launch_bounds__(kThreads) void k_md_ke_reduce(MdState st, const int
     if (out) out[(int64_t)m * S + s] = v;
     if (s == 0 && energy && epot_row) epot_row[m] = energy[m];
   }
-  if (first) {
-    const uint64_t step = ((uint64_t)st.head[0] | ((uint64_t)st.head[1] << 32)) + 1;
-    st.head[0] = (uint32_t)step;
-    st.head[1] = (uint32_t)(step >> 32);
-  }
+  if (first) loop_set_step(st.head, loop_step(st.head) + 1);
 }
 
 // one thread per molecule: the slice sums in slice order.  The status word is already latched by k_md_ke_reduce.

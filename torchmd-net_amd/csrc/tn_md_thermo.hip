@@ -6,8 +6,6 @@
 // move latches the sticky status 5 and writes nothing else.  k_md_scale of tn_md.hip with mu = 1 would give the same bits (a product
 // with 1.0f is exact); the kernel below is its own because it has no position to scale - without OPEN it does not touch pos at all
 // - and because an atom of infinite mass is left out of the scaling.
-#include <string>
-
 #include "tmdnet_amd.h"
 #include "tn_common.h"
 #include "tn_md_state.h"
@@ -24,20 +22,22 @@ struct ThermoState {  // views into the caller's thermostat workspace
   double* chain;      // [B, 2, M]
 };
 
-inline size_t thermo_bytes(int64_t B, int M) {
+inline ThermoState thermo_layout(LoopCarver& c, int64_t B, int M) {
   const size_t b = (size_t)B;
-  return align256(b * sizeof(float)) + align256(b * sizeof(double)) + align256(b * 2 * (size_t)M * sizeof(double)) + 256;
+  ThermoState t;
+  t.alpha = c.take<float>(b);
+  t.reservoir = c.take<double>(b);
+  t.chain = c.take<double>(b * 2 * (size_t)M);
+  return t;
 }
 
-inline ThermoState carve_thermo(void* ws, int64_t B) {
-  char* p = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(ws)));
-  ThermoState t;
-  t.alpha = reinterpret_cast<float*>(p);
-  p += align256((size_t)B * sizeof(float));
-  t.reservoir = reinterpret_cast<double*>(p);
-  p += align256((size_t)B * sizeof(double));
-  t.chain = reinterpret_cast<double*>(p);
-  return t;
+inline size_t thermo_bytes(int64_t B, int M) {
+  return layout_bytes([&](LoopCarver& c) { thermo_layout(c, B, M); });
+}
+
+inline ThermoState carve_thermo(void* ws, int64_t B, int M) {
+  LoopCarver c(ws);
+  return thermo_layout(c, B, M);
 }
 
 struct ThermoArgs {
@@ -53,36 +53,23 @@ struct ThermoArgs {
   MdState st;
 };
 
-// ONE block, after the closing launch and its kinetic-energy reduction (which has latched an overflow and advanced the step
-// counter).  Pass 1: every molecule's move on copies of its state, and whether any of them is unusable; pass 2, only when none is:
-// the move again, kept.  Otherwise the status word becomes 5 and nothing else is written.  A molecule belongs to one thread in both
-// passes, and the move is a function of what pass 1 read.
+// ONE block, after the closing launch and its kinetic-energy reduction: per_molecule_move (tn_loop.h) with status 5.  Pass 1 runs
+// every molecule's move on copies of its state; pass 2 runs it again, kept.
+__device__ __forceinline__ int thermo_eval(const ThermoArgs& a, int m, uint64_t step, int keep, float* alpha) {
+  return tn_md::thermo_move(a.kind, a.ekin[m], a.force_scale, a.ndof[m], a.kT, a.tau, a.dt, a.c, a.M, a.substeps, a.seed, step, (uint32_t)m,
+                            a.th.chain + 2 * (int64_t)a.M * m, a.th.reservoir + m, keep, alpha);
+}
+
 __global__ __launch_bounds__(kThreads) void k_md_thermo_factor(ThermoArgs a) {
-  __shared__ int bad;
-  if (a.st.head[2]) return;             // frozen
-  if (a.counts && a.counts[2]) return;  // (k_md_ke_reduce has latched it)
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  // the counter was advanced by the reduction: the O step of this MD step would have used the value before
-  const uint64_t step = ((uint64_t)a.st.head[0] | ((uint64_t)a.st.head[1] << 32)) - 1;
-  int flag = 0;
   float alpha;
-  for (int m = threadIdx.x; m < a.B; m += kThreads)
-    flag |= tn_md::thermo_move(a.kind, a.ekin[m], a.force_scale, a.ndof[m], a.kT, a.tau, a.dt, a.c, a.M, a.substeps, a.seed, step,
-                               (uint32_t)m, a.th.chain + 2 * (int64_t)a.M * m, a.th.reservoir + m, 0, &alpha);
-  if (flag) bad = 1;  // (every writer stores the same value)
-  __syncthreads();
-  if (bad) {
-    if (threadIdx.x == 0) a.st.head[2] = 5u;
-    return;
-  }
-  for (int m = threadIdx.x; m < a.B; m += kThreads) {
-    tn_md::thermo_move(a.kind, a.ekin[m], a.force_scale, a.ndof[m], a.kT, a.tau, a.dt, a.c, a.M, a.substeps, a.seed, step, (uint32_t)m,
-                       a.th.chain + 2 * (int64_t)a.M * m, a.th.reservoir + m, 1, &alpha);
-    a.th.alpha[m] = alpha;
-    if (a.scale_row) a.scale_row[m] = alpha;
-    if (a.reservoir_row) a.reservoir_row[m] = a.th.reservoir[m];
-  }
+  per_molecule_move(
+      a.st, a.counts, a.B, 5u, [&](int m, uint64_t step) { return thermo_eval(a, m, step, 0, &alpha); },
+      [&](int m, uint64_t step) {
+        thermo_eval(a, m, step, 1, &alpha);
+        a.th.alpha[m] = alpha;
+        if (a.scale_row) a.scale_row[m] = alpha;
+        if (a.reservoir_row) a.reservoir_row[m] = a.th.reservoir[m];
+      });
 }
 
 struct ThermoScaleArgs {
@@ -117,10 +104,8 @@ __global__ __launch_bounds__(kThreads) void k_md_thermo_scale(ThermoScaleArgs a)
     for (int d = 0; d < 3; ++d) {
       x[d] = a.pos[i * 3 + d];
       f[d] = a.forces[i * 3 + d];
-      a.st.x_keep[i * 3 + d] = x[d];
-      a.st.v_keep[i * 3 + d] = v[d];
     }
-    tn_md::open_step(x, v, f, hk, a.dt);
+    md_save_and_open(a.st, i, x, v, f, hk, a.dt);
 #pragma unroll
     for (int d = 0; d < 3; ++d) a.pos[i * 3 + d] = x[d];
   }
@@ -169,12 +154,11 @@ int tmdnet_md_thermostat(tmdnet_model* m, void* stream, void* graph_ws, void* md
   t.c = exp(-(double)dt / tau);
   t.force_scale = force_scale;
   t.seed = seed;
-  t.th = carve_thermo(thermo_ws, n_mol);
+  t.th = carve_thermo(thermo_ws, n_mol, t.M);
   t.scale_row = scale_log_row;
   t.reservoir_row = reservoir_log_row;
-  t.counts = nullptr;
+  t.counts = loop_graph(m, graph_ws, n_atoms, n_mol).counts;
   t.st = carve_md(md_ws, n_atoms, n_mol);
-  if (graph_ws) t.counts = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr).counts;
   hipLaunchKernelGGL(k_md_thermo_factor, dim3(1), dim3(kThreads), 0, s, t);
   if (N > 0) {
     ThermoScaleArgs a;
@@ -194,9 +178,7 @@ int tmdnet_md_thermostat(tmdnet_model* m, void* stream, void* graph_ws, void* md
     else
       hipLaunchKernelGGL((k_md_thermo_scale<false>), grid, block, 0, s, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_md_thermostat: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
-  return TMDNET_OK;
+  return loop_launch_result(m, "tmdnet_md_thermostat");
 }
 
 }  // extern "C"

@@ -26,22 +26,20 @@
 // Cell relaxation (tmdnet_min_*_cell, the second half of this file): the same three launches on N + 3 rows per molecule.  The atoms
 // are integrated in xt = x D^-T, the three rows of the deformation gradient D count as three more atoms with coordinates c D and
 // force (W_s - p V I) D^-T / c from the step's virial, the controller's sums get their terms added, and the move rewrites the box
-// H0 D^T the next evaluation reads.  The scheme is stated with the entries in include/tmdnet_amd.h; the existing kernels are not
-// touched, so the fixed-box path issues the launches and produces the bits it did before.
+// H0 D^T the next evaluation reads.  The scheme is stated with the entries in include/tmdnet_amd.h; the reduction is one template
+// (k_min_reduce<CELL>: the cell adds one statement), the controller and the per-atom kernel have siblings of their own, so the
+// fixed-box path issues the launches and produces the bits it did before.
 #include <cmath>
-#include <string>
 
 #include "tmdnet_amd.h"
 #include "tn_common.h"
+#include "tn_loop.h"
 #include "tn_min_math.h"
 #include "tn_model.h"
 
 namespace tn {
 
 namespace {
-
-constexpr int kMinThreads = 256;
-constexpr size_t kMinHeaderBytes = 256;
 
 struct MinState {  // views into the caller's workspace
   uint32_t* head;    // [0] step lo, [1] step hi, [2] status (sticky: 1 overflow, 2 non-finite sums), [3] 1 = reset, not yet controlled
@@ -56,104 +54,97 @@ struct MinState {  // views into the caller's workspace
   double* slices;    // [B, S, 4] vf, ff, vv, fmax2
 };
 
-inline size_t min_align256(size_t n) { return (n + 255) & ~size_t(255); }
+// the cell relaxation's arrays sit behind MinState in the same workspace (see "cell relaxation" below)
+struct MinCell {
+  double* H0;       // [B, 9] the reference box
+  double* D_keep;   // [B, 9] before the last move
+  double* VD_keep;  // [B, 9]
+  double* D_next;   // [B, 9] what the last control prepared
+  double* VD_next;  // [B, 9]
+  float* box_keep;  // [B, 9]
+  float* box_next;  // [B, 9]
+  float* d32;       // [B, 9]
+  float* d32_prev;  // [B, 9]
+  float* d32_next;  // [B, 9]
+};
 
-int min_slices(int64_t N, int64_t B) {
-  if (B <= 0 || N <= 1024 * B) return 1;
-  const int64_t s = (N + 1024 * B - 1) / (1024 * B);
-  return (int)(s > 256 ? 256 : s);
-}
-
-size_t min_bytes(int64_t N, int64_t B) {
+MinState min_layout(LoopCarver& c, int64_t N, int64_t B, MinCell* cell) {
   const size_t n = (size_t)(N > 0 ? N : 0), b = (size_t)(B > 0 ? B : 0);
-  const size_t S = (size_t)min_slices(N, B);
-  return kMinHeaderBytes + 3 * min_align256(b * 8) + min_align256(b * 4) + min_align256(b * 3 * sizeof(float)) +
-         2 * min_align256(n * 3 * sizeof(float)) + min_align256(b * S * 4 * sizeof(double)) + 256;  // + room to align the pointer
-}
-
-MinState carve_min(void* ws, int64_t N, int64_t B) {
-  char* p = reinterpret_cast<char*>(min_align256(reinterpret_cast<size_t>(ws)));
-  const size_t n = (size_t)(N > 0 ? N : 0), b = (size_t)(B > 0 ? B : 0);
+  const size_t S = (size_t)mol_slices(N, B);
   MinState st;
-  st.head = reinterpret_cast<uint32_t*>(p);
-  st.start = reinterpret_cast<double*>(p + 16);
-  p += kMinHeaderBytes;
-  st.dt = reinterpret_cast<double*>(p);
-  p += min_align256(b * 8);
-  st.alpha = reinterpret_cast<double*>(p);
-  p += min_align256(b * 8);
-  st.conv = reinterpret_cast<int64_t*>(p);
-  p += min_align256(b * 8);
-  st.n_pos = reinterpret_cast<int32_t*>(p);
-  p += min_align256(b * 4);
-  st.coef = reinterpret_cast<float*>(p);
-  p += min_align256(b * 3 * sizeof(float));
-  st.x_keep = reinterpret_cast<float*>(p);
-  p += min_align256(n * 3 * sizeof(float));
-  st.v_keep = reinterpret_cast<float*>(p);
-  p += min_align256(n * 3 * sizeof(float));
-  st.slices = reinterpret_cast<double*>(p);
+  st.head = c.take<uint32_t>(kHeaderBytes / sizeof(uint32_t));
+  st.start = reinterpret_cast<double*>(st.head + 4);
+  st.dt = c.take<double>(b);
+  st.alpha = c.take<double>(b);
+  st.conv = c.take<int64_t>(b);
+  st.n_pos = c.take<int32_t>(b);
+  st.coef = c.take<float>(b * 3);
+  st.x_keep = c.take<float>(n * 3);
+  st.v_keep = c.take<float>(n * 3);
+  st.slices = c.take<double>(b * S * 4);
+  if (cell) {
+    for (double** q : {&cell->H0, &cell->D_keep, &cell->VD_keep, &cell->D_next, &cell->VD_next}) *q = c.take<double>(b * 9);
+    for (float** q : {&cell->box_keep, &cell->box_next, &cell->d32, &cell->d32_prev, &cell->d32_next}) *q = c.take<float>(b * 9);
+  }
   return st;
 }
 
-__device__ __forceinline__ uint64_t min_step(const MinState& st) { return (uint64_t)st.head[0] | ((uint64_t)st.head[1] << 32); }
+size_t min_bytes(int64_t N, int64_t B, bool with_cell) {
+  MinCell cell;
+  return layout_bytes([&](LoopCarver& c) { min_layout(c, N, B, with_cell ? &cell : nullptr); });
+}
 
-// grid (B, S): slice s of molecule m -> slices[m, s, 0..3].  Threads stride the atoms, lanes by the xor tree, waves in turn.
-__global__ __launch_bounds__(kMinThreads) void k_min_reduce(MinState st, const int* __restrict__ counts, const int* __restrict__ mstart,
-                                                            const int* __restrict__ mend, int N, int B, int S,
-                                                            const int64_t* __restrict__ batch, const float* __restrict__ vel,
-                                                            const float* __restrict__ forces, const uint8_t* __restrict__ fixed) {
-  __shared__ double sh[4][kMinThreads / 64];
-  if (st.head[2]) return;               // frozen
-  if (counts && counts[2]) return;      // overflowed: stale forces, the controller latches it
+MinState carve_min(void* ws, int64_t N, int64_t B) {
+  LoopCarver c(ws);
+  return min_layout(c, N, B, nullptr);
+}
+
+MinCell carve_min_cell(void* ws, int64_t N, int64_t B) {
+  LoopCarver c(ws);
+  MinCell cell;
+  min_layout(c, N, B, &cell);
+  return cell;
+}
+
+// grid (B, S): slice s of molecule m -> slices[m, s, 0..3].  Threads stride the atoms, lanes by the xor tree, waves in turn.  CELL: on
+// the generalised forces Ft = F D32 of the D32 the positions were formed with (`d32`: [B, 9]).
+template <bool CELL>
+__global__ __launch_bounds__(kThreads) void k_min_reduce(MinState st, const float* __restrict__ d32, const int* __restrict__ counts,
+                                                         const int* __restrict__ mstart, const int* __restrict__ mend, int N, int S,
+                                                         const int64_t* __restrict__ batch, const float* __restrict__ vel,
+                                                         const float* __restrict__ forces, const uint8_t* __restrict__ fixed) {
+  __shared__ double sh[4][kThreads / 64];
+  if (st.head[2]) return;           // frozen
+  if (counts && counts[2]) return;  // overflowed: stale forces, the controller latches it
   const int m = blockIdx.x, s = blockIdx.y;
-  const bool filter = counts ? counts[3] != 0 : batch != nullptr;
-  int a = 0, b = N;
-  if (counts && !filter) {
-    a = mstart[m];
-    b = mend[m];
-    a = a < 0 ? 0 : a;
-    b = b > N ? N : b;
-    b = b < a ? a : b;
-  }
-  const int64_t len = b - a;
-  const int i0 = a + (int)(len * s / S), i1 = a + (int)(len * (s + 1) / S);
+  const SliceRange r = mol_slice_range(counts, mstart, mend, N, S, batch, m, s);
+  float D[9];
+  if (CELL)
+#pragma unroll
+    for (int k = 0; k < 9; ++k) D[k] = d32[m * 9 + k];
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int i = i0 + (int)threadIdx.x; i < i1; i += kMinThreads) {
-    if (filter && batch && batch[i] != m) continue;  // (no batch vector: one molecule)
+  for (int i = r.i0 + (int)threadIdx.x; i < r.i1; i += kThreads) {
+    if (slice_skips(r, batch, i, m)) continue;
     float v[3], f[3], t[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       v[d] = vel[i * 3 + d];
       f[d] = forces[i * 3 + d];
     }
-    tn_min::atom_terms(v, f, fixed && fixed[i], t);
+    if (CELL) {
+      float ft[3];
+      tn_min::cell_atom_force(f, D, ft);
+      tn_min::atom_terms(v, ft, fixed && fixed[i], t);
+    } else {
+      tn_min::atom_terms(v, f, fixed && fixed[i], t);
+    }
     acc[0] += (double)t[0];
     acc[1] += (double)t[1];
     acc[2] += (double)t[2];
     acc[3] = (double)t[1] > acc[3] ? (double)t[1] : acc[3];
   }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    acc[0] += __shfl_xor(acc[0], o, 64);
-    acc[1] += __shfl_xor(acc[1], o, 64);
-    acc[2] += __shfl_xor(acc[2], o, 64);
-    const double other = __shfl_xor(acc[3], o, 64);
-    acc[3] = other > acc[3] ? other : acc[3];
-  }
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sh[k][threadIdx.x >> 6] = acc[k];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double* out = st.slices + ((int64_t)m * S + s) * 4;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[k] = ((sh[k][0] + sh[k][1]) + sh[k][2]) + sh[k][3];
-    double mx = sh[3][0];
-#pragma unroll
-    for (int w = 1; w < kMinThreads / 64; ++w) mx = sh[3][w] > mx ? sh[3][w] : mx;
-    out[3] = mx;
-  }
+  block_reduce_waves<4, 8u>(acc, sh);
+  if (threadIdx.x == 0) block_reduce_rows<4, 8u>(sh, st.slices + ((int64_t)m * S + s) * 4);
 }
 
 struct MinCtlArgs {
@@ -197,7 +188,7 @@ __device__ __forceinline__ void min_load(const MinCtlArgs& a, int m, bool fresh,
 // ONE block striding the molecules, after k_min_reduce.  Pass 1: is any molecule's move unusable?  Pass 2, only when none is:
 // every molecule's state, coefficients and log rows; then thread 0 advances the step counter (the first control after a reset
 // belongs to the start geometry and counts no step).  The move is a function of what pass 1 read, so pass 2 evaluates it again.
-__global__ __launch_bounds__(kMinThreads) void k_min_control(MinCtlArgs a) {
+__global__ __launch_bounds__(kThreads) void k_min_control(MinCtlArgs a) {
   __shared__ int bad;
   if (a.st.head[2]) return;  // frozen
   if (a.counts && a.counts[2]) {
@@ -205,14 +196,14 @@ __global__ __launch_bounds__(kMinThreads) void k_min_control(MinCtlArgs a) {
     return;
   }
   const bool fresh = a.st.head[3] != 0;
-  const uint64_t step = min_step(a.st) + (fresh ? 0 : 1);
+  const uint64_t step = loop_step(a.st.head) + (fresh ? 0 : 1);
   if (threadIdx.x == 0) bad = 0;
   __syncthreads();  // (every thread has read the header by now: thread 0 rewrites it at the end)
   int flag = 0;
   double sums[4];
   float coef[3];
   tn_min::FireState s;
-  for (int m = threadIdx.x; m < a.B; m += kMinThreads) {
+  for (int m = threadIdx.x; m < a.B; m += kThreads) {
     min_load(a, m, fresh, sums, &s);
     flag |= tn_min::fire_control(&s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef) == tn_min::FIRE_UNUSABLE;
   }
@@ -222,7 +213,7 @@ __global__ __launch_bounds__(kMinThreads) void k_min_control(MinCtlArgs a) {
     if (threadIdx.x == 0) a.st.head[2] = 2u;
     return;
   }
-  for (int m = threadIdx.x; m < a.B; m += kMinThreads) {
+  for (int m = threadIdx.x; m < a.B; m += kThreads) {
     min_load(a, m, fresh, sums, &s);
     tn_min::fire_control(&s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef);
     a.st.dt[m] = s.dt;
@@ -244,8 +235,7 @@ __global__ __launch_bounds__(kMinThreads) void k_min_control(MinCtlArgs a) {
     if (a.conv_row) a.conv_row[m] = s.converged_at;
   }
   if (threadIdx.x == 0) {
-    a.st.head[0] = (uint32_t)step;
-    a.st.head[1] = (uint32_t)(step >> 32);
+    loop_set_step(a.st.head, step);
     a.st.head[3] = 0u;
   }
 }
@@ -265,8 +255,8 @@ struct MinAtomArgs {
 // one thread per atom, the caller's atom order.  ACCEPT (after k_min_control): keep the forces of the evaluation, or, when it
 // overflowed, go back to the state the last move saved.  MOVE: save x and v, then the update with the molecule's coefficients.
 template <bool ACCEPT, bool MOVE>
-__global__ __launch_bounds__(kMinThreads) void k_min_atoms(MinAtomArgs a) {
-  const int i = blockIdx.x * kMinThreads + threadIdx.x;
+__global__ __launch_bounds__(kThreads) void k_min_atoms(MinAtomArgs a) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= a.N) return;
   const uint32_t status = a.st.head[2], fresh = a.st.head[3];
   if (status) {
@@ -314,8 +304,7 @@ __global__ __launch_bounds__(kMinThreads) void k_min_atoms(MinAtomArgs a) {
 
 __global__ void k_min_reset(MinState st, uint64_t step0, double dt0, double alpha0) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    st.head[0] = (uint32_t)step0;
-    st.head[1] = (uint32_t)(step0 >> 32);
+    loop_set_step(st.head, step0);
     st.head[2] = 0u;
     st.head[3] = 1u;
     st.start[0] = dt0;
@@ -330,104 +319,8 @@ __global__ void k_min_reset(MinState st, uint64_t step0, double dt0, double alph
 // current positions were formed with, and `d32_prev`, which the positions before the last move were formed with.  A move (the
 // end of the controller in MIDDLE, k_min_cell_commit in OPEN) saves the current values, makes the prepared ones current and moves
 // d32 to d32_prev; the per-atom kernel then forms the generalised force with d32_prev and the new position with d32.
-struct MinCell {
-  double* H0;       // [B, 9] the reference box
-  double* D_keep;   // [B, 9] before the last move
-  double* VD_keep;  // [B, 9]
-  double* D_next;   // [B, 9] what the last control prepared
-  double* VD_next;  // [B, 9]
-  float* box_keep;  // [B, 9]
-  float* box_next;  // [B, 9]
-  float* d32;       // [B, 9]
-  float* d32_prev;  // [B, 9]
-  float* d32_next;  // [B, 9]
-};
-
-size_t min_cell_bytes(int64_t N, int64_t B) {
-  const size_t b = (size_t)(B > 0 ? B : 0);
-  return min_bytes(N, B) + 5 * min_align256(b * 9 * sizeof(double)) + 5 * min_align256(b * 9 * sizeof(float));
-}
-
-MinCell carve_min_cell(void* ws, int64_t N, int64_t B) {
-  char* p = reinterpret_cast<char*>(min_align256(reinterpret_cast<size_t>(ws))) + (min_bytes(N, B) - 256);  // behind MinState
-  const size_t b = (size_t)(B > 0 ? B : 0);
-  MinCell c;
-  double** d64[5] = {&c.H0, &c.D_keep, &c.VD_keep, &c.D_next, &c.VD_next};
-  for (auto q : d64) {
-    *q = reinterpret_cast<double*>(p);
-    p += min_align256(b * 9 * sizeof(double));
-  }
-  float** f32[5] = {&c.box_keep, &c.box_next, &c.d32, &c.d32_prev, &c.d32_next};
-  for (auto q : f32) {
-    *q = reinterpret_cast<float*>(p);
-    p += min_align256(b * 9 * sizeof(float));
-  }
-  return c;
-}
-
-// head[8] (header byte 32): which sum or input was unusable when status 2 was latched (tn_min::CELL_BAD_*)
-
-// grid (B, S) as k_min_reduce, on the generalised forces Ft = F D32 of the D32 the positions were formed with
-__global__ __launch_bounds__(kMinThreads) void k_min_reduce_cell(MinState st, MinCell cs, const int* __restrict__ counts,
-                                                                 const int* __restrict__ mstart, const int* __restrict__ mend, int N, int B,
-                                                                 int S, const int64_t* __restrict__ batch, const float* __restrict__ vel,
-                                                                 const float* __restrict__ forces, const uint8_t* __restrict__ fixed) {
-  __shared__ double sh[4][kMinThreads / 64];
-  if (st.head[2]) return;           // frozen
-  if (counts && counts[2]) return;  // overflowed: stale forces, the controller latches it
-  const int m = blockIdx.x, s = blockIdx.y;
-  const bool filter = counts ? counts[3] != 0 : batch != nullptr;
-  int a = 0, b = N;
-  if (counts && !filter) {
-    a = mstart[m];
-    b = mend[m];
-    a = a < 0 ? 0 : a;
-    b = b > N ? N : b;
-    b = b < a ? a : b;
-  }
-  float d32[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) d32[k] = cs.d32[m * 9 + k];
-  const int64_t len = b - a;
-  const int i0 = a + (int)(len * s / S), i1 = a + (int)(len * (s + 1) / S);
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int i = i0 + (int)threadIdx.x; i < i1; i += kMinThreads) {
-    if (filter && batch && batch[i] != m) continue;
-    float v[3], f[3], ft[3], t[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      v[d] = vel[i * 3 + d];
-      f[d] = forces[i * 3 + d];
-    }
-    tn_min::cell_atom_force(f, d32, ft);
-    tn_min::atom_terms(v, ft, fixed && fixed[i], t);
-    acc[0] += (double)t[0];
-    acc[1] += (double)t[1];
-    acc[2] += (double)t[2];
-    acc[3] = (double)t[1] > acc[3] ? (double)t[1] : acc[3];
-  }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    acc[0] += __shfl_xor(acc[0], o, 64);
-    acc[1] += __shfl_xor(acc[1], o, 64);
-    acc[2] += __shfl_xor(acc[2], o, 64);
-    const double other = __shfl_xor(acc[3], o, 64);
-    acc[3] = other > acc[3] ? other : acc[3];
-  }
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sh[k][threadIdx.x >> 6] = acc[k];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double* out = st.slices + ((int64_t)m * S + s) * 4;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[k] = ((sh[k][0] + sh[k][1]) + sh[k][2]) + sh[k][3];
-    double mx = sh[3][0];
-#pragma unroll
-    for (int w = 1; w < kMinThreads / 64; ++w) mx = sh[3][w] > mx ? sh[3][w] : mx;
-    out[3] = mx;
-  }
-}
+// (MinCell and its layout: with MinState, above.)  head[8] (header byte 32): which sum or input was unusable when status 2 was
+// latched (tn_min::CELL_BAD_*)
 
 struct MinCellCtlArgs {
   MinCtlArgs base;
@@ -485,14 +378,14 @@ __device__ __forceinline__ void min_cell_eval(const MinCellCtlArgs& a, int m, bo
 }
 
 // k_min_control with the cell rows: ONE block striding the molecules.  On an overflow it also puts D, V_D, the box and d32 back.
-__global__ __launch_bounds__(kMinThreads) void k_min_control_cell(MinCellCtlArgs a) {
+__global__ __launch_bounds__(kThreads) void k_min_control_cell(MinCellCtlArgs a) {
   __shared__ int bad;
   const MinState& st = a.base.st;
   if (st.head[2]) return;  // frozen
   const bool fresh = st.head[3] != 0;
   if (a.base.counts && a.base.counts[2]) {
     if (!fresh)  // nothing was saved before the first control
-      for (int m = threadIdx.x; m < a.base.B; m += kMinThreads)
+      for (int m = threadIdx.x; m < a.base.B; m += kThreads)
         for (int k = 0; k < 9; ++k) {
           const int j = m * 9 + k;
           a.deform[j] = a.cs.D_keep[j];
@@ -504,12 +397,12 @@ __global__ __launch_bounds__(kMinThreads) void k_min_control_cell(MinCellCtlArgs
     if (threadIdx.x == 0) st.head[2] = 1u;
     return;
   }
-  const uint64_t step = min_step(st) + (fresh ? 0 : 1);
+  const uint64_t step = loop_step(st.head) + (fresh ? 0 : 1);
   if (threadIdx.x == 0) bad = 0;
   __syncthreads();
   MinCellOut o;
   int why = 0;
-  for (int m = threadIdx.x; m < a.base.B; m += kMinThreads) {
+  for (int m = threadIdx.x; m < a.base.B; m += kThreads) {
     min_cell_eval(a, m, fresh, (int64_t)step, &o);
     if (o.ret == tn_min::FIRE_UNUSABLE && o.why > why) why = o.why;
   }
@@ -522,7 +415,7 @@ __global__ __launch_bounds__(kMinThreads) void k_min_control_cell(MinCellCtlArgs
     }
     return;
   }
-  for (int m = threadIdx.x; m < a.base.B; m += kMinThreads) {
+  for (int m = threadIdx.x; m < a.base.B; m += kThreads) {
     min_cell_eval(a, m, fresh, (int64_t)step, &o);
     st.dt[m] = o.s.dt;
     st.alpha[m] = o.s.alpha;
@@ -551,16 +444,15 @@ __global__ __launch_bounds__(kMinThreads) void k_min_control_cell(MinCellCtlArgs
     if (a.move) min_cell_commit(a.cs, a.box, a.deform, a.cell_vel, m);
   }
   if (threadIdx.x == 0) {
-    st.head[0] = (uint32_t)step;
-    st.head[1] = (uint32_t)(step >> 32);
+    loop_set_step(st.head, step);
     st.head[3] = 0u;
   }
 }
 
 // OPEN: the cell's part of the move from what the last control prepared, before the per-atom kernel
-__global__ __launch_bounds__(kMinThreads) void k_min_cell_commit(MinState st, MinCell cs, int B, float* box, double* deform,
+__global__ __launch_bounds__(kThreads) void k_min_cell_commit(MinState st, MinCell cs, int B, float* box, double* deform,
                                                                   double* cell_vel) {
-  const int m = blockIdx.x * kMinThreads + threadIdx.x;
+  const int m = blockIdx.x * kThreads + threadIdx.x;
   if (m >= B || st.head[2] || st.head[3]) return;  // frozen, or straight after a reset: nothing is prepared yet
   min_cell_commit(cs, box, deform, cell_vel, m);
 }
@@ -574,9 +466,9 @@ struct MinCellAtomArgs {
 // k_min_atoms on xt: the generalised force from d32_prev, the update, then the position the evaluation reads from d32.  A fixed atom
 // keeps xt and so follows the cell; an atom of a converged molecule is not touched at all (its D does not change either).
 template <bool ACCEPT, bool MOVE>
-__global__ __launch_bounds__(kMinThreads) void k_min_atoms_cell(MinCellAtomArgs c) {
+__global__ __launch_bounds__(kThreads) void k_min_atoms_cell(MinCellAtomArgs c) {
   const MinAtomArgs& a = c.base;
-  const int i = blockIdx.x * kMinThreads + threadIdx.x;
+  const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= a.N) return;
   const uint32_t status = a.st.head[2], fresh = a.st.head[3];
   const int64_t m = a.batch ? a.batch[i] : 0;
@@ -646,13 +538,12 @@ __global__ __launch_bounds__(kMinThreads) void k_min_atoms_cell(MinCellAtomArgs 
 
 // the header as k_min_reset; per molecule H0 = the box, D = I, V_D = 0, every saved and prepared value equal to the current one; per
 // atom xt = x
-__global__ __launch_bounds__(kMinThreads) void k_min_reset_cell(MinState st, MinCell cs, int N, int B, uint64_t step0, double dt0,
+__global__ __launch_bounds__(kThreads) void k_min_reset_cell(MinState st, MinCell cs, int N, int B, uint64_t step0, double dt0,
                                                                  double alpha0, const float* box, double* deform, double* cell_vel,
                                                                  const float* pos, float* xt) {
-  const int i = blockIdx.x * kMinThreads + threadIdx.x;
+  const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i == 0) {
-    st.head[0] = (uint32_t)step0;
-    st.head[1] = (uint32_t)(step0 >> 32);
+    loop_set_step(st.head, step0);
     st.head[2] = 0u;
     st.head[3] = 1u;
     st.head[8] = 0u;
@@ -682,7 +573,7 @@ extern "C" {
 
 int tmdnet_min_workspace_bytes(int64_t n_atoms, int64_t n_mol, size_t* bytes) {
   if (!bytes || n_atoms < 0 || n_mol < 0 || n_atoms > INT32_MAX / 4 || n_mol > INT32_MAX / 16) return TMDNET_ERR_INVALID;
-  *bytes = min_bytes(n_atoms, n_mol);
+  *bytes = min_bytes(n_atoms, n_mol, false);
   return TMDNET_OK;
 }
 
@@ -707,19 +598,12 @@ int tmdnet_min_advance(tmdnet_model* m, void* stream, void* graph_ws, void* min_
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int N = (int)n_atoms, B = (int)n_mol;
   const MinState st = carve_min(min_ws, n_atoms, n_mol);
-  const int* counts = nullptr;
-  const int* mstart = nullptr;
-  const int* mend = nullptr;
-  if (graph_ws) {
-    const Graph g = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr);
-    counts = g.counts;
-    mstart = g.mstart;
-    mend = g.mend;
-  }
-  const dim3 block(kMinThreads);
+  const LoopGraph g = loop_graph(m, graph_ws, n_atoms, n_mol);
+  const int* counts = g.counts;
+  const dim3 block(kThreads);
   if (phase != TMDNET_MIN_OPEN) {
-    const int S = min_slices(n_atoms, n_mol);
-    hipLaunchKernelGGL(k_min_reduce, dim3(B, S), block, 0, s, st, counts, mstart, mend, N, B, S, batch, vel, forces, fixed);
+    const int S = mol_slices(n_atoms, n_mol);
+    hipLaunchKernelGGL(k_min_reduce<false>, dim3(B, S), block, 0, s, st, nullptr, counts, g.mstart, g.mend, N, S, batch, vel, forces, fixed);
     MinCtlArgs c;
     c.B = B;
     c.S = S;
@@ -755,7 +639,7 @@ int tmdnet_min_advance(tmdnet_model* m, void* stream, void* graph_ws, void* min_
     a.batch = batch;
     a.counts = counts;
     a.st = st;
-    const dim3 grid((N + kMinThreads - 1) / kMinThreads);
+    const dim3 grid((N + kThreads - 1) / kThreads);
     if (phase == TMDNET_MIN_OPEN)
       hipLaunchKernelGGL((k_min_atoms<false, true>), grid, block, 0, s, a);
     else if (phase == TMDNET_MIN_MIDDLE)
@@ -763,9 +647,7 @@ int tmdnet_min_advance(tmdnet_model* m, void* stream, void* graph_ws, void* min_
     else
       hipLaunchKernelGGL((k_min_atoms<true, false>), grid, block, 0, s, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_min_advance: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
-  return TMDNET_OK;
+  return loop_launch_result(m, "tmdnet_min_advance");
 }
 
 int tmdnet_min_status(void* stream, void* min_ws, uint64_t host[2]) {
@@ -774,14 +656,14 @@ int tmdnet_min_status(void* stream, void* min_ws, uint64_t host[2]) {
   uint32_t head[3] = {0, 0, 0};
   if (hipMemcpyAsync(head, carve_min(min_ws, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
   if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = (uint64_t)head[0] | ((uint64_t)head[1] << 32);
+  host[0] = loop_step(head);
   host[1] = head[2];
   return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
 }
 
 int tmdnet_min_workspace_bytes_cell(int64_t n_atoms, int64_t n_mol, size_t* bytes) {
   if (!bytes || n_atoms < 0 || n_mol < 0 || n_atoms > INT32_MAX / 4 || n_mol > INT32_MAX / 16) return TMDNET_ERR_INVALID;
-  *bytes = min_cell_bytes(n_atoms, n_mol);
+  *bytes = min_bytes(n_atoms, n_mol, true);
   return TMDNET_OK;
 }
 
@@ -791,7 +673,7 @@ int tmdnet_min_reset_cell(void* stream, void* min_ws, int64_t n_atoms, int64_t n
       n_mol > INT32_MAX / 16 || (n_atoms > 0 && (!pos || !xt)))
     return TMDNET_ERR_INVALID;
   const int64_t threads = 3 * n_atoms > n_mol ? 3 * n_atoms : n_mol;
-  hipLaunchKernelGGL(k_min_reset_cell, dim3((unsigned)((threads + kMinThreads - 1) / kMinThreads)), dim3(kMinThreads), 0,
+  hipLaunchKernelGGL(k_min_reset_cell, dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), carve_min(min_ws, n_atoms, n_mol), carve_min_cell(min_ws, n_atoms, n_mol),
                      (int)n_atoms, (int)n_mol, step0, dt0, alpha0, box, deform, cell_vel, pos, xt);
   return hipGetLastError() == hipSuccess ? TMDNET_OK : TMDNET_ERR_HIP;
@@ -818,19 +700,12 @@ int tmdnet_min_advance_cell(tmdnet_model* m, void* stream, void* graph_ws, void*
   const int N = (int)n_atoms, B = (int)n_mol;
   const MinState st = carve_min(min_ws, n_atoms, n_mol);
   const MinCell cs = carve_min_cell(min_ws, n_atoms, n_mol);
-  const int* counts = nullptr;
-  const int* mstart = nullptr;
-  const int* mend = nullptr;
-  if (graph_ws) {
-    const Graph g = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr);
-    counts = g.counts;
-    mstart = g.mstart;
-    mend = g.mend;
-  }
-  const dim3 block(kMinThreads);
+  const LoopGraph g = loop_graph(m, graph_ws, n_atoms, n_mol);
+  const int* counts = g.counts;
+  const dim3 block(kThreads);
   if (phase != TMDNET_MIN_OPEN) {
-    const int S = min_slices(n_atoms, n_mol);
-    hipLaunchKernelGGL(k_min_reduce_cell, dim3(B, S), block, 0, s, st, cs, counts, mstart, mend, N, B, S, batch, vel, forces, fixed);
+    const int S = mol_slices(n_atoms, n_mol);
+    hipLaunchKernelGGL(k_min_reduce<true>, dim3(B, S), block, 0, s, st, cs.d32, counts, g.mstart, g.mend, N, S, batch, vel, forces, fixed);
     MinCellCtlArgs c;
     c.base.B = B;
     c.base.S = S;
@@ -868,7 +743,7 @@ int tmdnet_min_advance_cell(tmdnet_model* m, void* stream, void* graph_ws, void*
     c.cell_force_row = cell_force_log_row;
     hipLaunchKernelGGL(k_min_control_cell, dim3(1), block, 0, s, c);
   } else {
-    hipLaunchKernelGGL(k_min_cell_commit, dim3((B + kMinThreads - 1) / kMinThreads), block, 0, s, st, cs, B, box, deform, cell_vel);
+    hipLaunchKernelGGL(k_min_cell_commit, dim3((B + kThreads - 1) / kThreads), block, 0, s, st, cs, B, box, deform, cell_vel);
   }
   if (N > 0) {
     MinCellAtomArgs a;
@@ -884,7 +759,7 @@ int tmdnet_min_advance_cell(tmdnet_model* m, void* stream, void* graph_ws, void*
     a.base.st = st;
     a.cs = cs;
     a.xt = xt;
-    const dim3 grid((N + kMinThreads - 1) / kMinThreads);
+    const dim3 grid((N + kThreads - 1) / kThreads);
     if (phase == TMDNET_MIN_OPEN)
       hipLaunchKernelGGL((k_min_atoms_cell<false, true>), grid, block, 0, s, a);
     else if (phase == TMDNET_MIN_MIDDLE)
@@ -892,9 +767,7 @@ int tmdnet_min_advance_cell(tmdnet_model* m, void* stream, void* graph_ws, void*
     else
       hipLaunchKernelGGL((k_min_atoms_cell<true, false>), grid, block, 0, s, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_min_advance_cell: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
-  return TMDNET_OK;
+  return loop_launch_result(m, "tmdnet_min_advance_cell");
 }
 
 int tmdnet_min_status_cell(void* stream, void* min_ws, uint64_t host[3]) {
@@ -903,7 +776,7 @@ int tmdnet_min_status_cell(void* stream, void* min_ws, uint64_t host[3]) {
   uint32_t head[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (hipMemcpyAsync(head, carve_min(min_ws, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
   if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = (uint64_t)head[0] | ((uint64_t)head[1] << 32);
+  host[0] = loop_step(head);
   host[1] = head[2];
   host[2] = head[2] == 2 ? head[8] : 0;
   return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;

@@ -14,18 +14,18 @@
 //   atoms     per atom: accept (F_neb -> forces_keep, or the saved state back after an overflow) and, in MIDDLE, the move
 // CLOSE omits the move, OPEN is the move alone from the coefficients the workspace holds and the kept F_neb.
 //
-// Reductions follow k_min_reduce: threads stride the atoms of a slice, lanes add by the wave's xor tree, waves in turn, slices in
-// slice order.  No floating-point atomics: repeats are bit-identical.
+// Reductions are tn_loop.h's, as in k_min_reduce: threads stride the atoms of a slice, lanes add by the wave's xor tree, waves in
+// turn, slices in slice order.  No floating-point atomics: repeats are bit-identical.
 //
 // Overflow, non-finite sums and unusable tangents follow the minimiser's protocol: the controller is the only kernel that writes
 // the status word; an overflowed evaluation latches status 1 and the per-atom kernel puts x and v back; a band that still moves
 // and has an energy that is not finite, a tangent of length zero or a sum that is not finite latches status 2 (the cause in header
 // word 5) before anything of that step is written.  From then on every launch returns at once until tmdnet_neb_reset.
 #include <cmath>
-#include <string>
 
 #include "tmdnet_amd.h"
 #include "tn_common.h"
+#include "tn_loop.h"
 #include "tn_model.h"
 #include "tn_neb_math.h"
 
@@ -33,8 +33,6 @@ namespace tn {
 
 namespace {
 
-constexpr int kNebThreads = 256;
-constexpr size_t kNebHeaderBytes = 256;
 // The header: six uint32 words, then two doubles.  Words 0 / 1 the step counter (lo / hi), 2 the status, 3 "reset, not yet controlled",
 constexpr int kNebClimbWord = 4;       // 1: the climbing image is on
 constexpr int kNebCauseWord = 5;       // which input was unusable when status 2 was latched (tn_neb::NEB_*)
@@ -42,7 +40,7 @@ constexpr int kNebHeadWords = 6;       // words the status entry reads back
 constexpr size_t kNebStartByte = 32;   // dt0, alpha0 (fp64)
 static_assert(kNebClimbWord > 3 && kNebCauseWord != kNebClimbWord && kNebCauseWord < kNebHeadWords, "header words must not overlap");
 static_assert(kNebHeadWords * sizeof(uint32_t) <= kNebStartByte && kNebStartByte % sizeof(double) == 0 &&
-                  kNebStartByte + 2 * sizeof(double) <= kNebHeaderBytes,
+                  kNebStartByte + 2 * sizeof(double) <= kHeaderBytes,
               "the start values lie behind the header words, aligned, inside the header");
 
 struct NebState {  // views into the caller's workspace
@@ -64,98 +62,36 @@ struct NebState {  // views into the caller's workspace
   float* f_neb;         // [N, 3] F_neb of the evaluation being controlled
 };
 
-inline size_t neb_align256(size_t n) { return (n + 255) & ~size_t(255); }
-
-// slices per image: tn_min.hip's min_slices with one image as the molecule
-int neb_slices(int64_t n) {
-  if (n <= 1024) return 1;
-  const int64_t s = (n + 1023) / 1024;
-  return (int)(s > 256 ? 256 : s);
-}
-
-struct NebSizes {
-  size_t g, gm, N, S;
-};
-
-NebSizes neb_sizes(int64_t n, int64_t M, int64_t G) {
-  NebSizes z;
-  z.g = (size_t)(G > 0 ? G : 0);
-  z.gm = z.g * (size_t)(M > 0 ? M : 0);
-  z.N = z.gm * (size_t)(n > 0 ? n : 0);
-  z.S = (size_t)neb_slices(n);
-  return z;
-}
-
-size_t neb_bytes(int64_t n, int64_t M, int64_t G) {
-  const NebSizes z = neb_sizes(n, M, G);
-  return kNebHeaderBytes + 3 * neb_align256(z.g * 8) + neb_align256(z.g * 4) + neb_align256(z.g * 3 * sizeof(float)) +
-         neb_align256(z.gm * 5 * 8) + neb_align256(z.gm * 2 * 8) + neb_align256(z.gm * 2 * sizeof(float)) + neb_align256(z.gm * 4) +
-         neb_align256(z.gm * z.S * 6 * 8) + neb_align256(z.gm * z.S * 4 * 8) + 3 * neb_align256(z.N * 3 * sizeof(float)) +
-         256;  // + room to align the pointer
-}
-
-NebState carve_neb(void* ws, int64_t n, int64_t M, int64_t G) {
-  char* p = reinterpret_cast<char*>(neb_align256(reinterpret_cast<size_t>(ws)));
-  const NebSizes z = neb_sizes(n, M, G);
+NebState neb_layout(LoopCarver& c, int64_t n, int64_t M, int64_t G) {
+  const size_t g = (size_t)(G > 0 ? G : 0), gm = g * (size_t)(M > 0 ? M : 0), N = gm * (size_t)(n > 0 ? n : 0);
+  const size_t S = (size_t)mol_slices(n, 1);  // slices per image: one image is the molecule
   NebState st;
-  st.head = reinterpret_cast<uint32_t*>(p);
-  st.start = reinterpret_cast<double*>(p + kNebStartByte);
-  p += kNebHeaderBytes;
-  auto take = [&p](size_t bytes) {
-    char* q = p;
-    p += neb_align256(bytes);
-    return q;
-  };
-  st.dt = reinterpret_cast<double*>(take(z.g * 8));
-  st.alpha = reinterpret_cast<double*>(take(z.g * 8));
-  st.conv = reinterpret_cast<int64_t*>(take(z.g * 8));
-  st.n_pos = reinterpret_cast<int32_t*>(take(z.g * 4));
-  st.coef = reinterpret_cast<float*>(take(z.g * 3 * sizeof(float)));
-  st.img_sums = reinterpret_cast<double*>(take(z.gm * 5 * 8));
-  st.img_w = reinterpret_cast<double*>(take(z.gm * 2 * 8));
-  st.img_s = reinterpret_cast<float*>(take(z.gm * 2 * sizeof(float)));
-  st.img_why = reinterpret_cast<int32_t*>(take(z.gm * 4));
-  st.path_slices = reinterpret_cast<double*>(take(z.gm * z.S * 6 * 8));
-  st.fire_slices = reinterpret_cast<double*>(take(z.gm * z.S * 4 * 8));
-  st.x_keep = reinterpret_cast<float*>(take(z.N * 3 * sizeof(float)));
-  st.v_keep = reinterpret_cast<float*>(take(z.N * 3 * sizeof(float)));
-  st.f_neb = reinterpret_cast<float*>(take(z.N * 3 * sizeof(float)));
+  st.head = c.take<uint32_t>(kHeaderBytes / sizeof(uint32_t));
+  st.start = reinterpret_cast<double*>(reinterpret_cast<char*>(st.head) + kNebStartByte);
+  st.dt = c.take<double>(g);
+  st.alpha = c.take<double>(g);
+  st.conv = c.take<int64_t>(g);
+  st.n_pos = c.take<int32_t>(g);
+  st.coef = c.take<float>(g * 3);
+  st.img_sums = c.take<double>(gm * 5);
+  st.img_w = c.take<double>(gm * 2);
+  st.img_s = c.take<float>(gm * 2);
+  st.img_why = c.take<int32_t>(gm);
+  st.path_slices = c.take<double>(gm * S * 6);
+  st.fire_slices = c.take<double>(gm * S * 4);
+  st.x_keep = c.take<float>(N * 3);
+  st.v_keep = c.take<float>(N * 3);
+  st.f_neb = c.take<float>(N * 3);
   return st;
 }
 
-__device__ __forceinline__ uint64_t neb_step(const NebState& st) { return (uint64_t)st.head[0] | ((uint64_t)st.head[1] << 32); }
+size_t neb_bytes(int64_t n, int64_t M, int64_t G) {
+  return layout_bytes([&](LoopCarver& c) { neb_layout(c, n, M, G); });
+}
 
-// K sums of one block in the order of k_min_reduce (lanes by the xor tree, waves in turn); entry MAXK (-1: none) takes the maximum
-// instead.  Thread 0 holds the result in acc.
-template <int K, int MAXK>
-__device__ __forceinline__ void neb_block_reduce(double acc[K], double (*sh)[kNebThreads / 64]) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1)
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const double other = __shfl_xor(acc[k], o, 64);
-      if (k == MAXK)
-        acc[k] = other > acc[k] ? other : acc[k];
-      else
-        acc[k] += other;
-    }
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) sh[k][threadIdx.x >> 6] = acc[k];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      if (k == MAXK) {
-        double mx = sh[k][0];
-#pragma unroll
-        for (int w = 1; w < kNebThreads / 64; ++w) mx = sh[k][w] > mx ? sh[k][w] : mx;
-        acc[k] = mx;
-      } else {
-        acc[k] = ((sh[k][0] + sh[k][1]) + sh[k][2]) + sh[k][3];
-      }
-    }
-  }
+NebState carve_neb(void* ws, int64_t n, int64_t M, int64_t G) {
+  LoopCarver c(ws);
+  return neb_layout(c, n, M, G);
 }
 
 struct NebGeom {
@@ -175,17 +111,17 @@ __device__ __forceinline__ void neb_load_diff(const float* __restrict__ pos, int
 }
 
 // grid (G M, S): slice s of interior image img -> path_slices[img, s, 0..5]
-__global__ __launch_bounds__(kNebThreads) void k_neb_path(NebState st, NebGeom g, const int* __restrict__ counts,
+__global__ __launch_bounds__(kThreads) void k_neb_path(NebState st, NebGeom g, const int* __restrict__ counts,
                                                           const float* __restrict__ pos, const float* __restrict__ forces,
                                                           const uint8_t* __restrict__ fixed) {
-  __shared__ double sh[6][kNebThreads / 64];
+  __shared__ double sh[6][kThreads / 64];
   if (st.head[2]) return;           // frozen
   if (counts && counts[2]) return;  // overflowed: stale forces, the controller latches it
   const int img = blockIdx.x, s = blockIdx.y, i = img % g.M;
   if (i == 0 || i == g.M - 1) return;  // an endpoint has no tangent
   const int a0 = (int)((int64_t)g.n * s / g.S), a1 = (int)((int64_t)g.n * (s + 1) / g.S);
   double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int a = a0 + (int)threadIdx.x; a < a1; a += kNebThreads) {
+  for (int a = a0 + (int)threadIdx.x; a < a1; a += kThreads) {
     const int64_t row = (int64_t)img * g.n + a;
     const int fx = fixed && fixed[a];
     float dp[3], dm[3], f[3], t[5];
@@ -197,27 +133,23 @@ __global__ __launch_bounds__(kNebThreads) void k_neb_path(NebState st, NebGeom g
     for (int k = 0; k < 5; ++k) acc[k] += (double)t[k];
     acc[5] += fx ? 0.0 : 1.0;  // (a count: exact)
   }
-  neb_block_reduce<6, -1>(acc, sh);
-  if (threadIdx.x == 0) {
-    double* out = st.path_slices + ((int64_t)img * g.S + s) * 6;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) out[k] = acc[k];
-  }
+  block_reduce_waves<6, 0u>(acc, sh);
+  if (threadIdx.x == 0) block_reduce_rows<6, 0u>(sh, st.path_slices + ((int64_t)img * g.S + s) * 6);
 }
 
 // grid (G M, S), after k_neb_path: the image's coefficients (every block of the image computes the same bits; the block of slice 0
 // records them), F_neb of the slice's atoms into the workspace, fire_slices[img, s, 0..3] = v.F_neb, F_neb.F_neb, v.v, max |F_neb|^2
-__global__ __launch_bounds__(kNebThreads) void k_neb_project(NebState st, NebGeom g, const int* __restrict__ counts,
+__global__ __launch_bounds__(kThreads) void k_neb_project(NebState st, NebGeom g, const int* __restrict__ counts,
                                                              const float* __restrict__ pos, const float* __restrict__ vel,
                                                              const float* __restrict__ forces, const float* __restrict__ energy,
                                                              const uint8_t* __restrict__ fixed, double spring_k) {
-  __shared__ double sh[4][kNebThreads / 64];
+  __shared__ double sh[4][kThreads / 64];
   if (st.head[2]) return;
   if (counts && counts[2]) return;
   const int img = blockIdx.x, s = blockIdx.y, i = img % g.M;
   const int a0 = (int)((int64_t)g.n * s / g.S), a1 = (int)((int64_t)g.n * (s + 1) / g.S);
   if (i == 0 || i == g.M - 1) {  // an endpoint feels no band force
-    for (int a = a0 + (int)threadIdx.x; a < a1; a += kNebThreads) {
+    for (int a = a0 + (int)threadIdx.x; a < a1; a += kThreads) {
       const int64_t row = (int64_t)img * g.n + a;
 #pragma unroll
       for (int d = 0; d < 3; ++d) st.f_neb[row * 3 + d] = 0.f;
@@ -241,7 +173,7 @@ __global__ __launch_bounds__(kNebThreads) void k_neb_project(NebState st, NebGeo
     st.img_why[img] = why;
   }
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int a = a0 + (int)threadIdx.x; a < a1; a += kNebThreads) {
+  for (int a = a0 + (int)threadIdx.x; a < a1; a += kThreads) {
     const int64_t row = (int64_t)img * g.n + a;
     const int fx = fixed && fixed[a];
     float dp[3], dm[3], f[3], v[3], fn[3], t[3];
@@ -265,12 +197,8 @@ __global__ __launch_bounds__(kNebThreads) void k_neb_project(NebState st, NebGeo
     acc[2] += (double)t[2];
     acc[3] = (double)t[1] > acc[3] ? (double)t[1] : acc[3];
   }
-  neb_block_reduce<4, 3>(acc, sh);
-  if (threadIdx.x == 0) {
-    double* out = st.fire_slices + ((int64_t)img * g.S + s) * 4;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = acc[k];
-  }
+  block_reduce_waves<4, 8u>(acc, sh);
+  if (threadIdx.x == 0) block_reduce_rows<4, 8u>(sh, st.fire_slices + ((int64_t)img * g.S + s) * 4);
 }
 
 struct NebCtlArgs {
@@ -329,7 +257,7 @@ __device__ __forceinline__ int neb_load(const NebCtlArgs& a, int b, bool fresh, 
 
 // ONE block striding the bands, after k_neb_project: k_min_control with the tangents' causes.  Pass 1: is any band that still moves
 // unusable?  Pass 2, only when none is: every band's state, coefficients and log rows; then thread 0 advances the step counter.
-__global__ __launch_bounds__(kNebThreads) void k_neb_control(NebCtlArgs a) {
+__global__ __launch_bounds__(kThreads) void k_neb_control(NebCtlArgs a) {
   __shared__ int bad;
   if (a.st.head[2]) return;  // frozen
   if (a.counts && a.counts[2]) {
@@ -337,14 +265,14 @@ __global__ __launch_bounds__(kNebThreads) void k_neb_control(NebCtlArgs a) {
     return;
   }
   const bool fresh = a.st.head[3] != 0;
-  const uint64_t step = neb_step(a.st) + (fresh ? 0 : 1);
+  const uint64_t step = loop_step(a.st.head) + (fresh ? 0 : 1);
   if (threadIdx.x == 0) bad = 0;
   __syncthreads();  // (every thread has read the header by now: thread 0 rewrites it at the end)
   int cause = 0;
   double sums[4];
   float coef[3];
   tn_min::FireState s;
-  for (int b = threadIdx.x; b < a.g.G; b += kNebThreads) {
+  for (int b = threadIdx.x; b < a.g.G; b += kThreads) {
     const int why = neb_load(a, b, fresh, sums, &s);
     if (s.converged_at >= 0) continue;  // a band that has converged looks at nothing
     int c = why;
@@ -362,7 +290,7 @@ __global__ __launch_bounds__(kNebThreads) void k_neb_control(NebCtlArgs a) {
     return;
   }
   const int M = a.g.M;
-  for (int b = threadIdx.x; b < a.g.G; b += kNebThreads) {
+  for (int b = threadIdx.x; b < a.g.G; b += kThreads) {
     neb_load(a, b, fresh, sums, &s);
     tn_min::fire_control(&s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef);
     a.st.dt[b] = s.dt;
@@ -399,8 +327,7 @@ __global__ __launch_bounds__(kNebThreads) void k_neb_control(NebCtlArgs a) {
     }
   }
   if (threadIdx.x == 0) {
-    a.st.head[0] = (uint32_t)step;
-    a.st.head[1] = (uint32_t)(step >> 32);
+    loop_set_step(a.st.head, step);
     a.st.head[3] = 0u;
   }
 }
@@ -420,8 +347,8 @@ struct NebAtomArgs {
 // one thread per row.  ACCEPT (after k_neb_control): keep F_neb of the evaluation, or, when it overflowed, go back to the state the
 // last move saved.  MOVE: save x and v, then the update with the band's coefficients (ACCEPT: on the F_neb just made, else on `forces`).
 template <bool ACCEPT, bool MOVE>
-__global__ __launch_bounds__(kNebThreads) void k_neb_atoms(NebAtomArgs a) {
-  const int64_t r = (int64_t)blockIdx.x * kNebThreads + threadIdx.x;
+__global__ __launch_bounds__(kThreads) void k_neb_atoms(NebAtomArgs a) {
+  const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (r >= a.N) return;
   const uint32_t status = a.st.head[2], fresh = a.st.head[3];
   if (status) {
@@ -467,8 +394,7 @@ __global__ __launch_bounds__(kNebThreads) void k_neb_atoms(NebAtomArgs a) {
 
 __global__ void k_neb_reset(NebState st, uint64_t step0, double dt0, double alpha0, uint32_t climb) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    st.head[0] = (uint32_t)step0;
-    st.head[1] = (uint32_t)(step0 >> 32);
+    loop_set_step(st.head, step0);
     st.head[2] = 0u;
     st.head[3] = 1u;
     st.head[kNebClimbWord] = climb;
@@ -524,12 +450,11 @@ int tmdnet_neb_advance(tmdnet_model* m, void* stream, void* graph_ws, void* neb_
   g.n = (int)n_atoms_per_image;
   g.M = (int)n_images;
   g.G = (int)n_bands;
-  g.S = neb_slices(n_atoms_per_image);
+  g.S = mol_slices(n_atoms_per_image, 1);
   const int64_t n_img = n_images * n_bands, N = n_img * n_atoms_per_image;
   const NebState st = carve_neb(neb_ws, n_atoms_per_image, n_images, n_bands);
-  const int* counts = nullptr;
-  if (graph_ws) counts = carve_graph(graph_ws, N, n_img, (int64_t)m->hp.max_num_neighbors * N, nullptr).counts;
-  const dim3 block(kNebThreads);
+  const int* counts = loop_graph(m, graph_ws, N, n_img).counts;
+  const dim3 block(kThreads);
   if (phase != TMDNET_MIN_OPEN) {
     const dim3 grid((unsigned)n_img, (unsigned)g.S);
     hipLaunchKernelGGL(k_neb_path, grid, block, 0, s, st, g, counts, pos, forces, fixed);
@@ -571,7 +496,7 @@ int tmdnet_neb_advance(tmdnet_model* m, void* stream, void* graph_ws, void* neb_
     a.fixed = fixed;
     a.counts = counts;
     a.st = st;
-    const dim3 grid((unsigned)((N + kNebThreads - 1) / kNebThreads));
+    const dim3 grid((unsigned)((N + kThreads - 1) / kThreads));
     if (phase == TMDNET_MIN_OPEN)
       hipLaunchKernelGGL((k_neb_atoms<false, true>), grid, block, 0, s, a);
     else if (phase == TMDNET_MIN_MIDDLE)
@@ -579,9 +504,7 @@ int tmdnet_neb_advance(tmdnet_model* m, void* stream, void* graph_ws, void* neb_
     else
       hipLaunchKernelGGL((k_neb_atoms<true, false>), grid, block, 0, s, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_neb_advance: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
-  return TMDNET_OK;
+  return loop_launch_result(m, "tmdnet_neb_advance");
 }
 
 int tmdnet_neb_status(void* stream, void* neb_ws, uint64_t host[3]) {
@@ -590,7 +513,7 @@ int tmdnet_neb_status(void* stream, void* neb_ws, uint64_t host[3]) {
   uint32_t head[kNebHeadWords] = {0, 0, 0, 0, 0, 0};
   if (hipMemcpyAsync(head, carve_neb(neb_ws, 0, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
   if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = (uint64_t)head[0] | ((uint64_t)head[1] << 32);
+  host[0] = loop_step(head);
   host[1] = head[2];
   host[2] = head[2] == 2 ? head[kNebCauseWord] : 0;
   return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;

@@ -12,8 +12,6 @@
 // tried.  Launch 2 (k_remd_atoms, one thread per atom): from the replica's new slot and the pair's flag, the velocity factor and
 // the new sigma.  Both launches return at once when the status word is set or the evaluation of this step overflowed: a frozen
 // loop exchanges nothing.  No atomics; the result is a function of (seed, step, energies).
-#include <string>
-
 #include "tmdnet_amd.h"
 #include "tn_common.h"
 #include "tn_md_state.h"
@@ -44,10 +42,13 @@ struct RemdArgs {
   MdState st;
 };
 
+// the exchange workspace: one accept flag per neighbouring pair of every ladder
+inline uint8_t* remd_layout(LoopCarver& c, int64_t G, int64_t R) { return c.take<uint8_t>((size_t)G * (size_t)(R - 1)); }
+
 __device__ __forceinline__ bool remd_frozen(const RemdArgs& a) { return a.st.head[2] != 0u || (a.counts && a.counts[2]); }
 
 // the closing launch's reduction has advanced the counter: it reads the number of completed steps
-__device__ __forceinline__ uint64_t remd_step(const RemdArgs& a) { return (uint64_t)a.st.head[0] | ((uint64_t)a.st.head[1] << 32); }
+__device__ __forceinline__ uint64_t remd_step(const RemdArgs& a) { return loop_step(a.st.head); }
 
 __global__ __launch_bounds__(kThreads) void k_remd_decide(RemdArgs a) {
   const int t = blockIdx.x * kThreads + threadIdx.x;
@@ -89,7 +90,7 @@ extern "C" {
 
 int tmdnet_md_exchange_workspace_bytes(int64_t n_mol, int32_t ladder, size_t* bytes) {
   if (!bytes || ladder < 2 || n_mol < 1 || n_mol > INT32_MAX / 16 || n_mol % ladder != 0) return TMDNET_ERR_INVALID;
-  *bytes = align256((size_t)(n_mol / ladder) * (size_t)(ladder - 1)) + 256;  // one flag per pair, and room to align the caller's pointer
+  *bytes = layout_bytes([&](LoopCarver& c) { remd_layout(c, n_mol / ladder, ladder); });
   return TMDNET_OK;
 }
 
@@ -119,19 +120,17 @@ int tmdnet_md_exchange(tmdnet_model* m, void* stream, void* graph_ws, void* md_w
   a.down = scale_down;
   a.slot = slot;
   a.holder = holder;
-  a.accept = reinterpret_cast<uint8_t*>(align256(reinterpret_cast<size_t>(ex_ws)));
+  LoopCarver c(ex_ws);
+  a.accept = remd_layout(c, a.G, a.R);
   a.slot_log = slot_log_row;
   a.accept_log = accept_log_row;
   a.counters = counters;
-  a.counts = nullptr;
+  a.counts = loop_graph(m, graph_ws, n_atoms, n_mol).counts;
   a.st = carve_md(md_ws, n_atoms, n_mol);
-  if (graph_ws) a.counts = carve_graph(graph_ws, n_atoms, n_mol, (int64_t)m->hp.max_num_neighbors * n_atoms, nullptr).counts;
   const dim3 block(kThreads);
   hipLaunchKernelGGL(k_remd_decide, dim3(((int)n_mol + kThreads - 1) / kThreads), block, 0, s, a);
   if (a.N > 0) hipLaunchKernelGGL(k_remd_atoms, dim3((a.N + kThreads - 1) / kThreads), block, 0, s, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return m ? fail(m, TMDNET_ERR_HIP, std::string("tmdnet_md_exchange: ") + hipGetErrorString(e)) : TMDNET_ERR_HIP;
-  return TMDNET_OK;
+  return loop_launch_result(m, "tmdnet_md_exchange");
 }
 
 }  // extern "C"
