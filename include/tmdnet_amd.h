@@ -977,6 +977,69 @@ int tmdnet_md_bias(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, v
                    double bias_factor, int64_t pace, int32_t walkers_per_group, int64_t capacity, double* cv_log_row,
                    double* restraint_log_row, double* bias_log_row, float* force_log_row);
 
+/* ---- Observables of the device-resident MD loop (csrc/tn_observe.hip; additive exports, the ABI revision stays 10) -------------
+ * Sample frames, the pair-distance histogram g(r), the mean-square displacement and the velocity autocorrelation, recorded inside
+ * the captured graph.  The observer sits where the bias launch sits: a sampled step is
+ *     evaluation;  tmdnet_md_observe(...);  tmdnet_md_advance(TMDNET_MD_MIDDLE or _CLOSE, ...)
+ * It reads pos, vel and the caller's tables and writes ONLY into obs_ws: the trajectory keeps every bit.  At that point the step
+ * counter n of md_ws counts the completed steps, pos is x at the full step s = n + 1 and vel is the leapfrog velocity v(s - 1/2)
+ * the opening half stored (after the opening kick and, with constraints, after SHAKE's correction).
+ * Sampling: s0 is what tmdnet_md_observe_start wrote.  Step s is a sample when s > s0 and (s - s0) % every == 0; its index is
+ * j = (s - s0) / every - 1, computed on the device from the 64-bit counter.  The caller enqueues the entry only at the sampling
+ * positions of its graph (replay position k with (k + 1) % every == 0 when every divides the steps of a replay), so other steps cost
+ * nothing; a launch at a step that is no sample writes nothing.  There is no sample counter on the device: the number of samples
+ * recorded is (n - s0) / every for the n tmdnet_md_status reports.
+ * Frames (frame_capacity = F > 0): row j % F of a ring of F position frames (and velocity frames with frame_velocities) gets the
+ * bits of pos (vel), in the caller's atom order.
+ * Histogram (n_pair_types = P in 1..4, bins <= 1024): per molecule and pair type, counts[m][p][bin] += 1 (uint64) for every pair of
+ * atoms i < j of molecule m whose selector masks match type p - one atom matches selector a (bit 2p of atom_mask) and the other
+ * selector b (bit 2p + 1), in either orientation, once - and whose squared distance d2, the engine's pair geometry in fp32 with the
+ * minimum image of that molecule's box (delta = pos[j] - pos[i], fused shifts z -> y -> x), satisfies d2 < r_max2:
+ * bin = min((int)(sqrtf(d2) * inv_dr), bins - 1), sqrtf correctly rounded, the product one rounded fp32 multiplication.  The caller
+ * passes r_max2 = r_max^2 and inv_dr = bins / r_max, each formed in fp64 and rounded once.  The minimum image is exact only for r_max
+ * up to half the smallest height of the box; the caller checks that.  Molecules are contiguous (mol_start, a sorted batch); the
+ * caller's table `tiles` holds one row (m, it, jt), jt >= it, per pair of 256-atom tiles of a molecule, one block each.  All adds are
+ * integer atomicAdd on LDS and on global memory: sums do not depend on their order, repeats are bit-identical.
+ * MSD (n_msd_groups = G in 1..4, msd_capacity = T): msd[j][m][g] = sum over the atoms of molecule m in group g (bit 8 + g of
+ * atom_mask) of |pos_i - origin_i|^2 in fp64 on the fp32 values; origin is the pos tmdnet_md_observe_start copied.  Samples j >= T
+ * are not written.  The caller divides by the group sizes.
+ * VACF (n_vacf_groups = G in 1..4, lags = L <= 256): vel goes into row j % L of a ring; then for every lag l <= min(j, L - 1),
+ * acc[m][g][l] += sum over the atoms of molecule m in group g (bit 16 + g) of v_i(j) . v_i(j - l), in fp64.  The caller divides
+ * by (n_samples - l) and the group size.
+ * fp64 sums have a fixed order (a thread strides by 256, lanes by the wave xor tree, waves in turn), without floating-point
+ * atomics.  Frozen state: when the status word of md_ws is set, or the evaluation of this step overflowed (graph_ws), nothing is
+ * written.  Enqueues at most three launches: the per-atom copies, the histogram, and a grid (n_mol, 1 + L) for MSD and VACF.
+ *   obs_ws        tmdnet_md_observe_workspace_bytes(...) bytes, aligned up to 256 by the callee; arrays, each on a multiple of 256
+ *                 bytes, an array that is off taking none: a 256-byte header (uint64 s0), frames pos [F, N, 3] float, frames vel
+ *                 [F, N, 3] float, counts [B, P, bins] uint64, origin [N, 3] float, msd [T, B, G] double, ring [L, N, 3] float,
+ *                 acc [B, G, L] double.
+ *   batch [n_atoms] int64 (NULL: one molecule), box [3, 3] (box_mode 1) or [n_mol, 3, 3] (box_mode 2) or NULL (box_mode 0).
+ *   atom_mask [n_atoms] uint32, mol_start [n_mol + 1] int32 and tiles [n_tiles, 3] int32 (both read with n_pair_types > 0 only).
+ * TMDNET_ERR_INVALID: every < 1, no observable, more than 4 pair types or groups, bins outside 1..1024, lags outside 1..256,
+ * msd_capacity < 1, r_max2 or inv_dr not positive, a box_mode that does not fit box, or a NULL workspace, position, velocity or
+ * table pointer. */
+typedef struct {
+  int32_t every;            /* S: the sampling interval in steps */
+  int32_t frame_capacity;   /* F, 0: no frames */
+  int32_t frame_velocities; /* != 0: velocity frames too */
+  int32_t n_pair_types;     /* P, 0: no histogram */
+  int32_t bins;
+  float r_max2;
+  float inv_dr;
+  int32_t n_msd_groups;     /* 0: no MSD */
+  int32_t n_vacf_groups;    /* 0: no VACF */
+  int32_t lags;             /* L */
+  int64_t msd_capacity;     /* T */
+} tmdnet_md_observe_spec;
+int tmdnet_md_observe_workspace_bytes(int64_t n_atoms, int64_t n_mol, const tmdnet_md_observe_spec* spec, size_t* bytes);
+/* Enqueues: the whole workspace zeroed (histogram, logs, accumulators, rings), s0 into its header and pos into origin.  Required
+ * once before the first tmdnet_md_observe on a workspace, and again whenever the loop is given new positions or a new step. */
+int tmdnet_md_observe_start(void* stream, void* obs_ws, int64_t n_atoms, int64_t n_mol, const tmdnet_md_observe_spec* spec, uint64_t s0,
+                            const float* pos);
+int tmdnet_md_observe(tmdnet_model* m, void* stream, void* graph_ws, void* md_ws, void* obs_ws, int64_t n_atoms, int64_t n_mol,
+                      const tmdnet_md_observe_spec* spec, const float* pos, const float* vel, const int64_t* batch, const float* box,
+                      int32_t box_mode, const uint32_t* atom_mask, const int32_t* mol_start, const int32_t* tiles, int64_t n_tiles);
+
 /* ---- Distance constraints of the device-resident MD loop (csrc/tn_md_cons.hip; additive exports, the ABI revision stays 10) ------
  * Holonomic constraints |x_i - x_j| = d_c by RATTLE (Andersen, J. Comput. Phys. 52, 24, 1983) in the splitting above:
  *     B  v <- v + hk F

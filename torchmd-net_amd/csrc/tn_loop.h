@@ -1,6 +1,6 @@
 // What every captured loop needs on the device side, in one place: the MD loop and its barostats, thermostats, constraints, replica
-// exchange, bias and committee gate (tn_md*.hip, tn_remd.hip, tn_bias.hip, tn_committee.hip) and the optimisers (tn_min.hip,
-// tn_lbfgs.hip, tn_neb.hip).  Workspace layout (align256, Carver), the slices of a molecule's atoms (mol_slices, mol_slice_range),
+// exchange, bias, observer and committee gate (tn_md*.hip, tn_remd.hip, tn_bias.hip, tn_observe.hip, tn_committee.hip) and the
+// optimisers (tn_min.hip, tn_lbfgs.hip, tn_neb.hip).  Workspace layout (align256, Carver), the slices of a molecule's atoms (mol_slices, mol_slice_range),
 // the 64-bit step counter of a workspace header, the fixed-order block reduction, the prelude and tail of a C entry (loop_graph,
 // loop_launch_result), the opening half of an MD step and the two-pass per-molecule controller.  Nothing here belongs to one loop
 // only.  Everything sits in an unnamed namespace: every file that includes this header gets its own copy.  The host parts compile

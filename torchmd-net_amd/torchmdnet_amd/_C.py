@@ -98,6 +98,16 @@ class CommitteeGate(C.Structure):
                [(n, C.c_void_p) for n in ("md_ws", "flagged_at", "flagged_dev", "flagged_atom", "flagged_pos")]
 
 
+class ObserveSpec(C.Structure):
+    """tmdnet_md_observe_spec (include/tmdnet_amd.h): what the MD loop's observer records and how large its arrays are."""
+    _fields_ = [("every", C.c_int32), ("frame_capacity", C.c_int32), ("frame_velocities", C.c_int32), ("n_pair_types", C.c_int32),
+                ("bins", C.c_int32), ("r_max2", C.c_float), ("inv_dr", C.c_float), ("n_msd_groups", C.c_int32),
+                ("n_vacf_groups", C.c_int32), ("lags", C.c_int32), ("msd_capacity", C.c_int64)]
+
+
+# limits of the observer (tn_obs::kMax* of csrc/tn_observe_math.h) and the tile of its pair sweep
+OBSERVE_MAX_TYPES, OBSERVE_MAX_BINS, OBSERVE_MAX_LAGS, OBSERVE_TILE = 4, 1024, 256, 256
+
 # flags of tmdnet_set_pair_priors and the brute-force limit of the pass (TMDNET_PRIOR_* in the header)
 PRIOR_ZBL, PRIOR_D2, PRIOR_MAX_MOLECULE_ATOMS = 1, 2, 32768
 # limit and gate flags of the committee pass (TMDNET_COMMITTEE_* in the header)
@@ -222,6 +232,9 @@ def lib():
     L.tmdnet_md_bias_reset.argtypes = [vp, vp, u64, u64]
     L.tmdnet_md_bias.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32,
                                  f64, f64, f64, f64, f64, i64, i32, i64, vp, vp, vp, vp]
+    L.tmdnet_md_observe_workspace_bytes.argtypes = [i64, i64, C.POINTER(ObserveSpec), C.POINTER(sz)]
+    L.tmdnet_md_observe_start.argtypes = [vp, vp, i64, i64, C.POINTER(ObserveSpec), u64, vp]
+    L.tmdnet_md_observe.argtypes = [vp, vp, vp, vp, vp, i64, i64, C.POINTER(ObserveSpec), vp, vp, vp, vp, i32, vp, vp, vp, i64]
     L.tmdnet_md_constraints_workspace_bytes.argtypes = [i64, i64, i64, C.POINTER(sz)]
     L.tmdnet_md_advance_constrained.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, u64, vp, vp,
                                                 vp, vp, i64, i64, vp, vp, vp, vp, f64, i32]

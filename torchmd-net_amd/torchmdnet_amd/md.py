@@ -19,6 +19,9 @@ velocity rescaling or a Nose-Hoover chain - that scales all velocities of a mole
 half), and in anisotropic mode the box is kept lower triangular by rotating positions, velocities and forces with it.
 ``Ensemble.capture_md`` (``torchmdnet_amd.committee.DeviceCommitteeMD``) drives the loop with the mean force of a committee of models
 and gates it on the members' disagreement inside the graph (csrc/tn_committee.hip).
+``TorchMD_Net.capture_md_observed`` attaches an observer (``torchmdnet_amd.observe.Observer``, csrc/tn_observe.hip) to ``DeviceMD`` or
+``DeviceGlobalMD``: sample frames, g(r), MSD and the velocity autocorrelation recorded inside the graph at every S-th step, by launches
+that read ``pos`` / ``vel`` and write only their own workspace (``md.frames() / rdf() / msd() / vacf() / n_samples``).
 The capture sequence, the stale-graph guard, ``md(n)``, the status read-back and the skeleton of ``reset`` are those of every
 captured loop: ``torchmdnet_amd.captured``."""
 import ctypes as C
@@ -271,9 +274,12 @@ class DeviceMD(CapturedLoop):
 
     _capture_name, _noun = "capture_md", "the MD state"
 
+    _observer = None  # torchmdnet_amd.observe.Observer of a loop made by capture_md_observed
+
     def __init__(self, model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, thermostat, warmup,
-                 barostat=None, constraints=None):
+                 barostat=None, constraints=None, observer=None):
         super().__init__(model, steps_per_replay)
+        self._observer, self._keep_observables = observer, False
         L = _C.lib()
         dev = pos.device
         n = int(z.shape[0])
@@ -335,6 +341,8 @@ class DeviceMD(CapturedLoop):
         if self.constraints is not None:
             self._cons_ws.zero_()
             self._advance(MD_PROJECT, None, None, 0)
+        if self._observer is not None and not self._keep_observables:
+            self._observer.start(self, step)  # origins = these positions, s0 = step, everything else cleared
 
     def _stage_sigma(self, m64):
         """[N] fp32 thermal velocities sqrt(kT force_scale / m) the O step reads, from fp64, rounded once"""
@@ -345,11 +353,53 @@ class DeviceMD(CapturedLoop):
 
     def _capture_step(self, k, K, out):
         """The launches that follow evaluation k of a replay (inside the capture): close step k, open step k + 1"""
+        self._observe(k)
         if self.barostat is None:
             self._advance(MD_MIDDLE if k + 1 < K else MD_CLOSE, out[1], out[0], k)
         else:  # the kinetic energy of the closing half is reduced before the move: CLOSE, then scale (and open)
             self._advance(MD_CLOSE, out[1], out[0], k)
             self._barostat_move(k + 1 < K, out[1], out[2], k)
+
+    def _observe(self, k):
+        """The observer's launches after evaluation k, when there is an observer and replay position k is a sampling step; otherwise
+        nothing: pos is x at the full step, vel the leapfrog velocity the opening half stored"""
+        if self._observer is not None and (k + 1) % self._observer.spec["every"] == 0:
+            self._observer.launch(self)
+
+    def _observed(self):
+        if self._observer is None:
+            raise ValueError("this loop was captured without an observer: use capture_md_observed(..., observe=dict(...))")
+        return self._observer
+
+    @property
+    def n_samples(self) -> int:
+        """Samples the observer has recorded, from the device's step counter (one synchronisation) and not from ``steps_done``: a
+        loop frozen by an overflow reports what it recorded"""
+        return self._observed().n_samples(self)
+
+    def frames(self):
+        """-> (steps [n] int64 (host), pos [n,N,3] [, vel [n,N,3]]) clones of the n = min(capacity, n_samples) newest sampled frames,
+        oldest first, in the caller's atom order; ``vel`` is the leapfrog velocity v(s - 1/2)"""
+        return self._observed().frames(self)
+
+    def rdf(self):
+        """-> (r [bins] bin centres, g [B,P,bins] float64 (host), counts [B,P,bins] int64) of the pair-distance histogram over all
+        samples.  With a box g = counts / (n_samples n_pairs shell / V), shell = 4 pi / 3 (r_hi^3 - r_lo^3), n_pairs = N_a N_b or
+        N_a (N_a - 1) / 2 for a type whose two selectors are the same; WITHOUT a box there is no density to refer to and g is
+        counts / (n_samples n_pairs), the fraction of the type's pairs per bin."""
+        return self._observed().rdf(self)
+
+    def msd(self):
+        """-> (steps [n] int64 (host), msd [n,B,G] float64): the mean of |x_i(s) - x_i(s0)|^2 over each group's atoms per sample, from
+        the unwrapped positions; the origin is the configuration at capture or the last ``reset``"""
+        return self._observed().msd(self)
+
+    def vacf(self):
+        """-> (lag_times [L] float64 (host), C [B,G,L] float64): the autocorrelation <v(t) . v(t + lag)> of the LEAPFROG velocities
+        v(s - 1/2) the loop stores at a sampled step (after the opening kick and, with constraints, after SHAKE's correction),
+        averaged over each group's atoms and the n_samples - l origins of lag l; lags are multiples of every * dt; a lag with no
+        sample is NaN"""
+        return self._observed().vacf(self)
 
     @property
     def ndof(self) -> Tensor:
@@ -440,14 +490,27 @@ class DeviceMD(CapturedLoop):
             raise RuntimeError(f"tmdnet_md_status failed (code {rc})")
         return step
 
-    def reset(self, pos: Optional[Tensor] = None, vel: Optional[Tensor] = None, step: int = 0, box: Optional[Tensor] = None):
+    def reset(self, pos: Optional[Tensor] = None, vel: Optional[Tensor] = None, step: int = 0, box: Optional[Tensor] = None,
+              observables: str = "clear"):
         """New positions and / or velocities (copied into the static buffers), forces evaluated there, status cleared, device step
         counter and ``steps_done`` set to ``step`` (the Langevin noise is a function of (seed, step, atom)).  ``box`` is copied into
         the static box (a barostat has scaled it since the capture).  With constraints: new positions must satisfy them (ValueError
         naming the worst pair, before anything is changed), and the velocities are projected onto them again.  After a cluster
         did not converge (``check()`` named the constraints) the state is not a point of the trajectory, so both ``pos`` and ``vel``
-        are required: a reset without one of them raises RuntimeError and changes nothing."""
+        are required: a reset without one of them raises RuntimeError and changes nothing.  With an observer
+        (``capture_md_observed``): ``observables="clear"`` zeroes the histogram, the logs and the accumulators and takes these
+        positions as the new origins and ``step`` as the new s0; ``"keep"`` continues the sums and is refused (ValueError) unless
+        ``pos`` and ``vel`` are None and ``step`` is the loop's current step; a new ``box`` must keep r_max within half its height."""
         dev = self.pos.device
+        if observables not in ("clear", "keep"):
+            raise ValueError(f"reset(observables=...): 'clear' or 'keep', got {observables!r}")
+        if self._observer is not None:
+            from torchmdnet_amd.observe import refuse_keep
+
+            if observables == "keep":
+                refuse_keep(pos, vel, step, self._status(_C.lib().tmdnet_md_status, 2)[1][0])
+            if box is not None:
+                self._observer.check_box(box)
 
         def copy_in():
             if self.constraints is not None and (pos is None or vel is None):
@@ -469,7 +532,11 @@ class DeviceMD(CapturedLoop):
             self.forces.copy_(out[1])
             self._restart(int(step))
 
-        self._reset(copy_in, start, step)
+        self._keep_observables = observables == "keep"
+        try:
+            self._reset(copy_in, start, step)
+        finally:
+            self._keep_observables = False
         if self.constraints is not None:
             self.check()
         return self
@@ -1007,11 +1074,11 @@ class DeviceGlobalMD(DeviceMD):
     An atom of infinite mass is no degree of freedom and is not scaled."""
 
     def __init__(self, model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, warmup, thermostat,
-                 constraints=None):
+                 constraints=None, observer=None):
         self.global_thermostat = thermostat
         self._thermo_ready = False
         super().__init__(model, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, None, warmup, None,
-                         constraints)
+                         constraints, observer)
 
     def _stage_thermostat(self):
         th, dev, K, B = self.global_thermostat, self.pos.device, self.steps_per_replay, self.n_mol
@@ -1052,6 +1119,7 @@ class DeviceGlobalMD(DeviceMD):
     def _capture_step(self, k, K, out):
         # CLOSE (kick, kinetic energy, step counter), the thermostat, and the opening half of the next step: fused into the scaling
         # launch, or with constraints the velocity projection and the constrained OPEN launch on the forces the closing half kept
+        self._observe(k)
         self._advance(MD_CLOSE, out[1], out[0], k)
         more = k + 1 < K
         self._thermostat_move(more and self.constraints is None, out[1], k)

@@ -1682,6 +1682,49 @@ class TorchMD_Net(nn.Module):
         stage_ndof(th["ndof"], count_ndof(masses, batch, n_mol, constraints), n_mol)
         return DeviceGlobalMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, warmup, th, constraints)
 
+    def capture_md_observed(self, z: Tensor, pos: Tensor, vel: Tensor, masses: Tensor, dt: float, batch: Optional[Tensor] = None,
+                            box: Optional[Tensor] = None, q: Optional[Tensor] = None, num_systems: Optional[int] = None,
+                            steps_per_replay: int = 10, force_scale: float = 1.0, thermostat: Optional[dict] = None, warmup: int = 3,
+                            constraints: Optional[dict] = None, observe: Optional[dict] = None):
+        """``capture_md`` that records what happens between two replays: sample frames, the radial distribution function, the
+        mean-square displacement and the velocity autocorrelation, inside the graph (``tmdnet_md_observe``: at most three launches
+        after the evaluation of a SAMPLED step, none at any other step).  The observer reads ``pos`` / ``vel`` and writes only its own
+        workspace: the trajectory is bit for bit that of the loop without it.
+        ``thermostat``: None (NVE), the Langevin dict of ``capture_md``, or a dict with ``kind=`` ("csvr" / "nose-hoover"), which
+        selects the loop of ``capture_md_global``.  ``constraints``: the dict of ``capture_md_constrained``.
+        ``observe=dict(every=S, frames=, rdf=, msd=, vacf=)`` with at least one observable; ``S`` must divide ``steps_per_replay``.
+        Samples are the steps s0 + S, s0 + 2 S, ... after the step s0 of the capture or the last ``reset``.
+        ``frames=dict(capacity=F, velocities=False)``: a ring of the last F sampled frames -> ``md.frames()``;
+        ``rdf=dict(pairs=[(za, zb), ...], r_max=, bins=)``: 1 to 4 pair types (None: every species), bins <= 1024, per molecule a
+        histogram of pair distances over all samples (minimum image with a box; ``r_max`` at most half the smallest box height; the
+        batch must be sorted) -> ``md.rdf()``;
+        ``msd=dict(groups=[z | None, ...], capacity=T)``: sum |x(s) - x(s0)|^2 per sample, molecule and group from the unwrapped
+        positions, T rows -> ``md.msd()``;
+        ``vacf=dict(lags=L, groups=[...])``: L <= 256 lags of the autocorrelation of the leapfrog velocities v(s - 1/2) -> ``md.vacf()``.
+        Returns the loop object of the chosen integrator (``DeviceMD`` or ``DeviceGlobalMD``) with the observer attached:
+        ``md.n_samples`` and ``md.reset(..., observables="clear" | "keep")`` besides the four accessors.
+        Not offered, so not parameters of this method (follow-ups): a barostat, a bias, replica exchange, atom weights and the halo
+        exchange.  Everything ``capture_md`` refuses is refused, before anything is staged."""
+        from torchmdnet_amd.md import DeviceGlobalMD, DeviceMD, count_ndof, parse_global_thermostat, prepare_constraints, stage_ndof
+        from torchmdnet_amd.observe import Observer, parse_observe, prepare_observe
+
+        parse_observe(observe, steps_per_replay)  # everything below is refused before anything is allocated or captured
+        glob = thermostat is not None and "kind" in thermostat
+        th = parse_global_thermostat(thermostat) if glob else thermostat
+        z, batch, box, q, n_mol, dev = self._capture_inputs("capture_md_observed", "molecular dynamics needs", z, pos, batch, box, q,
+                                                            num_systems, steps_per_replay)
+        prep = prepare_observe(observe, z, batch, box, n_mol, steps_per_replay)
+        if constraints is not None:
+            constraints = prepare_constraints(constraints, pos, batch, masses, n_mol)
+        if glob:
+            stage_ndof(th["ndof"], count_ndof(masses, batch, n_mol, constraints), n_mol)
+        observer = Observer(prep, z.shape[0], n_mol, dt, dev)
+        if glob:
+            return DeviceGlobalMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, warmup, th,
+                                  constraints, observer)
+        return DeviceMD(self, z, pos, vel, masses, dt, batch, box, q, n_mol, steps_per_replay, force_scale, th, warmup, None,
+                        constraints, observer)
+
     def capture_md_cell(self, z: Tensor, pos: Tensor, vel: Tensor, masses: Tensor, dt: float, batch: Optional[Tensor] = None,
                         box: Optional[Tensor] = None, q: Optional[Tensor] = None, num_systems: Optional[int] = None,
                         steps_per_replay: int = 10, force_scale: float = 1.0, thermostat: Optional[dict] = None, warmup: int = 3,
