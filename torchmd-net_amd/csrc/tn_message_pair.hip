@@ -43,6 +43,9 @@ constexpr int MP_FC = 32;  // channels per block
 constexpr int MP_W = 64;   // source-window capacity (rows staged in LDS)
 constexpr int MP_E = 4096;  // adjacency entries of a tile kept in LDS (32 KB)
 constexpr int MP_U = 2;    // edges whose weights are loaded ahead of their use
+constexpr int MP_WAVES = 8;  // waves of a reverse sweep's block
+constexpr int MP_SLOT_PAIRS = MP_TA * (MP_TA - 1) / 2;  // pairs of a closed tile: 2016
+constexpr int MP_SLOTS = 2 * MP_SLOT_PAIRS;             // their slots (pair, direction) of one channel chunk, kept in LDS (16 KB)
 
 typedef float f4v __attribute__((ext_vector_type(4)));
 typedef float f2v __attribute__((ext_vector_type(2)));
@@ -98,6 +101,9 @@ struct TileLds {
   TN_LDS float* help;                    // helper partial sums of the long rows [MP_TA / 2][9][32]
   TN_LDS int *col, *pair;                // the tile's slice of col / epair [MP_E]
   TN_LDS int *rp, *len, *rank, *byrank;  // row table [MP_TA]: start within the slice, length, rank by length, row of a rank
+  // reverse sweeps only (see "Slots of a tile" below)
+  TN_LDS int* prange;                    // per wave of the block: smallest / largest pair id and count of the slice's non-self entries [3][MP_WAVES]
+  TN_LDS float* slot;                    // the tile's slots [MP_SLOTS]
 };
 struct Tile {
   TileLds lds;
@@ -127,8 +133,15 @@ __device__ __forceinline__ Tile tile_of_block(const Graph& g, int N, int nchunks
 // load in front of every eight trips' weight loads.  Rows r0 .. r1 are one contiguous range of col / epair (~1500 entries
 // for 64-atom molecules); it is requested together with the row table (and, with WINDOW, the column bounds of the thread's row:
 // rows are sorted ascending, first / last entry) and read from LDS afterwards.  in_lds: the slice fits (block-uniform).
+//
+// Slots of a tile.  The engine numbers the pairs of rows r0 .. r1 of a closed tile contiguously, and both directions of each lie
+// in the tile: it owns the slots [2 pmin, 2 pmax + 2) of its channel chunk and nothing else touches them.  While the slice is on
+// its way every wave reduces the smallest and largest pair id and the count of the non-self entries (pair id != self_pair =
+// counts[0]) it staged; the barrier that publishes the slice publishes them (slot_range reads them).  A slice left in global
+// memory counts nothing.
 template <int THREADS, bool WINDOW>
-__device__ __forceinline__ void stage_slice(const Graph& g, const Tile& T, bool in_lds, int tid, int& lo, int& hi) {
+__device__ __forceinline__ void stage_slice(const Graph& g, const Tile& T, bool in_lds, int tid, int& lo, int& hi, int self_pair) {
+  static_assert(THREADS == 64 * MP_WAVES, "one entry of prange per wave");
   int cbuf[MP_E / THREADS], pbuf[MP_E / THREADS];
   if (in_lds) {
 #pragma unroll
@@ -150,6 +163,7 @@ __device__ __forceinline__ void stage_slice(const Graph& g, const Tile& T, bool 
       hi = g.col[a1 - 1];
     }
   }
+  int pmin = 0x7fffffff, pmax = -1, pcnt = 0;
   if (in_lds) {
 #pragma unroll
     for (int k = 0; k < MP_E / THREADS; ++k) {
@@ -157,9 +171,43 @@ __device__ __forceinline__ void stage_slice(const Graph& g, const Tile& T, bool 
       if (idx < T.nE) {
         T.lds.col[idx] = cbuf[k];
         T.lds.pair[idx] = pbuf[k];
+        if (pbuf[k] != self_pair) {
+          pmin = min(pmin, pbuf[k]);
+          pmax = max(pmax, pbuf[k]);
+          ++pcnt;
+        }
       }
     }
   }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    pmin = min(pmin, __shfl_xor(pmin, off, 64));
+    pmax = max(pmax, __shfl_xor(pmax, off, 64));
+    pcnt += __shfl_xor(pcnt, off, 64);
+  }
+  if ((tid & 63) == 0) {
+    T.lds.prange[tid >> 6] = pmin;
+    T.lds.prange[MP_WAVES + (tid >> 6)] = pmax;
+    T.lds.prange[2 * MP_WAVES + (tid >> 6)] = pcnt;
+  }
+}
+
+// The tile's slot range from what stage_slice left (after the barrier behind it; block-uniform): the first pair id and the
+// number of slots when the tile takes its slots through LDS, 0 slots when it stores them directly.  Through LDS when the pair
+// ids of the slice's non-self entries span at most MP_SLOT_PAIRS ids and there are exactly two entries per id of the span: an
+// entry is one (pair, direction) and no two entries are the same one, so every slot of the span is then written exactly once by
+// this tile and nothing uninitialised leaves LDS.
+__device__ __forceinline__ int slot_range(const TileLds& s, int& pmin) {
+  int lo = s.prange[0], hi = s.prange[MP_WAVES], cnt = s.prange[2 * MP_WAVES];
+#pragma unroll
+  for (int k = 1; k < MP_WAVES; ++k) {
+    lo = min(lo, s.prange[k]);
+    hi = max(hi, s.prange[MP_WAVES + k]);
+    cnt += s.prange[2 * MP_WAVES + k];
+  }
+  pmin = lo;
+  const int span = hi - lo + 1;
+  return (cnt > 0 && span <= MP_SLOT_PAIRS && cnt == 2 * span) ? 2 * span : 0;
 }
 
 // column window of the tile: min / max of the rows' bounds over the block (one barrier; it also publishes slice and row table)
@@ -564,12 +612,14 @@ __global__ __launch_bounds__(64 * LPR) void k_message_rows8(Graph g, int N, int 
 // the ranks in LDS.  FOLD: the tile is closed - the window is the tile's own aligned 64 rows and always staged, the slice always in
 // LDS, and gPn already holds gY, which the epilogue's read-modify-write adds to (summation order gY + acc).  Otherwise csr_lds /
 // staged are the block-uniform choices of the prologue, lo the window's first row and gMi the source of an unstaged window.
-// 240 VGPRs in the edge loop: nothing may be added to it.
+// nslot / slot_p0: the tile's slot range (slot_range), read by the kernel where no store is in flight.
+// 252 (FOLD) and 248 VGPRs: nothing may be added to the edge loop.
 template <bool FOLD>
 __device__ __forceinline__ void adjoint_tile_body(const Tile& T, int N, int F, const float* __restrict__ w,
                                                   const float* __restrict__ dw, const float* __restrict__ gMi,
                                                   const float* __restrict__ Pn, float* __restrict__ gPn, float* __restrict__ slots,
-                                                  int64_t slot_stride, bool csr_lds_of_tile, bool staged_of_tile, int lo) {
+                                                  int64_t slot_stride, bool csr_lds_of_tile, bool staged_of_tile, int lo, int nslot,
+                                                  int slot_p0) {
   constexpr int LPR = 8, VW = 4, U = MP_U;
   constexpr SliceSrc SRC = FOLD ? SLICE_LDS_GUARDED : SLICE_LDS_OR_GLOBAL;
   typedef f4v vf;
@@ -581,6 +631,10 @@ __device__ __forceinline__ void adjoint_tile_body(const Tile& T, int N, int F, c
 #pragma unroll
   for (int c = 0; c < 9; ++c) acc[c] = (vf)(0.f);
   float* const slot_base = slots + (int64_t)T.chunk * slot_stride;
+  // A store of the edge loop shares its counter with the loads: the wait for the next weights also waited for the slot store in
+  // front of them to be acknowledged.  A tile that owns a contiguous slot range (slot_range) keeps its slots in LDS instead and
+  // writes the range out once, coalesced, behind the walk.
+  // (nslot, slot_p0: slot_range of the tile; nslot = 0: direct stores)
 
   // a slice read from global memory is walked by every row's own group only (no helpers)
   const TileWalk wk = walk_of_row<SRC, LPR>(T, csr_lds, csr_lds, rl, ql, T.r0);
@@ -627,21 +681,33 @@ __device__ __forceinline__ void adjoint_tile_body(const Tile& T, int N, int F, c
                     dv[u][2] * (s9[4] * y[4] + mul_rounded(s9[5], y[5]) + s9[6] * y[6] + s9[7] * y[7] + s9[8] * y[8]);
       const float h = row_sum((hv[0] + hv[1]) + (hv[2] + hv[3]), LPR);
       // slot (pair, direction): direction 0 when the walked row is the pair's i (its neighbour has the smaller index); self edge: none
-      if (ql == 0 && t + u < wk.ntrip && jj[u] != row_now) slot_base[2 * pp[u] + (jj[u] < row_now ? 0 : 1)] = h;
+      if (ql == 0 && t + u < wk.ntrip && jj[u] != row_now) {
+        const int sl = 2 * pp[u] + (jj[u] < row_now ? 0 : 1);
+        if (nslot) T.lds.slot[sl - 2 * slot_p0] = h;
+        else slot_base[sl] = h;
+      }
     }
   }
   if (!parked) {  // a helper whose own row is empty
     walk_park(acc, wk, T.lds, VW * ql);
     load_y(i);
   }
-  __syncthreads();  // the parked sums are complete
-  if (!live) return;
-  walk_add_parked(acc, wk, T.lds, VW * ql);
-  float* o = gPn + (int64_t)i * F9 + f;
+  __syncthreads();  // the parked sums and the tile's slots are complete
+  // The row's nine pieces of gPn are requested together: as *op = *op + acc[c], piece by piece, every load waited for the store
+  // of the piece before (the compiler cannot know that they do not overlap) - nine load and store round trips in a row at the
+  // end of every block.  Same sum, old + acc.  The slot write-out comes last: nothing waits for its stores.
+  if (live) {
+    float* o = gPn + (int64_t)i * F9 + f;
+    vf old[9];
+    load9(old, (const float*)o, F);
+    walk_add_parked(acc, wk, T.lds, VW * ql);
 #pragma unroll
-  for (int c = 0; c < 9; ++c) {
-    vf* op = reinterpret_cast<vf*>(o + c * F);
-    *op = *op + acc[c];
+    for (int c = 0; c < 9; ++c) *reinterpret_cast<vf*>(o + c * F) = old[c] + acc[c];
+  }
+#pragma unroll
+  for (int it = 0; it < (MP_SLOTS + 64 * MP_WAVES - 1) / (64 * MP_WAVES); ++it) {  // (the range is 8-byte aligned at best: dwords)
+    const int k = tid + it * 64 * MP_WAVES;
+    if (k < nslot) slot_base[2 * slot_p0 + k] = T.lds.slot[k];
   }
 }
 
@@ -660,20 +726,24 @@ __global__ __launch_bounds__(512) void k_message_adjoint_rows8(Graph g, int N, i
   __shared__ __attribute__((aligned(16))) float s_help[(MP_TA / 2) * 9 * MP_FC];
   __shared__ int s_col[MP_E], s_pair[MP_E];
   __shared__ int s_lo[THREADS / 64], s_hi[THREADS / 64], s_rp[MP_TA], s_len[MP_TA], s_rank[MP_TA], s_byrank[MP_TA];
+  __shared__ int s_prange[3 * MP_WAVES];
+  __shared__ float s_slot[MP_SLOTS];
   if (g.counts[2]) return;
   const Tile T = tile_of_block(g, N, nchunks, {lds_ptr(win), lds_ptr(s_help), lds_ptr(s_col), lds_ptr(s_pair), lds_ptr(s_rp),
-                                               lds_ptr(s_len), lds_ptr(s_rank), lds_ptr(s_byrank)});
+                                               lds_ptr(s_len), lds_ptr(s_rank), lds_ptr(s_byrank), lds_ptr(s_prange), lds_ptr(s_slot)});
   const int tid = threadIdx.x;
 
   const bool csr_lds = T.nE <= MP_E;  // block-uniform
   int lo = 0x7fffffff, hi = -1;
-  stage_slice<THREADS, true>(g, T, csr_lds, tid, lo, hi);
+  stage_slice<THREADS, true>(g, T, csr_lds, tid, lo, hi, g.counts[0]);
   window_bounds<THREADS>(lo, hi, lds_ptr(s_lo), lds_ptr(s_hi), tid);
   const int wn = hi - lo + 1;
   const bool staged = hi >= lo && wn <= MP_W;  // block-uniform
   stage_window<THREADS, MP_FC>(gMi, F, T, lo, staged ? wn : 0, tid);
 
-  adjoint_tile_body<false>(T, N, F, w, dw, gMi, Pn, gPn, slots, slot_stride, csr_lds, staged, lo);
+  int slot_p0;
+  const int nslot = slot_range(T.lds, slot_p0);
+  adjoint_tile_body<false>(T, N, F, w, dw, gMi, Pn, gPn, slots, slot_stride, csr_lds, staged, lo, nslot, slot_p0);
 }
 
 // The reverse sweep with the adjoint of the group product (k_message_bwd_node, tn_kernels.hip) folded into its prologue, for CLOSED
@@ -696,21 +766,27 @@ __global__ __launch_bounds__(512) void k_message_adjoint_rows8_fold(Graph g, int
   __shared__ __attribute__((aligned(16))) float s_help[(MP_TA / 2) * 9 * MP_FC];
   __shared__ int s_col[MP_E], s_pair[MP_E];
   __shared__ int s_rp[MP_TA], s_len[MP_TA], s_rank[MP_TA], s_byrank[MP_TA];
+  __shared__ int s_prange[3 * MP_WAVES];
+  __shared__ float s_slot[MP_SLOTS];
   if (g.counts[2]) return;
   const Tile T = tile_of_block(g, N, nchunks, {lds_ptr(win), lds_ptr(s_help), lds_ptr(s_col), lds_ptr(s_pair), lds_ptr(s_rp),
-                                               lds_ptr(s_len), lds_ptr(s_rank), lds_ptr(s_byrank)});
+                                               lds_ptr(s_len), lds_ptr(s_rank), lds_ptr(s_byrank), lds_ptr(s_prange), lds_ptr(s_slot)});
   const int tid = threadIdx.x, F9 = 9 * F;
 
   if (T.nE > MP_E) return;  // not a closed tile (at most 64 x 64 entries): never launched on one; keeps the LDS slice in bounds
   int no_lo, no_hi;  // the window is the tile: WINDOW = false leaves them untouched
-  stage_slice<THREADS, false>(g, T, true, tid, no_lo, no_hi);
+  stage_slice<THREADS, false>(g, T, true, tid, no_lo, no_hi, g.counts[0]);
   __syncthreads();
+  // read here, with no store in flight: behind the prologue's gY stores the compiler waits for them in front of these LDS reads
+  int slot_p0;
+  const int nslot = slot_range(T.lds, slot_p0);
 
   const int rl = tid / LPR, i = T.r0 + rl, ql = tid & (LPR - 1), f = T.c0 + VW * ql;
   const bool live = i < T.r1;
   {
     // ---- prologue: the row's pieces of gCh, Pn and Mi are requested together; the rank of the rows is computed while they
-    // are on their way
+    // are on their way.  (Requested in front of the slice, so that slice and pieces share one round trip, the kernel was slower:
+    // 271.0 against 266.7 us per launch, profiles/pair_loop_stores_notes.md.)
     const int64_t base = (int64_t)min(i, N - 1) * F9 + f;
     f4v gc4[9], y4[9], m4[9];
     if (live) {
@@ -749,7 +825,7 @@ __global__ __launch_bounds__(512) void k_message_adjoint_rows8_fold(Graph g, int
     __syncthreads();
   }
 
-  adjoint_tile_body<true>(T, N, F, w, dw, nullptr, Pn, gPn, slots, slot_stride, true, true, T.r0);
+  adjoint_tile_body<true>(T, N, F, w, dw, nullptr, Pn, gPn, slots, slot_stride, true, true, T.r0, nslot, slot_p0);
 }
 
 bool message_adjoint_pair_ok(const Graph& g, int N, int F) {
