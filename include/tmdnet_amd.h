@@ -626,6 +626,123 @@ typedef struct tmdnet_tn2_unit_args {
   float* fpos;
 } tmdnet_tn2_unit_args;
 int tmdnet_debug_tn2(void* stream, const tmdnet_tn2_unit_args* args);
+/* One kernel of the Equivariant Transformer's edge sweeps (csrc/tn_et.hip, csrc/tn_et_g16.hip) on caller-built operands
+ * (additive: the ABI revision stays).  No model handle; for unit tests.  The graph is in the engine's form (tmdnet_debug_message)
+ * and is NOT validated; beyond the CSR it has pair_i / pair_j [P] (pair_i > pair_j), prhat [P, 3] = the unit vector of
+ * pos[pair_i] - pos[pair_j], and `batch` [N] (sorted; NULL: one molecule).  counts[0] = P, counts[1] = E = rowptr[N].
+ * Layouts: qkv [N, 5 F] = q | k | vx | v1 | v2; vec, vagg, g_vagg, g_vec [N, 3, F]; xagg, g_xagg [N, F]; C, dC [P + 1]; dkv, tkv
+ * [P + 1, Wd] with the key projection's F columns at dk_off and the value projection's 3 F at dv_off (-1: the model has no such
+ * projection, the factor is 1 and its tangent 0; both -1: dkv and tkv may be NULL), fp32, or bf16 when pair_bf16 = 1.  Channel c
+ * belongs to head c / hd.  With e = (i <- j) an entry of row i, p = epair[e], rhat = -esign[e] prhat[p] (0 on the self edge),
+ * cv = C[p], ca = 1 (vector_cutoff != 0) or cv = 1, ca = C[p]:
+ *   a[e, h] = sum_{c in h} q[i, c] k[j, c] dk[p, c];  A = silu(a) ca;  sx = vx[j] cv dvx[p], s1 = v1[j] cv dv1[p], s2 = v2[j] cv dv2[p]
+ *   TMDNET_ET_OP_ATTN_FWD      xagg[i] = sum_e sx A;  vagg[i, x] = sum_e vec[j, x] s1 + s2 rhat_x
+ *   TMDNET_ET_OP_ATTN_BWD      the adjoint for given g_xagg, g_vagg: g_qkv [N, 5 F] written, g_vec [N, 3, F] +=, and per slot
+ *                              array w the partial sums over its channels of d / d d(p) and d / d rhat of the edge (i <- j), at
+ *                              gd2[w slot_stride + 2 p + dir], gr2[(w slot_stride + 2 p + dir) 3 + x], dir = 0 where esign > 0,
+ *                              1 where esign < 0; self edges write no slot.  The caller always sums F / 32 arrays when F % 32 ==
+ *                              0 (ceil(F / 64) otherwise): the tile kernels write one per 32 channels, the row kernels one per
+ *                              64 and zero the rest.  slot_stride >= 2 (P + 1).
+ *   TMDNET_ET_OP_TILE_PREP     meta[0] = 0 when the greedy packing of whole molecules into tiles of at most 64 rows is closed
+ *                              and E >= min_fill x tiles x 4096 (else 1), meta[1] = tiles, tile_start [tiles + 1] (array of N + 8),
+ *                              erec [E, 8] = col | pair | esign | C | dC | prhat (zeros on the self edge)
+ *   TMDNET_ET_OP_PAIR_COMBINE  gd[p] = gd_extra[2 p] + sum_w gd2[w][2 p] + gd2[w][2 p + 1];  g_rhat[p] = sum_w -gr2[w][2 p] +
+ *                              gr2[w][2 p + 1]  over nw slot arrays, p < counts[0]
+ *   TMDNET_ET_OP_NBR_EMBED     xcat [N, 2 F] = emb[z_i] | sum_{j != i} Wn[p] embN[z_j]
+ *   TMDNET_ET_OP_NBR_EMBED_BWD gd2[2 p] += sum_c (g_xcat[i, F + c] embN[z_j, c] + g_xcat[j, F + c] embN[z_i, c]) dWn[p, c]
+ *   TMDNET_ET_OP_TRAIN_NBR     slots[dir dir_stride + p F + c] = g_xcat[i, F + c] embN[z_j, c];  gEN[i] = sum_{j != i} g_xcat[j, F +
+ *                              c] Wn[p, c]
+ *   TMDNET_ET_OP_TRAIN_FILTER  the adjoint of the filter rows dkv per directed edge: slots[dir dir_stride + p Wd + ..] (self
+ *                              edges: self_rows [N, Wd]);  g_dk = g_a q_i k_j, g_dvx = cv g_sx vx_j, g_dv1 = cv g_s1 v1_j,
+ *                              g_dv2 = cv g_s2 v2_j.  fp32 rows only.
+ *   TMDNET_ET_OP_TRAIN_GPRE    g_pre[p] = (slots[p] + slots[dir_stride + p]) silu'(pre[p]), row P from self_sum [Wd]
+ *   TMDNET_ET_OP_QUERY         no launch, nothing dereferenced: *route_out = 1 when the tile kernels' size conditions hold for
+ *                              (N, P, F, hd, Wd) - 32-bit offsets, and every pair id up to P in the slot table's 24 bits - else 0
+ * kernel (the two attention ops): TMDNET_ET_AUTO runs the tile prep and then the engine's own launcher (both generations
+ * enqueued, the flag meta[0] on the device picks); TMDNET_ET_ROW_GENERIC k_et_attn_fwd / k_et_attn_bwd; TMDNET_ET_ROW_PIPELINED
+ * k_et_attn_fwd_p / k_et_attn_bwd_p (F % 64 == 0, hd <= 16); TMDNET_ET_TILE the prep, then k_et_attn_fwd_g16 / k_et_attn_bwd_g16 alone
+ * (TMDNET_ET_OP_QUERY's conditions; it writes nothing when meta[0] != 0).  skip_prep != 0 (AUTO, TILE): meta, tile_start and
+ * erec are used as the caller left them.  slot_min, mailbox, sync_every (TILE) and min_fill (TILE_PREP, and the prep of AUTO and
+ * TILE) override the developer switches of the tile sweeps; a negative value is the shipped default (slot order from a longest
+ * row of 48, mailbox on, 4, 0.70 for fp32 and 0.25 for bf16 rows).  *route_out (may be NULL except for QUERY) receives the
+ * generation that wrote the outputs: for AUTO and TILE the call synchronises the stream and reads meta[0] back (TILE with
+ * meta[0] != 0: 0, nothing written).
+ * TMDNET_ERR_INVALID, and no launch: an unknown op or selector, N < 1, P < 0, B < 1 or E < 0 (ops that run the prep), F < 1, hd
+ * no power of two <= 64 or no divisor of F, F > 1024, an offset other than dk_off in {-1, 0}, dv_off in {-1, dk_off + F or 0},
+ * Wd smaller than the projections need (odd with bf16 rows), a row kernel outside its F / hd contract, the tile kernel outside
+ * QUERY's conditions or with an operand not 16-byte aligned, TRAIN_FILTER with pair_bf16 or without a projection, slot_stride <
+ * 2 (P + 1), nw < 1, a NULL graph array or operand the op reads or writes. */
+#define TMDNET_ET_OP_QUERY 0
+#define TMDNET_ET_OP_TILE_PREP 1
+#define TMDNET_ET_OP_ATTN_FWD 2
+#define TMDNET_ET_OP_ATTN_BWD 3
+#define TMDNET_ET_OP_PAIR_COMBINE 4
+#define TMDNET_ET_OP_NBR_EMBED 5
+#define TMDNET_ET_OP_NBR_EMBED_BWD 6
+#define TMDNET_ET_OP_TRAIN_NBR 7
+#define TMDNET_ET_OP_TRAIN_FILTER 8
+#define TMDNET_ET_OP_TRAIN_GPRE 9
+#define TMDNET_ET_AUTO 0
+#define TMDNET_ET_ROW_GENERIC 1
+#define TMDNET_ET_ROW_PIPELINED 2
+#define TMDNET_ET_TILE 3
+typedef struct tmdnet_et_unit_args {
+  int32_t op, kernel;
+  int32_t N, B, P, E, F, hd, Wd, dk_off, dv_off, vector_cutoff, pair_bf16;
+  int32_t skip_prep, slot_min, mailbox, sync_every, nw;
+  float min_fill;
+  int64_t slot_stride, dir_stride;
+  /* graph */
+  const int32_t* rowptr; /* [N + 1] */
+  const int32_t* col;
+  const int32_t* epair;
+  const float* esign;
+  const int32_t* counts; /* [8] */
+  const int32_t* pair_i; /* [P] */
+  const int32_t* pair_j;
+  const float* prhat;    /* [P, 3] */
+  const int64_t* batch;  /* [N], optional */
+  /* operands of the attention sweeps */
+  const float* C;
+  const float* dC;
+  const float* qkv;
+  const float* vec;
+  const void* dkv;
+  const void* tkv;
+  const float* g_xagg;
+  const float* g_vagg;
+  /* tile prep (written by TILE_PREP, AUTO and TILE unless skip_prep) */
+  int32_t* meta;       /* [2] */
+  int32_t* tile_start; /* [N + 8] */
+  float* erec;         /* [E, 8] */
+  /* outputs of the attention sweeps; gd2 / gr2 are inputs of PAIR_COMBINE, gd2 is the += output of NBR_EMBED_BWD */
+  float* xagg;
+  float* vagg;
+  float* g_qkv;
+  float* g_vec;
+  float* gd2;
+  float* gr2;
+  /* PAIR_COMBINE */
+  const float* gd_extra; /* [2 (P + 1)] */
+  float* gd;             /* [P] */
+  float* g_rhat;         /* [P, 3] */
+  /* neighbour embedding and its adjoints */
+  const int64_t* z;   /* [N] */
+  const float* emb;   /* [max_z, F] */
+  const float* embN;  /* [max_z, F] */
+  const float* Wn;    /* [P + 1, F] */
+  const float* dWn;   /* [P + 1, F] */
+  const float* g_xcat; /* [N, 2 F] */
+  float* xcat;        /* [N, 2 F] */
+  float* gEN;         /* [N, F] */
+  /* parameter-gradient sweeps: slots [2][dir_stride] (written by TRAIN_NBR / TRAIN_FILTER, read by TRAIN_GPRE) */
+  float* slots;
+  float* self_rows;      /* [N, Wd] */
+  const float* self_sum; /* [Wd] */
+  const float* pre;      /* [P + 1, Wd] */
+  float* g_pre;          /* [P + 1, Wd] */
+} tmdnet_et_unit_args;
+int tmdnet_debug_et(void* stream, const tmdnet_et_unit_args* args, int32_t* route_out);
 
 /* ---- First-order parameter gradients (TensorNet, TensorNet2 and Equivariant Transformer handles; energy-only training).
  * Replaces what autograd does in the reference for `loss(E).backward()` over torchmdnet/models/tensornet.py:543-619, 729-814,

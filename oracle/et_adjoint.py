@@ -137,6 +137,9 @@ def energy_forces(sd, hp, z, pos, batch, box=None, atomref=None, want_cache=Fals
         x = x + dx
         vec = vec + dvec
         cache[f"x_layer{l}"], cache[f"vec_layer{l}"] = x, vec
+        # operands and sums of the layer's edge sweep (tests/test_et_unit_oracle.py restates the sweep in the kernels' layouts)
+        cache[f"attn_layer{l}"] = dict(src=src, tgt=tgt, rhat=rhat, C=C, q=q, k=k, vx=vx, v1=v1, v2=v2, vec=saved[-1]["vec"],
+                                       dk=dk if has_dk else None, dv=(dvx, dv1, dv2) if has_dv else None, xagg=xagg, vagg=vagg)
     xf, xfh, rstdf = layer_norm(x, W(R + "out_norm"), B(R + "out_norm"))
     cache["x_out"] = xf
 

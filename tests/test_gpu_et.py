@@ -1,6 +1,7 @@
 """gpu: Equivariant Transformer energy+force path (BASELINE configs[3]) through the C ABI
 (tmdnet_create_et + the shared entry points) against the reference's golden vector, fixtures produced by the
-unmodified reference, and the oracle (oracle/et_torch.py, oracle/et_adjoint.py).  Tolerance: 1e-4 relative (fp32)."""
+unmodified reference, and the oracle (oracle/et_torch.py, oracle/et_adjoint.py).  Tolerance: 1e-4 relative (fp32).
+The attention sweeps kernel by kernel, every output and slot array against float64: tests/test_gpu_et_unit.py."""
 import json
 import os
 

@@ -19,6 +19,7 @@ def test_library_loads_and_exports_every_declared_symbol(hip_lib):
     assert "tmdnet_debug_message" in syms  # the sweeps' unit-test entry (tests/test_gpu_message.py)
     assert "tmdnet_debug_graph" in syms  # the graph's read-back entry (tests/test_gpu_graph.py)
     assert "tmdnet_debug_tn2" in syms  # the TensorNet2 kernels' unit-test entry (tests/test_gpu_tn2_unit.py)
+    assert "tmdnet_debug_et" in syms  # the ET edge sweeps' unit-test entry (tests/test_gpu_et_unit.py)
     assert hip_lib.tmdnet_version().decode().startswith("tmdnet_amd")
     # parameter table of the C side == state-dict keys of the Python side
     model = create_model(dict(W.TINY_ARGS))
@@ -501,3 +502,37 @@ def test_force_matching_backward_combines_the_passes_with_the_right_signs(monkey
         assert calls == dict(first=1 + extra, second=0, hv=0) and torch.allclose(g_pos, -ge[batch].unsqueeze(1) * F0)
         # the stand-in's first-order gradient does not depend on pos: every difference quotient of it is zero
         assert all(torch.allclose(p.grad, torch.full_like(p, float(ge.sum())), rtol=1e-5, atol=1e-5) for p in params)
+
+
+def test_et_tile_kernels_bound_the_pair_id_to_the_slot_tables_24_bits(hip_lib):
+    """The tile sweeps' slot table packs the pair id - the self pair's id P included - into 24 bits.  tmdnet_debug_et's query mode
+    returns et_g16_ok's size predicate without a launch and without reading a pointer: true up to P = 2^24 - 1, false from 2^24
+    on, also for a model without distance projections (Wd = 0), where the 32-bit offset conditions bound nothing."""
+    from torchmdnet_amd import _C
+
+    def ok(N, P, F, hd, Wd):
+        x = _C.EtUnitArgs()
+        x.op, x.N, x.P, x.F, x.hd, x.Wd = _C.ET_OP_QUERY, N, P, F, hd, Wd
+        r = C.c_int32(-7)
+        assert hip_lib.tmdnet_debug_et(None, C.byref(x), C.byref(r)) == _C.OK
+        return r.value
+
+    for Wd in (0, 4):  # (Wd = 4: P1 Wd 4 < 2^31 still holds at 2^24 pairs, so the new condition is the one that decides)
+        assert ok(64, 2 ** 24 - 1, 64, 16, Wd) == 1
+        assert ok(64, 2 ** 24, 64, 16, Wd) == 0
+        assert ok(64, 2 ** 24 + 1, 64, 16, Wd) == 0
+    # the conditions that were there before, each on its edge
+    assert ok(64, 100, 64, 16, 256) == 1 and ok(64, 100, 48, 16, 192) == 0 and ok(64, 100, 64, 64, 256) == 0 and ok(64, 100, 64, 1, 256) == 0
+    assert ok(64, 2 ** 21 - 1, 64, 16, 256) == 0 and ok(64, 2 ** 21 - 2, 64, 16, 256) == 1  # P1 Wd 4 < 2^31
+    assert ok(2 ** 31 // (5 * 64 * 4) + 1, 100, 64, 16, 0) == 0 and ok(2 ** 31 // (5 * 64 * 4), 100, 64, 16, 0) == 1  # N 5 F 4 < 2^31
+    # the query needs an out-parameter and sane sizes; nothing else
+    x = _C.EtUnitArgs()
+    x.op, x.N, x.P, x.F, x.hd, x.Wd = _C.ET_OP_QUERY, 64, 10, 64, 16, 0
+    assert hip_lib.tmdnet_debug_et(None, C.byref(x), None) == _C.ERR_INVALID
+    assert hip_lib.tmdnet_debug_et(None, None, None) == _C.ERR_INVALID
+    for field, bad in (("N", 0), ("P", -1), ("F", 0), ("hd", 0), ("Wd", -1)):
+        x = _C.EtUnitArgs()
+        x.op, x.N, x.P, x.F, x.hd, x.Wd = _C.ET_OP_QUERY, 64, 10, 64, 16, 0
+        setattr(x, field, bad)
+        r = C.c_int32(-7)
+        assert hip_lib.tmdnet_debug_et(None, C.byref(x), C.byref(r)) == _C.ERR_INVALID and r.value == -7

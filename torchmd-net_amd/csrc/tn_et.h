@@ -59,15 +59,29 @@ void launch_et_train_gpre(const Graph& g, int P, int Wd, const float* slots, int
                           float* g_pre, hipStream_t s);
 void launch_et_train_nbr(const Graph& g, int N, int F, const int64_t* z, const float* embN, const float* Wn, const float* g_xcat,
                          float* slots, int64_t dir_stride, float* gEN, hipStream_t s);
-// third generation of the two attention sweeps (tn_et_g16.hip); et_g16_ok: the layout and the 32-bit offsets apply (P1 = pair rows)
+// the row sweeps alone, as launch_et_attn_fwd / launch_et_attn_bwd enqueue them behind the tile sweeps: the pipelined kernels
+// (contract et_pipelined_contract: F % 64 == 0, F <= 1024, hd <= 16) or the generic ones.  et_pipelined_ok: the launchers' choice
+bool et_pipelined_contract(const EtAttnArgs& a);
+bool et_pipelined_ok(const EtAttnArgs& a);
+void launch_et_attn_fwd_rows(const Graph& g, int N, const EtAttnArgs& a, bool pipelined, float* xagg, float* vagg, hipStream_t s);
+void launch_et_attn_bwd_rows(const Graph& g, int N, const EtAttnArgs& a, bool pipelined, const float* g_xagg, const float* g_vagg,
+                             float* g_qkv, float* g_vec, float* gd2, float* gr2, hipStream_t s);
+// third generation of the two attention sweeps (tn_et_g16.hip); et_g16_ok: the layout and the 32-bit offsets apply (P1 = pair rows);
+// et_g16_shape_ok: its conditions on the sizes alone (no pointers, no developer switch)
+bool et_g16_shape_ok(int64_t N, int64_t P1, int F, int hd, int64_t Wd);
 bool et_g16_ok(int N, int64_t P1, const EtAttnArgs& a);
-// once per step before the first sweep: the closed-tiles flag and the per-edge records (ecap = rows of erec)
+// once per step before the first sweep: the closed-tiles flag and the per-edge records (ecap = rows of erec); min_fill < 0: the
+// shipped fill threshold of the storage mode
 void launch_et_tile_prep(const Graph& g, int N, int B, const int64_t* batch, const float* C, const float* dC, int64_t ecap, int pair_bf16,
-                         int* meta, int* tile_start, float* erec, hipStream_t s);
+                         int* meta, int* tile_start, float* erec, hipStream_t s, float min_fill = -1.f);
 int et_g16_max_tiles(int N, int B);
-void launch_et_attn_fwd_g16(const Graph& g, int N, const EtAttnArgs& a, float* xagg, float* vagg, hipStream_t s);
+struct EtG16Opts {  // overrides of the tile sweeps' developer switches (unit tests); a negative value: the shipped default
+  int slot_min = -1, mailbox = -1, sync_every = -1;
+};
+void launch_et_attn_fwd_g16(const Graph& g, int N, const EtAttnArgs& a, float* xagg, float* vagg, hipStream_t s,
+                            const EtG16Opts* opts = nullptr);
 void launch_et_attn_bwd_g16(const Graph& g, int N, const EtAttnArgs& a, const float* g_xagg, const float* g_vagg, float* g_qkv,
-                            float* g_vec, float* gd2, float* gr2, hipStream_t s);
+                            float* g_vec, float* gd2, float* gr2, hipStream_t s, const EtG16Opts* opts = nullptr);
 int et_sweep_waves(int F);  // waves per block of the attention sweeps = partial-sum slots per pair direction
 void launch_et_cat_norm(const float* xsrc, int Fx, const float* u, int ldu, int Fn, int N, float* hcat, hipStream_t s);
 void launch_et_norm_bwd(const float* g_n, int ldg, const float* u, int ldu, int Fn, int N, float* g_u, int ldgu, hipStream_t s);

@@ -269,9 +269,10 @@ __global__ void k_et_attn_fwd_p(Graph g, EtAttnArgs a, float* __restrict__ xagg,
   o[F] = va1;
   o[2 * F] = va2;
 }
-static bool et_pipelined_ok(const EtAttnArgs& a) {
+bool et_pipelined_contract(const EtAttnArgs& a) { return a.F % 64 == 0 && a.F <= 1024 && a.hd <= 16; }
+bool et_pipelined_ok(const EtAttnArgs& a) {
   static const bool off = getenv("TMDNET_ET_GENERIC_SWEEPS") != nullptr;  // developer switch: the generic kernels
-  return !off && a.F % 64 == 0 && a.F <= 1024 && a.hd <= 16;
+  return !off && et_pipelined_contract(a);
 }
 void launch_et_attn_fwd(const Graph& g, int N, const EtAttnArgs& a_in, float* xagg, float* vagg, hipStream_t s) {
   if (N <= 0) return;
@@ -281,7 +282,11 @@ void launch_et_attn_fwd(const Graph& g, int N, const EtAttnArgs& a_in, float* xa
   EtAttnArgs a = a_in;
   if (et_g16_ok(N, a.slot_stride / 2, a)) launch_et_attn_fwd_g16(g, N, a, xagg, vagg, s);
   else a.tile_open = nullptr;
-  if (et_pipelined_ok(a)) {
+  launch_et_attn_fwd_rows(g, N, a, et_pipelined_ok(a), xagg, vagg, s);
+}
+void launch_et_attn_fwd_rows(const Graph& g, int N, const EtAttnArgs& a, bool pipelined, float* xagg, float* vagg, hipStream_t s) {
+  if (N <= 0) return;
+  if (pipelined) {
     const dim3 grid(N), block(a.F);
 #define ET_FWD2(DK, DV, VC, BF)                                                                                    \
   if (a.hd == 16) hipLaunchKernelGGL((k_et_attn_fwd_p<DK, DV, VC, 16, BF>), grid, block, 0, s, g, a, xagg, vagg); \
@@ -653,7 +658,12 @@ void launch_et_attn_bwd(const Graph& g, int N, const EtAttnArgs& a_in, const flo
   if (!tiles) a.tile_open = nullptr;
   // (the row sweeps below write one slot array per 64 channels and zero the remaining et_sweep_waves(F) - F / 64 themselves)
   if (tiles) launch_et_attn_bwd_g16(g, N, a, g_xagg, g_vagg, g_qkv, g_vec, gd2, gr2, s);  // (see launch_et_attn_fwd)
-  if (et_pipelined_ok(a)) {
+  launch_et_attn_bwd_rows(g, N, a, et_pipelined_ok(a), g_xagg, g_vagg, g_qkv, g_vec, gd2, gr2, s);
+}
+void launch_et_attn_bwd_rows(const Graph& g, int N, const EtAttnArgs& a, bool pipelined, const float* g_xagg, const float* g_vagg,
+                             float* g_qkv, float* g_vec, float* gd2, float* gr2, hipStream_t s) {
+  if (N <= 0) return;
+  if (pipelined) {
     const dim3 grid(N), block(a.F);
 #define ET_BWD2(DK, DV, VC, BF)                                                                                                  \
   if (a.hd == 16)                                                                                                               \

@@ -1183,3 +1183,164 @@ int et_hvp_debug_tensor(tmdnet_model* m, hipStream_t s, const char* name, float*
   HIP_TRY(m, hipMemcpyAsync(out, it->second.first, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, s));
   return TMDNET_OK;
 }
+
+// ---- one kernel of tn_et.hip / tn_et_g16.hip through its launcher, on the caller's operands (tests/test_gpu_et_unit.py)
+static_assert(TMDNET_ET_OP_QUERY == 0 && TMDNET_ET_OP_TRAIN_GPRE == 9 && TMDNET_ET_AUTO == 0 && TMDNET_ET_TILE == 3, "values of the header");
+extern "C" int tmdnet_debug_et(void* stream, const tmdnet_et_unit_args* x, int32_t* route_out) {
+  if (!x) return TMDNET_ERR_INVALID;
+  const int op = x->op, N = x->N, P = x->P, F = x->F, hd = x->hd, Wd = x->Wd;
+  if (N < 1 || P < 0) return TMDNET_ERR_INVALID;
+  const int64_t P1 = (int64_t)P + 1;
+  if (op == TMDNET_ET_OP_QUERY) {  // the tile kernels' predicate on the sizes alone: nothing is dereferenced
+    if (!route_out || F < 1 || hd < 1 || Wd < 0) return TMDNET_ERR_INVALID;
+    *route_out = tn::et_g16_shape_ok(N, P1, F, hd, Wd) ? 1 : 0;
+    return TMDNET_OK;
+  }
+  const bool csr = x->rowptr && x->col && x->epair && x->esign && x->counts;
+  const bool attn = op == TMDNET_ET_OP_ATTN_FWD || op == TMDNET_ET_OP_ATTN_BWD;
+  const bool has_dk = x->dk_off >= 0, has_dv = x->dv_off >= 0;
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  // the layout of the attention operands (ATTN_FWD, ATTN_BWD, TRAIN_FILTER)
+  auto layout_ok = [&]() {
+    if (F < 1 || F > 1024 || hd < 1 || hd > 64 || (hd & (hd - 1)) || F % hd || Wd < 0) return false;
+    if (x->dk_off != -1 && x->dk_off != 0) return false;
+    if (x->dv_off != -1 && x->dv_off != (has_dk ? F : 0)) return false;
+    if (Wd < (has_dk ? F : 0) + (has_dv ? 3 * F : 0)) return false;
+    if (x->pair_bf16 != 0 && x->pair_bf16 != 1) return false;
+    if (x->pair_bf16 && (Wd & 1)) return false;
+    if ((has_dk || has_dv) && !x->dkv) return false;
+    return csr && x->prhat && x->C && x->dC && x->qkv && x->vec;
+  };
+  const bool runs_prep = op == TMDNET_ET_OP_TILE_PREP || (attn && (x->kernel == TMDNET_ET_AUTO || x->kernel == TMDNET_ET_TILE) && !x->skip_prep);
+  const bool prep_ok = x->B >= 1 && x->E >= 0 && csr && x->prhat && x->C && x->dC && x->meta && x->tile_start && x->erec && al16(x->erec);
+  bool ok = false;
+  switch (op) {
+    case TMDNET_ET_OP_TILE_PREP: ok = prep_ok; break;
+    case TMDNET_ET_OP_ATTN_FWD:
+    case TMDNET_ET_OP_ATTN_BWD: {
+      ok = layout_ok();
+      if (op == TMDNET_ET_OP_ATTN_FWD) ok = ok && x->xagg && x->vagg;
+      else
+        ok = ok && x->g_xagg && x->g_vagg && x->g_qkv && x->g_vec && x->gd2 && x->gr2 && x->slot_stride >= 2 * P1 &&
+             (!(has_dk || has_dv) || x->tkv);
+      if (!ok) break;
+      tn::EtAttnArgs probe{};
+      probe.F = F;
+      probe.hd = hd;
+      switch (x->kernel) {
+        case TMDNET_ET_ROW_GENERIC: break;
+        case TMDNET_ET_ROW_PIPELINED: ok = tn::et_pipelined_contract(probe); break;
+        case TMDNET_ET_TILE:
+          ok = tn::et_g16_shape_ok(N, op == TMDNET_ET_OP_ATTN_BWD ? x->slot_stride / 2 : P1, F, hd, Wd);
+          [[fallthrough]];
+        case TMDNET_ET_AUTO:
+          ok = ok && prep_ok && al16(x->qkv) && al16(x->vec) && al16(x->dkv) && al16(x->tkv) && al16(x->xagg) && al16(x->vagg) &&
+               al16(x->g_xagg) && al16(x->g_vagg) && al16(x->g_qkv) && al16(x->g_vec);
+          break;
+        default: ok = false;
+      }
+      break;
+    }
+    case TMDNET_ET_OP_PAIR_COMBINE:
+      ok = x->counts && x->gd2 && x->gr2 && x->gd_extra && x->gd && x->g_rhat && x->nw >= 1 && x->slot_stride >= 2 * P1;
+      break;
+    case TMDNET_ET_OP_NBR_EMBED: ok = csr && F >= 1 && x->z && x->emb && x->embN && x->Wn && x->xcat; break;
+    case TMDNET_ET_OP_NBR_EMBED_BWD:
+      ok = x->counts && x->pair_i && x->pair_j && F >= 1 && x->z && x->embN && x->g_xcat && x->dWn && x->gd2;
+      break;
+    case TMDNET_ET_OP_TRAIN_NBR:
+      ok = csr && F >= 1 && x->z && x->embN && x->Wn && x->g_xcat && x->slots && x->gEN && x->dir_stride >= P1 * F;
+      break;
+    case TMDNET_ET_OP_TRAIN_FILTER:
+      ok = layout_ok() && !x->pair_bf16 && (has_dk || has_dv) && x->g_xagg && x->g_vagg && x->slots && x->self_rows &&
+           x->dir_stride >= P1 * Wd;
+      break;
+    case TMDNET_ET_OP_TRAIN_GPRE:
+      ok = x->counts && Wd >= 1 && x->slots && x->self_sum && x->pre && x->g_pre && x->dir_stride >= P1 * Wd;
+      break;
+    default: break;
+  }
+  if (!ok) return TMDNET_ERR_INVALID;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (hipGetLastError() != hipSuccess) return TMDNET_ERR_HIP;  // an earlier error: nothing launched, *route_out untouched
+  tn::Graph g{};
+  g.rowptr = const_cast<int*>(x->rowptr);
+  g.col = const_cast<int*>(x->col);
+  g.epair = const_cast<int*>(x->epair);
+  g.esign = const_cast<float*>(x->esign);
+  g.counts = const_cast<int*>(x->counts);
+  g.pair_i = const_cast<int*>(x->pair_i);
+  g.pair_j = const_cast<int*>(x->pair_j);
+  g.prhat = const_cast<float*>(x->prhat);
+  tn::EtAttnArgs a{};
+  a.qkv = x->qkv;
+  a.vec = x->vec;
+  a.dkv = reinterpret_cast<const float*>(x->dkv);
+  a.tkv = reinterpret_cast<const float*>(x->tkv);
+  a.C = x->C;
+  a.dC = x->dC;
+  a.F = F;
+  a.hd = hd;
+  a.Wd = Wd;
+  a.dk_off = x->dk_off;
+  a.dv_off = x->dv_off;
+  a.vector_cutoff = x->vector_cutoff ? 1 : 0;
+  a.slot_stride = op == TMDNET_ET_OP_ATTN_BWD ? x->slot_stride : 2 * P1;
+  a.pair_bf16 = x->pair_bf16;
+  int route = 0;
+  bool read_meta = false;
+  if (runs_prep)
+    tn::launch_et_tile_prep(g, N, x->B, x->batch, x->C, x->dC, x->E, x->pair_bf16, x->meta, x->tile_start, x->erec, s, x->min_fill);
+  switch (op) {
+    case TMDNET_ET_OP_TILE_PREP: break;
+    case TMDNET_ET_OP_ATTN_FWD:
+    case TMDNET_ET_OP_ATTN_BWD: {
+      const bool fwd = op == TMDNET_ET_OP_ATTN_FWD;
+      if (x->kernel == TMDNET_ET_AUTO || x->kernel == TMDNET_ET_TILE) {
+        a.tile_open = x->meta;
+        a.tile_start = x->tile_start;
+        a.max_tiles = tn::et_g16_max_tiles(N, x->B);
+        a.erec = x->erec;
+        read_meta = true;
+      }
+      if (x->kernel == TMDNET_ET_AUTO) {  // exactly what the engine enqueues
+        if (fwd) tn::launch_et_attn_fwd(g, N, a, x->xagg, x->vagg, s);
+        else tn::launch_et_attn_bwd(g, N, a, x->g_xagg, x->g_vagg, x->g_qkv, x->g_vec, x->gd2, x->gr2, s);
+        route = tn::et_pipelined_ok(a) ? TMDNET_ET_ROW_PIPELINED : TMDNET_ET_ROW_GENERIC;
+        if (!tn::et_g16_ok(N, a.slot_stride / 2, a)) read_meta = false;  // the launcher took the row sweeps without asking the flag
+      } else if (x->kernel == TMDNET_ET_TILE) {
+        const tn::EtG16Opts o{x->slot_min, x->mailbox, x->sync_every};
+        if (fwd) tn::launch_et_attn_fwd_g16(g, N, a, x->xagg, x->vagg, s, &o);
+        else tn::launch_et_attn_bwd_g16(g, N, a, x->g_xagg, x->g_vagg, x->g_qkv, x->g_vec, x->gd2, x->gr2, s, &o);
+        route = 0;
+      } else {
+        const bool pip = x->kernel == TMDNET_ET_ROW_PIPELINED;
+        if (fwd) tn::launch_et_attn_fwd_rows(g, N, a, pip, x->xagg, x->vagg, s);
+        else tn::launch_et_attn_bwd_rows(g, N, a, pip, x->g_xagg, x->g_vagg, x->g_qkv, x->g_vec, x->gd2, x->gr2, s);
+        route = x->kernel;
+      }
+      break;
+    }
+    case TMDNET_ET_OP_PAIR_COMBINE:
+      tn::launch_et_pair_combine(g, P, x->gd2, x->gr2, x->nw, x->slot_stride, x->gd_extra, x->gd, x->g_rhat, s);
+      break;
+    case TMDNET_ET_OP_NBR_EMBED: tn::launch_et_nbr_embed(g, N, F, x->z, x->emb, x->embN, x->Wn, x->xcat, s); break;
+    case TMDNET_ET_OP_NBR_EMBED_BWD: tn::launch_et_nbr_embed_bwd(g, P, F, x->z, x->embN, x->g_xcat, x->dWn, x->gd2, s); break;
+    case TMDNET_ET_OP_TRAIN_NBR:
+      tn::launch_et_train_nbr(g, N, F, x->z, x->embN, x->Wn, x->g_xcat, x->slots, x->dir_stride, x->gEN, s);
+      break;
+    case TMDNET_ET_OP_TRAIN_FILTER:
+      tn::launch_et_train_filter(g, N, a, x->g_xagg, x->g_vagg, x->slots, x->dir_stride, x->self_rows, s);
+      break;
+    default: tn::launch_et_train_gpre(g, P, Wd, x->slots, x->dir_stride, x->self_sum, x->pre, x->g_pre, s);
+  }
+  if (hipGetLastError() != hipSuccess) return TMDNET_ERR_HIP;
+  if (read_meta) {  // which generation wrote: the flag the kernels themselves read
+    int meta0 = 1;
+    if (hipMemcpyAsync(&meta0, x->meta, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
+    if (meta0 == 0) route = TMDNET_ET_TILE;
+  }
+  if (route_out) *route_out = route;
+  return TMDNET_OK;
+}

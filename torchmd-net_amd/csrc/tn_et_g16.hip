@@ -749,12 +749,16 @@ using namespace g16;
 
 // the 16-lane-group sweeps apply: channel slices of 32, a head inside a lane group, and every array the kernels index with a
 // 32-bit byte offset below 2 GiB (P1 = rows of the per-pair arrays)
+// ... and every pair id, the self pair's P1 - 1 included, in the 24 bits the slot table gives it (G16_NONE, g16_walk): the
+// offset conditions do not bound the pairs of a model without distance projections (Wd = 0)
+bool et_g16_shape_ok(int64_t N, int64_t P1, int F, int hd, int64_t Wd) {
+  const int64_t lim = (int64_t)1 << 31;
+  return F % 32 == 0 && F <= 1024 && (hd == 2 || hd == 4 || hd == 8 || hd == 16 || hd == 32) &&
+         N * 5 * F * 4 < lim && P1 * Wd * 4 < lim && (2 * P1 + N) * 32 < lim && P1 - 1 <= 0xFFFFFF;
+}
 bool et_g16_ok(int N, int64_t P1, const EtAttnArgs& a) {
   static const bool off = getenv("TMDNET_ET_NO_G16") != nullptr;  // developer switch: the one-channel-per-lane kernels
-  const int64_t lim = (int64_t)1 << 31;
-  const int hd = a.hd;
-  return !off && a.tile_open && a.tile_start && a.max_tiles > 0 && a.erec && a.F % 32 == 0 && a.F <= 1024 && (hd == 2 || hd == 4 || hd == 8 || hd == 16 || hd == 32) &&
-         (int64_t)N * 5 * a.F * 4 < lim && P1 * a.Wd * 4 < lim && (2 * P1 + N) * 32 < lim;
+  return !off && a.tile_open && a.tile_start && a.max_tiles > 0 && a.erec && et_g16_shape_ok(N, P1, a.F, a.hd, a.Wd);
 }
 
 #define G16_LAUNCH(KERNEL, DK, DV, VC, HL, ...)                                                                    \
@@ -775,7 +779,8 @@ bool et_g16_ok(int N, int64_t P1, const EtAttnArgs& a) {
   {                                                                                                \
     const dim3 grid(a.max_tiles * (a.F / 32)), block(1024);                                    \
     const int key = (a.dk_off >= 0 ? 4 : 0) | (a.dv_off >= 0 ? 2 : 0) | (a.vector_cutoff ? 1 : 0); \
-    const int se = g16_sync_every(), sm = g16_slot_min();                                          \
+    const int se = opts && opts->sync_every >= 0 ? opts->sync_every : g16_sync_every();            \
+    const int sm = opts && opts->slot_min >= 0 ? opts->slot_min : g16_slot_min();                  \
     if (a.hd == 16) {                                                                              \
       G16_KEY(KERNEL, 8, __VA_ARGS__)                                                              \
     } else {                                                                                       \
@@ -789,31 +794,34 @@ int et_g16_max_tiles(int N, int B) {  // closed tiles hold whole molecules, and 
   return t < 1 ? 1 : t;
 }
 void launch_et_tile_prep(const Graph& g, int N, int B, const int64_t* batch, const float* C, const float* dC, int64_t ecap, int pair_bf16,
-                         int* meta, int* tile_start, float* erec, hipStream_t s) {
+                         int* meta, int* tile_start, float* erec, hipStream_t s, float min_fill_in) {
   if (N <= 0) return;
   const int max_tiles = et_g16_max_tiles(N, B);
   // directed edges per tile slot (64 x 64) below which the step takes the row sweeps (developer switch, in percent)
   static const int fill_env = getenv("TMDNET_ET_G16_MIN_FILL") ? atoi(getenv("TMDNET_ET_G16_MIN_FILL")) : -1;
-  const float min_fill = fill_env >= 0 ? 0.01f * (float)fill_env : (pair_bf16 ? 0.25f : 0.70f);  // (pair_bf16 = 2, bf16 values in fp32 rows, chooses like the bf16 rows)
+  const float min_fill = min_fill_in >= 0.f ? min_fill_in : fill_env >= 0 ? 0.01f * (float)fill_env : (pair_bf16 ? 0.25f : 0.70f);  // (pair_bf16 = 2, bf16 values in fp32 rows, chooses like the bf16 rows)
   launch_fill(reinterpret_cast<float*>(meta), 0.f, 2, s);
   hipLaunchKernelGGL(k_et_tile_pack, dim3(1), dim3(1024), 0, s, g, batch, N, max_tiles, min_fill, tile_start, meta);
   hipLaunchKernelGGL(k_et_tile_open, dim3((max_tiles + 3) / 4), dim3(256), 0, s, g, N, tile_start, meta);
   hipLaunchKernelGGL(k_et_edge_records, dim3((unsigned)((ecap + 255) / 256)), dim3(256), 0, s, g, C, dC, ecap, erec);
 }
-void launch_et_attn_fwd_g16(const Graph& g, int N, const EtAttnArgs& a_in, float* xagg, float* vagg, hipStream_t s) {
+void launch_et_attn_fwd_g16(const Graph& g, int N, const EtAttnArgs& a_in, float* xagg, float* vagg, hipStream_t s,
+                            const EtG16Opts* opts) {
   if (N <= 0) return;
   EtAttnArgs a = a_in;
-  a.mailbox = (g16_mailbox() && !a.pair_bf16 && a.dk_off == 0 && a.dv_off == a.F) ? 1 : 0;
+  const bool mb_on = opts && opts->mailbox >= 0 ? opts->mailbox != 0 : g16_mailbox();
+  a.mailbox = (mb_on && !a.pair_bf16 && a.dk_off == 0 && a.dv_off == a.F) ? 1 : 0;
   G16_DISPATCH(k_et_attn_fwd_g16, xagg, vagg)
 }
 void launch_et_attn_bwd_g16(const Graph& g, int N, const EtAttnArgs& a_in, const float* g_xagg, const float* g_vagg, float* g_qkv,
-                            float* g_vec, float* gd2, float* gr2, hipStream_t s) {
+                            float* g_vec, float* gd2, float* gr2, hipStream_t s, const EtG16Opts* opts) {
   if (N <= 0) return;
   EtAttnArgs a = a_in;
+  const bool mb_on = opts && opts->mailbox >= 0 ? opts->mailbox != 0 : g16_mailbox();
   {  // the exchange addresses tkv as dkv + a 32-bit byte offset
     const int64_t delta = reinterpret_cast<const char*>(a.tkv) - reinterpret_cast<const char*>(a.dkv);
     const int64_t rows_b = (a.slot_stride / 2) * (int64_t)a.Wd * (a.pair_bf16 ? 2 : 4);
-    a.mailbox = (g16_mailbox() && !a.pair_bf16 && delta >= 0 && delta + rows_b < ((int64_t)1 << 32)) ? 1 : 0;  // (bf16 rows: see the forward kernel)
+    a.mailbox = (mb_on && !a.pair_bf16 && delta >= 0 && delta + rows_b < ((int64_t)1 << 32)) ? 1 : 0;  // (bf16 rows: see the forward kernel)
   }
   G16_DISPATCH(k_et_attn_bwd_g16, g_xagg, g_vagg, g_qkv, g_vec, gd2, gr2)
 }

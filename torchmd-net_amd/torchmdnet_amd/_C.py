@@ -84,6 +84,19 @@ class Tn2UnitArgs(C.Structure):
                                           "g_pre1", "gB", "gCs", "gAp", "dAp", "dC", "gd", "pos", "box", "wq", "ec", "g_q", "fpos")]
 
 
+class EtUnitArgs(C.Structure):
+    """tmdnet_et_unit_args (include/tmdnet_amd.h): one edge-sweep kernel of the Equivariant Transformer on caller-built operands,
+    tmdnet_debug_et."""
+    _fields_ = [(n, C.c_int32) for n in ("op", "kernel", "N", "B", "P", "E", "F", "hd", "Wd", "dk_off", "dv_off", "vector_cutoff",
+                                         "pair_bf16", "skip_prep", "slot_min", "mailbox", "sync_every", "nw")] + \
+               [("min_fill", C.c_float), ("slot_stride", C.c_int64), ("dir_stride", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("rowptr", "col", "epair", "esign", "counts", "pair_i", "pair_j", "prhat", "batch",
+                                          "C", "dC", "qkv", "vec", "dkv", "tkv", "g_xagg", "g_vagg", "meta", "tile_start", "erec",
+                                          "xagg", "vagg", "g_qkv", "g_vec", "gd2", "gr2", "gd_extra", "gd", "g_rhat",
+                                          "z", "emb", "embN", "Wn", "dWn", "g_xcat", "xcat", "gEN",
+                                          "slots", "self_rows", "self_sum", "pre", "g_pre")]
+
+
 class PairPriors(C.Structure):
     """tmdnet_pair_priors (include/tmdnet_amd.h): flags, unit scales and host tables of the ZBL / D2 pair priors."""
     _fields_ = [("flags", C.c_int32), ("max_z", C.c_int32)] + \
@@ -115,6 +128,10 @@ COMMITTEE_MAX_MEMBERS, COMMITTEE_FLAG, COMMITTEE_STOP = 16, 1, 2
 # ops of tmdnet_debug_tn2 (TMDNET_TN2_* in the header)
 (TN2_EDGE_REVERSE, TN2_CP_FEAT, TN2_CP_FEAT_BWD, TN2_QEQ_FWD, TN2_QEQ_BWD, TN2_EDGE_PRE1, TN2_EDGE_GW, TN2_EDGE_REDUCE, TN2_PAIR_GD,
  TN2_COULOMB) = range(10)
+# ops and kernel selectors of tmdnet_debug_et (TMDNET_ET_* in the header)
+(ET_OP_QUERY, ET_OP_TILE_PREP, ET_OP_ATTN_FWD, ET_OP_ATTN_BWD, ET_OP_PAIR_COMBINE, ET_OP_NBR_EMBED, ET_OP_NBR_EMBED_BWD,
+ ET_OP_TRAIN_NBR, ET_OP_TRAIN_FILTER, ET_OP_TRAIN_GPRE) = range(10)
+ET_AUTO, ET_ROW_GENERIC, ET_ROW_PIPELINED, ET_TILE = range(4)
 # sweeps and kernels of tmdnet_debug_message (TMDNET_MSG_* in the header)
 MSG_OP_FWD, MSG_OP_ADJ, MSG_OP_GD, MSG_OP_DUAL = range(4)
 (MSG_AUTO, MSG_FWD_ROW, MSG_FWD_SPLIT, MSG_FWD_TILE, MSG_ADJ_ROW, MSG_ADJ_SPLIT, MSG_GD_ROW, MSG_GD_SPLIT, MSG_GD_TILE, MSG_DUAL,
@@ -202,6 +219,7 @@ def lib():
     L.tmdnet_debug_message.argtypes = [vp, C.POINTER(MessageArgs), C.POINTER(i32), C.POINTER(i32)]
     L.tmdnet_debug_message_fold.argtypes = [vp, C.POINTER(MessageFoldArgs)]
     L.tmdnet_debug_tn2.argtypes = [vp, C.POINTER(Tn2UnitArgs)]
+    L.tmdnet_debug_et.argtypes = [vp, C.POINTER(EtUnitArgs), C.POINTER(i32)]
     L.tmdnet_param_grad_count.argtypes = [vp]
     L.tmdnet_param_grad_entry.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64)]
     L.tmdnet_param_grad_entry.restype = C.c_char_p
