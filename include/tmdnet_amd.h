@@ -1448,6 +1448,82 @@ int tmdnet_neb_advance(tmdnet_model* m, void* stream, void* graph_ws, void* neb_
 /* tmdnet_min_status, and host[2] = what was unusable when status is 2: 1 a force sum, 2 the path (coincident images), 3 an energy. */
 int tmdnet_neb_status(void* stream, void* neb_ws, uint64_t host[3]);
 
+/* ---- Device-resident dimer saddle search (csrc/tn_dimer.hip; additive exports, the ABI revision stays 10) ------------------------
+ * A first-order saddle from ONE known state by minimum-mode following: the dimer method (Henkelman and Jonsson, J. Chem. Phys. 111,
+ * 7010, 1999) with forward differences (Heyden, Bell and Keil, J. Chem. Phys. 123, 224101, 2005) and the rotation from two curvature
+ * rows (Kaestner and Sherwood, J. Chem. Phys. 128, 014106, 2008), driven by the FIRE controller above with ONE controller per dimer.
+ * The launches sit between two tmdnet_energy_forces calls of a captured step: K steps replay as one HIP graph.
+ * Storage: a call has G >= 1 dimers of the same n atoms.  A dimer carries its midpoint R0, a unit axis N and a unit partner
+ * direction M at a right angle to N, both fp32 [n, 3] and zero on fixed atoms (mode, partner [G, n, 3]).  Every step evaluates three
+ * images as one batch of 3 G molecules, rows image-major: atom a of image i of dimer g is row (g 3 + i) n + a, with image 0 = R0,
+ * image 1 = R0 + delta N, image 2 = R0 + delta M (no minimum image between images).  vel, the kept forces, mode and partner have
+ * one row per atom of a DIMER: [G, n, 3].
+ * Per step, from the energies E and the forces F0, F1, F2 of the three images, dl = fp32(delta), inv = fp32(1 / delta):
+ *   per atom, fp32 under the rounding contract of the MD loop:  HN = (F0 - F1) inv,  HM = (F0 - F2) inv  (one rounded sum, one
+ *     rounded product per component), and the terms N.HN, N.HM, M.HN, M.HM, F0.N, F0.M each as (x + y) + z of three rounded
+ *     products, and (F0.F0 + F1.F1) + F2.F2; an atom with fixed[a] != 0 contributes nothing
+ *   per dimer, the terms widened and added in fp64 in the fixed order of the minimiser's sums; then, fp64 in the order written:
+ *     a = N.HN,  b = (N.HM + M.HN) / 2,  c = M.HM
+ *     (co, si), co >= 0, the unit eigenvector of [[a, b], [b, c]] for the smaller eigenvalue:  b = 0: (1, 0) when a <= c (the tie
+ *     a = c keeps the axis), (0, 1) when a > c;  otherwise theta = atan2(-2 b, c - a) / 2, co = cos theta, si = sin theta
+ *     nu^2 = sum over the free atoms of |co N + si M|^2, from the vectors, every term in fp64;  nu = sqrt(nu^2)
+ *     C = (((co co) a + ((2 co) si) b) + (si si) c) / nu^2        (the curvature N'.HN' along the new axis)
+ *     p = (co F0.N + si F0.M) / nu                                 (F0.N')
+ *     cn = fp32(co / nu), sn = fp32(si / nu), cc = fp32(C);  C < 0: k0 = 1, e = fp32(-2 p);  otherwise k0 = 0, e = fp32(-p)
+ *   per atom, fp32 under the contract:  N' = cn N + sn M,  HN' = cn HN + sn HM,  T = HN' - cc N' (the rotation residual),
+ *     R = -fp32(si) N + fp32(co) M (the rotated partner),  F_eff = k0 F0 + e N'  - that is F0 - 2 (F0.N') N' where the curvature is
+ *     negative and -(F0.N') N' in the convex region (Henkelman's rule); a fixed atom has N' = T = 0 and keeps F0
+ *   per dimer: vf, ff, vv, fmax2 of the minimiser on F_eff over the free atoms of image 0, and T.T, T.N', N'.N', R.R, R.N', HN'.HN';
+ *     the next partner M' = (mt T + mr R) + mn N':  k = T.N' / N'.N',  |T_perp|^2 = T.T - k T.N'  (T made orthogonal to N'),
+ *     mt = fp32(1 / |T_perp|), mn = fp32(-(k / |T_perp|)), mr = 0 - unless |T_perp|^2 is zero, not finite or at most 2^-40 HN'.HN':
+ *     then R takes T's place (mt = 0; mr, mn likewise from R.R and R.N'), so a converged mode keeps a defined partner; M' = 0 when R
+ *     has no length either.  |T| = sqrt(T.T) is logged; with forward differences it does not go to zero and is no criterion.
+ *     Then the minimiser's controller, unchanged, with the dimer's sums: the dimer converges when sqrt(fmax2) < fmax AND C < 0
+ *     (while C >= 0 the controller is handed a bound of zero) and is frozen bit for bit from then on - R0, N, M and the kept forces.
+ *   per atom: N <- N', M <- M', the minimiser's update of R0 with the dimer's three coefficients on F_eff (fixed atoms and frozen
+ *     dimers: v <- 0, x is not touched), then - at every launch - image 1 <- R0 + dl N and image 2 <- R0 + dl M, each one rounded
+ *     product and sum.
+ * translate = 0 (tmdnet_dimer_reset) is a mode search: R0 keeps its bits, the FIRE state is not touched, no dimer converges, and
+ * the loop only refines N and C.
+ * A dimer that still moves is unusable - status 2, nothing of that step is accepted - when an energy of its three images is not
+ * finite (cause 3), when a force sum or a FIRE sum is not finite (cause 1), or when a, b, c or nu^2 is not finite or nu^2 is zero
+ * (cause 2: the mode has no length).  When every atom is fixed there is no mode: nothing is unusable and the dimer converges as it
+ * stands.  Overflow is the minimiser's protocol: the move saves R0 and v, an overflowed evaluation latches status 1 and puts them
+ * back (and rewrites the images from them).  Only the single-block controller writes the status word; every later launch returns
+ * at once until a reset. */
+/* Bytes of the dimer state `dimer_ws`: a 256-byte header (step counter, status, the start values, the translate flag, the cause),
+ * per dimer the controller's state, the coefficients, the sums and the slice sums, per atom of a dimer R0 and v before the last
+ * move and the pending F_eff, N' and T (60 bytes).  n_dimers >= 1. */
+int tmdnet_dimer_workspace_bytes(int64_t n_atoms_per_image, int64_t n_dimers, size_t* bytes);
+/* tmdnet_min_reset, and translate = 1 / 0 switches the move of the midpoint on / off for every dimer: one captured graph serves the
+ * saddle search and the mode search.  The first launch after it must be tmdnet_dimer_advance(TMDNET_MIN_CLOSE) on the start
+ * images (vel = 0; images 1 and 2 written by the caller as R0 + fp32(delta) N, R0 + fp32(delta) M). */
+int tmdnet_dimer_reset(void* stream, void* dimer_ws, uint64_t step0, double dt0, double alpha0, int32_t translate);
+/* Enqueues one phase (TMDNET_MIN_OPEN / MIDDLE / CLOSE with the minimiser's meaning).  MIDDLE and CLOSE are four launches - the
+ * sums on a grid (dimer, slice of <= 1 024 atoms); the projection on the same grid, every block deriving its dimer's rotation from
+ * the slice sums; the controller as one block; one thread per atom of a dimer for its three rows - and OPEN is one.  The arguments
+ * of tmdnet_neb_advance with its meaning, except:
+ *   n_atoms_per_image, n_dimers   the evaluation had 3 n_dimers molecules;  pos [3 n_dimers n, 3],  vel [n_dimers n, 3].
+ *   mode, partner [n_dimers, n, 3]   N and M, read and rewritten.
+ *   forces        MIDDLE / CLOSE: the evaluation's F [3 n_dimers n, 3];  OPEN: the kept F_eff [n_dimers n, 3].
+ *   energy        [n_dimers, 3], required for MIDDLE / CLOSE.
+ *   forces_keep, true_forces_keep [n_dimers n, 3]   receive F_eff and F0 once the step is accepted; each may be NULL.
+ *   delta         > 0, in place of spring_k.
+ *   log rows      epot [n_dimers] (image 0); fmax, sums, coef, dt, alpha, converged_at per DIMER as for the minimiser; then
+ *                 curvature [n_dimers] fp64 (C), rotation [.., 2] fp64 (co, si), residual [n_dimers] fp64 (|T|), quad [.., 3] fp64
+ *                 (a, b, c), mode_sums [.., 15] fp64 (N.HN, N.HM, M.HN, M.HM, F0.N, F0.M, the forces' squares, the number of free
+ *                 atoms, nu^2, T.T, T.N', N'.N', R.R, R.N', HN'.HN') and mode_coef [.., 10] fp32 (cn, sn, cc, k0, e, fp32(co),
+ *                 fp32(si), mt, mr, mn).  Each may be NULL. */
+int tmdnet_dimer_advance(tmdnet_model* m, void* stream, void* graph_ws, void* dimer_ws, int64_t n_atoms_per_image, int64_t n_dimers,
+                         int32_t phase, float* pos, float* vel, float* mode, float* partner, const float* forces, const float* energy,
+                         const uint8_t* fixed, float* forces_keep, float* true_forces_keep, double dt_max, int32_t n_min, double f_inc,
+                         double f_dec, double alpha0, double f_alpha, double max_step, double fmax, double delta, float* epot_log_row,
+                         float* fmax_log_row, double* sums_log_row, float* coef_log_row, double* dt_log_row, double* alpha_log_row,
+                         int64_t* converged_log_row, double* curvature_log_row, double* rotation_log_row, double* residual_log_row,
+                         double* quad_log_row, double* mode_sums_log_row, float* mode_coef_log_row);
+/* tmdnet_min_status, and host[2] = what was unusable when status is 2: 1 a force or FIRE sum, 2 the mode, 3 an energy. */
+int tmdnet_dimer_status(void* stream, void* dimer_ws, uint64_t host[3]);
+
 /* ---- Hessians and normal-mode preparation assembled on the device (csrc/tn_vib.hip; additive exports, the ABI revision stays 10) ----
  * The molecules of a batch are independent, so R replicas of a batch of B molecules and N atoms, each carrying ONE coordinate of
  * every molecule, give R Hessian columns of every molecule from one evaluation of the replicated batch: analytically, hv = H v of

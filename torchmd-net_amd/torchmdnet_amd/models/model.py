@@ -1933,6 +1933,56 @@ class TorchMD_Net(nn.Module):
         images = images if images.dim() == 4 else images[None]
         return DeviceNEB(self, z, images, box, q, steps_per_replay, fmax, spring, climb, fire, fixed, warmup)
 
+    def capture_dimer(self, z: Tensor, pos: Tensor, mode: Optional[Tensor] = None, box: Optional[Tensor] = None,
+                      q: Optional[Tensor] = None, steps_per_replay: int = 10, fmax: float = 0.05, delta: float = 0.01,
+                      translate: bool = True, seed: int = 0, fire: Optional[dict] = None, fixed: Optional[Tensor] = None,
+                      warmup: int = 3):
+        """Capture ``steps_per_replay`` steps of a dimer (minimum-mode-following) saddle search into ONE HIP graph (needs
+        ``static_shapes=True``): a first-order saddle point from ONE known state.  ``z`` [n]; ``pos`` [n,3] (one dimer) or [G,n,3]
+        (G dimers of the same atoms); ``mode`` [n,3] or [G,n,3], the start axis (None: a seeded normal draw per dimer, ``seed``); the
+        axis and a seeded partner direction at a right angle are orthonormalised in fp64 on the host.  Every step evaluates the
+        midpoint R0, R0 + delta N and R0 + delta M of all dimers as one batch of 3 G molecules; the curvatures, the rotation of the
+        axis towards the lowest mode, the force with its component along the axis inverted (F0 - 2 (F0.N) N where the curvature C is
+        negative, -(F0.N) N where it is not) and FIRE with one controller per dimer run as HIP kernels between the evaluations
+        (``tmdnet_dimer_advance``) - no host work between steps.  A dimer stops moving at the step where its largest atomic |F_eff|
+        falls below ``fmax`` with C < 0.  ``delta`` in length units (forward differences: 0.01, the default of
+        ``hessian(method="central")``); ``translate=False`` keeps the midpoint and only refines the mode and C; ``fire`` as for
+        ``capture_minimize``; ``fixed`` [n] marks atoms that never move and carry no mode; a [3,3] ``box`` is shared by all images;
+        ``q``, if given, is one value per dimer.  Works for every architecture ``capture_minimize`` serves.  Returns a
+        ``torchmdnet_amd.dimer.DeviceDimer``: ``dimer(n)`` replays n times; ``dimer.pos / mode / forces / effective_forces``
+        [G,n,3], ``dimer.epot / curvature / fmax / residual`` [K,G], ``dimer.converged_at / step_size`` [G], ``dimer.check()``,
+        ``dimer.reset(pos=None, mode=None, translate=None)``, ``dimer.run(max_steps, check_every)``."""
+        from torchmdnet_amd.dimer import DeviceDimer, orthonormal_pair
+        from torchmdnet_amd.minimize import parse_fire
+
+        if not float(fmax) > 0:
+            raise ValueError(f"fmax must be positive, got {fmax}")
+        if not (float(delta) > 0 and float(delta) < float("inf")):
+            raise ValueError(f"delta must be positive and finite, got {delta}")
+        parse_fire(fire)
+        if z.dim() != 1:
+            raise ValueError(f"z must be [n], the atoms of ONE dimer image, got {tuple(z.shape)}")
+        n = int(z.shape[0])
+        if pos.dim() not in (2, 3) or tuple(pos.shape[-2:]) != (n, 3):
+            raise ValueError(f"pos must be [{n},3] or [G,{n},3] for {n} atoms, got {tuple(pos.shape)}")
+        if pos.dim() == 3 and pos.shape[0] < 1:
+            raise ValueError("pos holds no dimer")
+        n_dimers = 1 if pos.dim() == 2 else int(pos.shape[0])
+        if mode is not None and tuple(mode.shape) not in ((n, 3), (n_dimers, n, 3)):
+            raise ValueError(f"mode must be [{n},3] or [{n_dimers},{n},3], got {tuple(mode.shape)}")
+        if fixed is not None and fixed.numel() != n:
+            raise ValueError(f"fixed must have one entry per atom of an image ({n}), got {fixed.numel()}")
+        if q is not None and q.numel() != n_dimers:
+            raise ValueError(f"q must have one entry per dimer ({n_dimers}), got {q.numel()}")
+        N, M = orthonormal_pair(mode, n_dimers, n, fixed, seed)  # (raises for a mode that is zero on the free atoms)
+        z, _, box, q, _, _ = self._capture_inputs("capture_dimer", "a dimer needs", z, pos, None, box, q, 3 * n_dimers, steps_per_replay)
+        if box is not None and box.dim() != 2:
+            raise ValueError(f"capture_dimer takes one [3,3] box shared by all images, got {tuple(box.shape)}")
+        q = None if q is None else q.reshape(-1)
+        pos = pos if pos.dim() == 3 else pos[None]
+        return DeviceDimer(self, z, pos, N.to(pos.device), M.to(pos.device), box, q, steps_per_replay, fmax, delta, translate, fire, fixed,
+                           warmup)
+
     def hessian(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None, q: Optional[Tensor] = None,
                 method: str = "analytic", delta: float = 0.01, fixed: Optional[Tensor] = None, replicas: Optional[int] = None,
                 max_workspace_bytes: int = 8 << 30, atom_weights=None):
