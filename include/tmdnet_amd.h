@@ -1524,6 +1524,74 @@ int tmdnet_dimer_advance(tmdnet_model* m, void* stream, void* graph_ws, void* di
 /* tmdnet_min_status, and host[2] = what was unusable when status is 2: 1 a force or FIRE sum, 2 the mode, 3 an energy. */
 int tmdnet_dimer_status(void* stream, void* dimer_ws, uint64_t host[3]);
 
+/* ---- Device-resident intrinsic reaction coordinate (csrc/tn_irc.hip; additive exports, the ABI revision stays 10) ----------------
+ * The path of steepest descent in mass-weighted coordinates from a saddle point, in both directions: the damped velocity Verlet
+ * path follower of Hratchian and Schlegel (J. Phys. Chem. A 106, 165, 2002) - a classical trajectory with a = force_scale F / m
+ * whose speed is put back to a constant v0 after every step, so that dx/dt is parallel to F / m; one evaluation per step, one time
+ * step per path chosen from an error estimate.  The launches sit between two tmdnet_energy_forces calls of a captured step: K steps
+ * replay as one HIP graph.
+ * Storage: a call has G >= 1 saddles of the same n atoms and D = 1 or 2 directions; the P = G D paths are evaluated as one batch of
+ * P molecules, rows path-major: atom a of path p = g D + d is row p n + a, with sigma = +1 for d = 0 (forward) and -1 for d = 1.
+ * pos, vel and the kept forces are [P, n, 3]; half_inv_mass [n] holds c_a = fp32(force_scale / (2 m_a)) and masses [n] fp32(m_a).
+ * An atom with fixed[a] != 0 or c_a = 0 (infinite mass) never moves, has v = 0 and is left out of every sum.
+ * Start (the caller writes it): x_0 = x_TS + (sigma fp32(initial_step)) u and v_0 = (sigma fp32(v0)) u with u the unit direction,
+ * zero on the atoms that never move; one rounded product (and sum) per component.
+ * Step i -> i+1, with dt_i the path's time step rounded to fp32 once:
+ *   open, before the evaluation (tn_md::open_step, unchanged):  hk = dt_i c_a,  v_half = v_i + hk F_i,  x_{i+1} = x_i + dt_i v_half;
+ *     (x_i, v_i, F_i) is kept as generation 1 and the former generation 1 becomes generation 2: (x_{i-1}, v_{i-1}, F_{i-1}, dt_{i-1})
+ *   per atom after the evaluation at x_{i+1}, fp32 under the rounding contract of the MD loop:  v' = v_half + hk F_{i+1}
+ *   per path over the atoms that move, the fp32 terms widened and added in fp64 in the fixed order of the minimiser's sums:
+ *     vv = sum |v'|^2,  P = sum F_{i+1}.v',  fmax2 = max |F_{i+1}|^2,  ds2 = sum m_a |x_{i+1} - x_i|^2,  the number of atoms, and -
+ *     only when a generation 2 exists -  D2 = sum |x_{i+1} - x'|^2  with  x' = (x_{i-1} + T v_{i-1}) + (T T) (c_a F_{i-1}),
+ *     T = dt_{i-1} + dt_i in fp32: where constant acceleration from two steps back would have led
+ *   per path, fp64 in the order written:
+ *     c = v0 / sqrt(vv)                                                                  (the damping; fp32(c) multiplies)
+ *     dt_{i+1} = clamp(dt_i clamp(cbrt(error / sqrt(D2)), 1/2, 2), dt_min, dt_max); unchanged on a path's first step and when D2 = 0
+ *     s_{i+1} = s_i + sqrt(ds2)                                                          (the mass-weighted arc length)
+ *     the path finishes at this step when sqrt(fmax2) < fmax (reason 1), otherwise when P <= 0 (reason 2: it has turned uphill, the
+ *     minimum lies within one step behind it), and is frozen bit for bit from then on - x, v, the kept forces, dt
+ *   per atom:  v_{i+1} = fp32(c) v', one product; then the open of the next step.
+ * The control of the start images (the launch after tmdnet_irc_reset) is the same with hk = 0, ds2 = 0 and the time step unchanged.
+ * A path that still moves is unusable - status 2, nothing of that step is accepted and x, v of generation 1 are put back - when its
+ * energy is not finite (cause 3), when P or fmax2 is not finite (cause 1), or when vv is zero or not finite or D2 or ds2 is not finite
+ * (cause 2), looked at in this order.  When no atom of a path moves nothing is unusable and the path is finished as it stands.
+ * Overflow is the minimiser's protocol: an overflowed evaluation latches status 1 and generation 1 is put back.  Only the
+ * single-block controller writes the status word; every later launch changes nothing until a reset.
+ * The path record lives in the workspace: on every `every`-th accepted step of a path (the start images are step 0) and on its
+ * finishing step x_{i+1} is copied into the path's next frame, with s and the energy; when the `capacity` frames are full recording
+ * stops and the count goes on counting.  Layout, so that a caller can read it: the workspace is used from its first address that is
+ * a multiple of 256; the 256-byte header is followed by n_recorded int32 [P], frame_s fp64 [P, capacity], frame_energy fp32
+ * [P, capacity] and frames fp32 [P, capacity, n, 3], each array beginning on the next multiple of 256 bytes. */
+/* Bytes of the state `irc_ws`: the header (step counter, status, cause, the start time step), the record, per path the controller's
+ * state, the sums and the slice sums, and per atom the two generations (72 bytes).  n_paths >= 1, capacity >= 1. */
+int tmdnet_irc_workspace_bytes(int64_t n_atoms, int64_t n_paths, int64_t capacity, size_t* bytes);
+/* Step counter = step0, status cleared, every path moving again with time step dt0 > 0, s = 0 and an empty record; both
+ * generations are forgotten.  The first launch after it must be tmdnet_irc_advance(TMDNET_MIN_CLOSE) on the start images. */
+int tmdnet_irc_reset(void* stream, void* irc_ws, uint64_t step0, double dt0);
+/* Enqueues one phase (TMDNET_MIN_OPEN / MIDDLE / CLOSE with the minimiser's meaning).  MIDDLE and CLOSE are three launches - the
+ * six sums in one pass on a grid (path, slice of <= 1 024 atoms); the controller as one block; one thread per atom - and OPEN is
+ * one.  Nothing allocates or synchronises.
+ *   m, graph_ws   as for tmdnet_min_advance (both NULL: no overflow counter is looked at).
+ *   n_atoms, n_paths, capacity   as given to tmdnet_irc_workspace_bytes;  every >= 1.
+ *   pos, vel [n_paths n, 3]   read and rewritten.
+ *   forces        MIDDLE / CLOSE: the evaluation's F [n_paths n, 3];  OPEN: the kept forces.
+ *   energy        [n_paths], required for MIDDLE / CLOSE.
+ *   half_inv_mass, masses [n]; fixed [n] or NULL.
+ *   forces_keep [n_paths n, 3]   receives F once the step is accepted; may be NULL.
+ *   fmax, v0, error, dt_min <= dt_max   all > 0.
+ *   log rows      epot, fmax [n_paths] fp32; sums [.., 6] fp64 (vv, P, fmax2, D2, ds2, the number of atoms that move); coef [.., 2]
+ *                 fp32 (fp32(c), fp32(dt_i)); dt (dt_{i+1}), arc (s_{i+1}), power (P) [n_paths] fp64.  Each may be NULL.
+ *   converged_at int64, reason int32, step_size fp64, arc_length fp64, n_recorded int32 [n_paths]   the paths' state after this
+ *                 step.  Each may be NULL. */
+int tmdnet_irc_advance(tmdnet_model* m, void* stream, void* graph_ws, void* irc_ws, int64_t n_atoms, int64_t n_paths, int64_t capacity,
+                       int32_t every, int32_t phase, float* pos, float* vel, const float* forces, const float* energy,
+                       const float* half_inv_mass, const float* masses, const uint8_t* fixed, float* forces_keep, double fmax, double v0,
+                       double error, double dt_min, double dt_max, float* epot_log_row, float* fmax_log_row, double* sums_log_row,
+                       float* coef_log_row, double* dt_log_row, double* arc_log_row, double* power_log_row, int64_t* converged_at,
+                       int32_t* reason, double* step_size, double* arc_length, int32_t* n_recorded);
+/* tmdnet_min_status, and host[2] = what was unusable when status is 2: 1 the forces, 2 the velocity or a path sum, 3 an energy. */
+int tmdnet_irc_status(void* stream, void* irc_ws, uint64_t host[3]);
+
 /* ---- Hessians and normal-mode preparation assembled on the device (csrc/tn_vib.hip; additive exports, the ABI revision stays 10) ----
  * The molecules of a batch are independent, so R replicas of a batch of B molecules and N atoms, each carrying ONE coordinate of
  * every molecule, give R Hessian columns of every molecule from one evaluation of the replicated batch: analytically, hv = H v of

@@ -281,6 +281,11 @@ def lib():
     L.tmdnet_dimer_advance.argtypes = [vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, f64, f64, f64, f64, f64,
                                        f64, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tmdnet_dimer_status.argtypes = [vp, vp, C.POINTER(u64)]
+    L.tmdnet_irc_workspace_bytes.argtypes = [i64, i64, i64, C.POINTER(sz)]
+    L.tmdnet_irc_reset.argtypes = [vp, vp, u64, f64]
+    L.tmdnet_irc_advance.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f64, f64, f64, f64, f64,
+                                     vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tmdnet_irc_status.argtypes = [vp, vp, C.POINTER(u64)]
     L.tmdnet_vib_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
     L.tmdnet_vib_seed.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, vp, vp, f32, vp]
     L.tmdnet_vib_gather.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]

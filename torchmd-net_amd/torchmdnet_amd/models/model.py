@@ -1983,6 +1983,79 @@ class TorchMD_Net(nn.Module):
         return DeviceDimer(self, z, pos, N.to(pos.device), M.to(pos.device), box, q, steps_per_replay, fmax, delta, translate, fire, fixed,
                            warmup)
 
+    def capture_irc(self, z: Tensor, pos: Tensor, mode: Tensor, masses: Tensor, dt: float, direction: str = "both",
+                    box: Optional[Tensor] = None, q: Optional[Tensor] = None, steps_per_replay: int = 10, force_scale: float = 1.0,
+                    fmax: float = 0.05, v0: float = 0.02, error: float = 1.5e-3, initial_step: float = 0.05,
+                    dt_min: Optional[float] = None, dt_max: Optional[float] = None, record: Optional[dict] = dict(every=1, capacity=512),
+                    fixed: Optional[Tensor] = None, warmup: int = 3):
+        """Capture ``steps_per_replay`` steps of an intrinsic-reaction-coordinate (IRC) follower into ONE HIP graph (needs
+        ``static_shapes=True``): the path of steepest descent in mass-weighted coordinates from a saddle point, which shows the two
+        minima the saddle connects and the energy profile E(s) between them.  ``z`` [n]; ``pos`` [n,3] (one saddle) or [G,n,3] (G
+        saddles of the same atoms); ``mode`` [n,3] or [G,n,3], a Cartesian direction along the transition vector (``dimer.mode``, or a
+        column of ``vib.displacements()`` reshaped), normalised in fp64 on the host; ``masses`` [n]; ``dt`` the first time step.
+        ``direction``: "both" (every saddle runs forward, along ``mode``, and backward), "forward" or "backward".  The damped
+        velocity Verlet path follower (Hratchian and Schlegel, J. Phys. Chem. A 106, 165, 2002): a trajectory with
+        a = ``force_scale`` F / m from x_TS +- ``initial_step`` u whose speed is put back to ``v0`` after every step, so that it
+        moves along F / m; each path chooses its own time step so that the estimated error of a step stays near ``error`` (a length),
+        between ``dt_min`` and ``dt_max`` (None: dt / 16 and 16 dt).  The paths of all saddles are evaluated as one batch and the
+        integrator, the controllers and the path record run as HIP kernels between the evaluations (``tmdnet_irc_advance``) - no host
+        work between steps.  A path finishes at the step where its largest atomic |F| falls below ``fmax`` (reason 1) or where it
+        turns uphill (reason 2: the minimum lies within one step behind it; ``capture_minimize`` from ``irc.pos`` relaxes it).  The
+        defaults of ``v0`` and ``error`` are the paper's 0.04 bohr/fs and 0.003 bohr in Angstrom and fs.  ``record`` =
+        dict(every=S, capacity=C) keeps every S-th point of a path, the start image and its last point on the device, at most C per
+        path (``irc.truncated`` tells when more were taken).  ``fixed`` [n] marks atoms that never move; a [3,3] ``box`` is shared by
+        all paths; ``q``, if given, is one value per saddle.  Works for every architecture ``capture_minimize`` serves.  Returns a
+        ``torchmdnet_amd.irc.DeviceIRC``: ``irc(n)`` replays n times; ``irc.pos / vel / forces`` [G,D,n,3], ``irc.epot / fmax /
+        arc / dt / power`` [K,G,D], ``irc.converged_at / reason / step_size / arc_length / n_recorded`` [G,D], ``irc.check()``,
+        ``irc.reset(pos=None, mode=None)``, ``irc.run(max_steps, check_every)``, ``irc.path(g)`` -> dict(s, energy, pos)."""
+        from torchmdnet_amd.irc import _DIRECTIONS, DeviceIRC, unit_direction
+
+        if direction not in _DIRECTIONS:
+            raise ValueError(f"direction must be one of {sorted(_DIRECTIONS)}, got {direction!r}")
+        for name, value in (("fmax", fmax), ("v0", v0), ("error", error), ("initial_step", initial_step), ("dt", dt), ("force_scale", force_scale)):
+            if not (float(value) > 0 and float(value) < float("inf")):
+                raise ValueError(f"{name} must be positive and finite, got {value}")
+        dt_min = float(dt) / 16.0 if dt_min is None else float(dt_min)
+        dt_max = float(dt) * 16.0 if dt_max is None else float(dt_max)
+        if not (dt_min > 0 and dt_max < float("inf")) or dt_min > dt_max:
+            raise ValueError(f"dt_min and dt_max must be positive, finite and ordered, got {dt_min} and {dt_max}")
+        record = dict(every=1, capacity=512) if record is None else dict(record)
+        every, capacity = int(record.pop("every", 1)), int(record.pop("capacity", 512))
+        if record:
+            raise ValueError(f"record takes every and capacity, got also {sorted(record)}")
+        if every < 1 or capacity < 1:
+            raise ValueError(f"record needs every >= 1 and capacity >= 1, got every={every}, capacity={capacity}")
+        if z.dim() != 1:
+            raise ValueError(f"z must be [n], the atoms of ONE saddle, got {tuple(z.shape)}")
+        n = int(z.shape[0])
+        if pos.dim() not in (2, 3) or tuple(pos.shape[-2:]) != (n, 3):
+            raise ValueError(f"pos must be [{n},3] or [G,{n},3] for {n} atoms, got {tuple(pos.shape)}")
+        if pos.dim() == 3 and pos.shape[0] < 1:
+            raise ValueError("pos holds no saddle")
+        n_saddles = 1 if pos.dim() == 2 else int(pos.shape[0])
+        if tuple(mode.shape) not in ((n, 3), (n_saddles, n, 3)):
+            raise ValueError(f"mode must be [{n},3] or [{n_saddles},{n},3], got {tuple(mode.shape)}")
+        if masses.numel() != n:
+            raise ValueError(f"masses must have one entry per atom of a saddle ({n}), got {masses.numel()}")
+        if not bool((masses.detach() > 0).all()):
+            raise ValueError("masses must be positive")
+        if fixed is not None and fixed.numel() != n:
+            raise ValueError(f"fixed must have one entry per atom of a saddle ({n}), got {fixed.numel()}")
+        if q is not None and q.numel() != n_saddles:
+            raise ValueError(f"q must have one entry per saddle ({n_saddles}), got {q.numel()}")
+        still = torch.isinf(masses.detach().cpu().reshape(-1))
+        if fixed is not None:
+            still = still | (fixed.detach().cpu().reshape(-1) != 0)
+        u = unit_direction(mode, n_saddles, n, still)  # (raises for a mode that is zero on the atoms that move)
+        signs = _DIRECTIONS[direction]
+        z, _, box, q, _, _ = self._capture_inputs("capture_irc", "a path needs", z, pos, None, box, q, len(signs) * n_saddles, steps_per_replay)
+        if box is not None and box.dim() != 2:
+            raise ValueError(f"capture_irc takes one [3,3] box shared by all paths, got {tuple(box.shape)}")
+        q = None if q is None else q.reshape(-1)
+        pos = pos if pos.dim() == 3 else pos[None]
+        return DeviceIRC(self, z, pos, u.to(pos.device), masses, dt, signs, box, q, steps_per_replay, force_scale, fmax, v0, error, initial_step,
+                         dt_min, dt_max, every, capacity, fixed, warmup)
+
     def hessian(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None, q: Optional[Tensor] = None,
                 method: str = "analytic", delta: float = 0.01, fixed: Optional[Tensor] = None, replicas: Optional[int] = None,
                 max_workspace_bytes: int = 8 << 30, atom_weights=None):
