@@ -1592,6 +1592,66 @@ int tmdnet_irc_advance(tmdnet_model* m, void* stream, void* graph_ws, void* irc_
 /* tmdnet_min_status, and host[2] = what was unusable when status is 2: 1 the forces, 2 the velocity or a path sum, 3 an energy. */
 int tmdnet_irc_status(void* stream, void* irc_ws, uint64_t host[3]);
 
+/* ---- Relaxed coordinate scans: a constrained FIRE minimiser in one graph (csrc/tn_scan.hip; additive exports, the ABI revision stays 10) ----
+ * G points, each a copy of the same n atoms (atom a of point g is row g n + a; the evaluation sees G molecules), share D <= 4
+ * collective variables - distance, angle, torsion, the functions and gradients of the MD bias (csrc/tn_bias_math.h), indices within
+ * the molecule - and each point has its own final targets t_fin [G, D].  Every point is minimised with its CVs held at exact values
+ * t_cur, which move from the CVs of the start geometry to t_fin by at most drive_d per step.  Per step, after the evaluation F(x),
+ * per point, in fp64 on the widened fp32 positions (csrc/tn_scan_math.h):
+ *   the CVs s_d and gradients g_d, rows on fixed atoms zero;  M = g g^T (D x D);  M lambda = g.F and M mu = g.v by Cholesky;
+ *     lambda and mu are rounded to fp32 once
+ *   F_perp = F - sum_d lambda_d g_d,  v_perp = v - sum_d mu_d g_d:  on a CV atom the correction is the fp64 sum in (CV, slot) order,
+ *     rounded to fp32 once and added with one md_add; other atoms are untouched
+ *   FIRE's sums vf, ff, vv, fmax2 of (v_perp, F_perp) over the atoms that are not fixed, in the minimiser's fixed order, and
+ *     tn_min::fire_control, unchanged, one controller per point: a point converges when sqrt(fmax2) < fmax AND t_cur = t_fin; until
+ *     the targets have arrived the controller is handed a bound of zero.  A converged point is frozen bit for bit
+ *   the move tn_min::atom_move on (v_perp, F_perp)
+ *   the drive  t_cur_d <- t_cur_d + clamp(diff(t_fin_d, t_cur_d), +-drive_d), exactly t_fin_d on arrival; a torsion goes the short way
+ *   the constraint step on the fp64 positions of the CV atoms: up to max_iter corrections x <- x - sum_d nu_d g_d with
+ *     (g g^T) nu = sigma, sigma_d = diff(s_d(x), t_cur_d), gradients at the current iterate, until max_d |sigma_d| < tol; then the
+ *     CV atoms that are not fixed are rounded to fp32 once and written
+ * At a constrained minimum dE/dt_d = -lambda_d: the logged multiplier is the mean force along the scan.
+ * A point that still moves is unusable - status 2 - when a FIRE sum or its energy is not finite (cause 1), a CV or a gradient is not
+ * finite (2), the Gram matrix has a pivot that is not positive and finite (3: two identical CVs, a CV whose atoms are all fixed) or
+ * the constraint step did not converge in max_iter corrections (4).  Causes 1 to 3 are found before anything of the step is accepted.
+ * The constraint step follows the move, so it writes nothing when it fails - neither positions nor the driven t_cur - and flags its point; the controller of the next step
+ * latches cause 4 and the x and v the move had saved are put back.  Overflow is the minimiser's protocol (status 1, x and v put
+ * back).  Only the single-block controller writes the status word; every later launch changes nothing until a reset. */
+/* Bytes of the state `scan_ws`: the header, per point the controller's state, targets, CVs, multipliers, the corrections of the <= 16
+ * CV atoms and the slice sums, and per atom the saved x and v (24 bytes).  n_atoms >= 1, n_points >= 1. */
+int tmdnet_scan_workspace_bytes(int64_t n_atoms, int64_t n_points, size_t* bytes);
+/* Step counter = step0, status cleared, every point moving again with dt0 > 0 and alpha0.  The first launch after it must be
+ * tmdnet_scan_advance(TMDNET_MIN_CLOSE) on the start geometry: it sets t_cur to the CVs found there and counts no step. */
+int tmdnet_scan_reset(void* stream, void* scan_ws, int64_t n_atoms, int64_t n_points, uint64_t step0, double dt0, double alpha0);
+/* Enqueues one phase (TMDNET_MIN_OPEN / MIDDLE / CLOSE with the minimiser's meaning).  MIDDLE is four launches - the projection and
+ * the sums on a grid (point, slice of <= 1 024 atoms), every block forming its point's multipliers itself with the same bits; the
+ * controller as one block; one thread per atom; one wave per point for the drive and the constraint step - CLOSE the first three, OPEN
+ * the last two: a replay of K steps is 4 K + 1 launches besides the evaluations.  Nothing allocates or synchronises.
+ *   m, graph_ws   as for tmdnet_min_advance (both NULL: no overflow counter is looked at).
+ *   pos, vel [n_points n, 3]   read and rewritten.
+ *   forces        MIDDLE / CLOSE: the evaluation's F [n_points n, 3];  OPEN: projected_keep.
+ *   energy        [n_points], required for MIDDLE / CLOSE.
+ *   fixed [n] or NULL.
+ *   forces_keep, projected_keep [n_points n, 3]   receive F and F_perp once the step is accepted; forces_keep may be NULL.
+ *   n_cv, cv_kind [n_cv], cv_atoms [n_cv, 4]   HOST arrays, read during the call: kinds 0 distance, 1 angle, 2 torsion; unused
+ *                 slots are ignored.  TMDNET_ERR_INVALID for n_cv outside 1..4, an index outside 0..n-1 or repeated within a CV.
+ *   targets [n_points, n_cv] fp64, device.  drive [n_cv] fp64 > 0, HOST.  tol > 0, max_iter >= 1.
+ *   the FIRE parameters and the seven log rows of tmdnet_min_advance, one entry per point.
+ *   log rows      cv, target [n_points, n_cv] fp64 (s and t_cur at the evaluation); multiplier [n_points, 2, n_cv] fp32 (lambda, mu);
+ *                 correction [n_points, A, 2, 3] fp32 (of F and v on the A distinct CV atoms, ascending); constrained
+ *                 [n_points, A, 3] fp32 and iterations [n_points] int32 (the CV atoms after this launch's constraint step and its
+ *                 number of corrections; MIDDLE and OPEN).  Each may be NULL. */
+int tmdnet_scan_advance(tmdnet_model* m, void* stream, void* graph_ws, void* scan_ws, int64_t n_atoms, int64_t n_points, int32_t phase,
+                        float* pos, float* vel, const float* forces, const float* energy, const uint8_t* fixed, float* forces_keep,
+                        float* projected_keep, int32_t n_cv, const int32_t* cv_kind, const int32_t* cv_atoms, const double* targets,
+                        const double* drive, double tol, int32_t max_iter, double dt_max, int32_t n_min, double f_inc, double f_dec,
+                        double alpha0, double f_alpha, double max_step, double fmax, float* epot_log_row, float* fmax_log_row,
+                        double* sums_log_row, float* coef_log_row, double* dt_log_row, double* alpha_log_row, int64_t* converged_log_row,
+                        double* cv_log_row, double* target_log_row, float* multiplier_log_row, float* correction_log_row,
+                        float* constrained_log_row, int32_t* iterations_log_row);
+/* tmdnet_min_status, and host[2] = the cause when status is 2: 1 a sum, 2 a CV or gradient, 3 the Gram matrix, 4 the constraint step. */
+int tmdnet_scan_status(void* stream, void* scan_ws, uint64_t host[3]);
+
 /* ---- Hessians and normal-mode preparation assembled on the device (csrc/tn_vib.hip; additive exports, the ABI revision stays 10) ----
  * The molecules of a batch are independent, so R replicas of a batch of B molecules and N atoms, each carrying ONE coordinate of
  * every molecule, give R Hessian columns of every molecule from one evaluation of the replicated batch: analytically, hv = H v of

@@ -286,6 +286,11 @@ def lib():
     L.tmdnet_irc_advance.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f64, f64, f64, f64, f64,
                                      vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tmdnet_irc_status.argtypes = [vp, vp, C.POINTER(u64)]
+    L.tmdnet_scan_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
+    L.tmdnet_scan_reset.argtypes = [vp, vp, i64, i64, u64, f64, f64]
+    L.tmdnet_scan_advance.argtypes = [vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, f64, i32, f64, i32, f64,
+                                      f64, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tmdnet_scan_status.argtypes = [vp, vp, C.POINTER(u64)]
     L.tmdnet_vib_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
     L.tmdnet_vib_seed.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, vp, vp, f32, vp]
     L.tmdnet_vib_gather.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]

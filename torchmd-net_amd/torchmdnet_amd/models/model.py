@@ -2056,6 +2056,67 @@ class TorchMD_Net(nn.Module):
         return DeviceIRC(self, z, pos, u.to(pos.device), masses, dt, signs, box, q, steps_per_replay, force_scale, fmax, v0, error, initial_step,
                          dt_min, dt_max, every, capacity, fixed, warmup)
 
+    def capture_scan(self, z: Tensor, pos: Tensor, cvs, targets: Tensor, box: Optional[Tensor] = None, q: Optional[Tensor] = None,
+                     steps_per_replay: int = 10, fmax: float = 0.05, drive=None, tol: float = 1e-8, max_iter: int = 16,
+                     fire: Optional[dict] = None, fixed: Optional[Tensor] = None, warmup: int = 3):
+        """Capture ``steps_per_replay`` steps of a relaxed coordinate scan into ONE HIP graph (needs ``static_shapes=True``): the
+        molecule minimised with chosen internal coordinates held at exact values - a torsion or bond profile, a first guess of a
+        reaction path.  ``z`` [n]; ``pos`` [n,3] (one start geometry for every point) or [G,n,3]; ``cvs`` = [("distance", i, j),
+        ("angle", i, j, k), ("torsion", i, j, k, l), ...], 1 to 4 collective variables as ``capture_md_biased`` takes them, indices
+        within the molecule, on the unwrapped positions without minimum image; ``targets`` [G,D], the final values of the D CVs at
+        each of the G points (``torchmdnet_amd.scan.grid(start, stop, n)`` makes a scan along one CV).  The G points are evaluated as
+        one batch.  Per step the force and FIRE's velocity are projected onto the tangent space of the constraints with Lagrange
+        multipliers from the D x D Gram matrix of the CV gradients, FIRE with one controller per point moves the atoms, every target
+        moves by at most ``drive`` (per CV; None: 0.1 rad for an angle or torsion, 0.05 length units for a distance) from the CV of
+        the start geometry towards its final value - a torsion the short way round - and up to ``max_iter`` Gauss-Newton corrections
+        put the CV atoms back on the constraint surface to within ``tol``: HIP kernels between the evaluations
+        (``tmdnet_scan_advance``), no host work between steps.  A point stops moving at the step where its largest atomic |F_perp|
+        falls below ``fmax`` with its targets at their final values.  ``fire`` as for ``capture_minimize``; ``fixed`` [n] marks atoms
+        that never move (a CV may contain some, not only, fixed atoms); a [3,3] ``box`` is shared by all points; ``q``, if given, is
+        one value per point.  Works for every architecture ``capture_minimize`` serves.  Returns a
+        ``torchmdnet_amd.scan.DeviceScan``: ``scan(n)`` replays n times; ``scan.pos / forces / projected_forces`` [G,n,3],
+        ``scan.epot / fmax`` [K,G], ``scan.cv / target / multiplier`` [K,G,D] (dE/dt = -multiplier at a constrained minimum),
+        ``scan.converged_at / step_size`` [G], ``scan.check()``, ``scan.reset(pos=, targets=)``, ``scan.run(max_steps,
+        check_every)``, ``scan.profile()`` -> dict(target, cv, energy, multiplier, converged)."""
+        from torchmdnet_amd.minimize import parse_fire
+        from torchmdnet_amd.scan import DeviceScan, parse_cvs, parse_drive
+
+        if not float(fmax) > 0:
+            raise ValueError(f"fmax must be positive, got {fmax}")
+        if not (float(tol) > 0 and float(tol) < float("inf")):
+            raise ValueError(f"tol must be positive and finite, got {tol}")
+        if int(max_iter) < 1:
+            raise ValueError(f"max_iter must be at least 1, got {max_iter}")
+        parse_fire(fire)
+        if z.dim() != 1:
+            raise ValueError(f"z must be [n], the atoms of ONE point, got {tuple(z.shape)}")
+        n = int(z.shape[0])
+        if pos.dim() not in (2, 3) or tuple(pos.shape[-2:]) != (n, 3):
+            raise ValueError(f"pos must be [{n},3] or [G,{n},3] for {n} atoms, got {tuple(pos.shape)}")
+        if fixed is not None and fixed.numel() != n:
+            raise ValueError(f"fixed must have one entry per atom of a point ({n}), got {fixed.numel()}")
+        kinds, atoms, distinct = parse_cvs(cvs, n, fixed)
+        drive = parse_drive(drive, kinds)
+        if targets.dim() != 2 or targets.shape[0] < 1 or targets.shape[1] != len(kinds):
+            raise ValueError(f"targets must be [G,{len(kinds)}], one row per point and one column per collective variable, got "
+                             f"{tuple(targets.shape)}")
+        if not bool(torch.isfinite(targets).all()):
+            raise ValueError("targets must be finite")
+        n_points = int(targets.shape[0])
+        if pos.dim() == 3 and pos.shape[0] != n_points:
+            raise ValueError(f"pos holds {pos.shape[0]} start geometries for {n_points} rows of targets")
+        if q is not None and q.numel() != n_points:
+            raise ValueError(f"q must have one entry per point ({n_points}), got {q.numel()}")
+        if box is not None and box.dim() != 2:  # (before anything is staged; the model's own box is looked at below)
+            raise ValueError(f"capture_scan takes one [3,3] box shared by all points, got {tuple(box.shape)}")
+        pos = (pos if pos.dim() == 3 else pos[None].expand(n_points, n, 3)).contiguous()
+        z, _, box, q, _, _ = self._capture_inputs("capture_scan", "a scan needs", z, pos, None, box, q, n_points, steps_per_replay)
+        if box is not None and box.dim() != 2:
+            raise ValueError(f"capture_scan takes one [3,3] box shared by all points, got {tuple(box.shape)}")
+        q = None if q is None else q.reshape(-1)
+        return DeviceScan(self, z, pos, kinds, atoms, distinct, targets, box, q, steps_per_replay, fmax, drive, tol, max_iter, fire, fixed,
+                          warmup)
+
     def hessian(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None, q: Optional[Tensor] = None,
                 method: str = "analytic", delta: float = 0.01, fixed: Optional[Tensor] = None, replicas: Optional[int] = None,
                 max_workspace_bytes: int = 8 << 30, atom_weights=None):
