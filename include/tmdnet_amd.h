@@ -1812,6 +1812,112 @@ int tmdnet_committee_latch(void* stream, void* ws, int64_t n_atoms, int64_t n_mo
  * bits of D (fp32) in the low word.  Synchronises the stream. */
 int tmdnet_committee_status(void* stream, void* ws, uint64_t host[5]);
 
+/* ---- Minima hopping: a conformer search inside a captured step (csrc/tn_hop.hip; additive exports, the ABI revision stays 10) ----
+ * Goedecker, J. Chem. Phys. 120, 9911 (2004); parameters named as in ASE's MinimaHopping.  The n_mol molecules of the batch are
+ * independent walkers.  A step is ONE evaluation (E, F at pos) and tmdnet_hop_advance; every walker is in one phase for the whole
+ * step, and walkers in different phases share the evaluation (csrc/tn_hop_math.h holds every statement below):
+ *   QUENCH   FIRE as in tmdnet_min_advance (unit masses, ASE's clamp), one controller per walker.  sqrt(max |f|^2) < fmax: the
+ *            walker does not move and goes to COMPARE.  After opt_steps moves without that (never for the quench of the start
+ *            geometry): outcome UNCONVERGED, the walker is put back on its current minimum, kT and ediff stay, new velocities are
+ *            drawn, LAUNCH follows.
+ *   COMPARE  one step; its evaluation repeats the last one.  For the current minimum and every live ring entry whose energy lies
+ *            within energy_tol of E, 18 fp64 sums of the pair (fresh geometry a, reference b) - n, sum a, sum b, sum a.a, sum b.b,
+ *            sum a_i b_j - give rmsd^2: align 2 (rotation) Horn's quaternion method, the largest eigenvalue of the 4 x 4 matrix of
+ *            the centred cross-covariance by 12 cyclic Jacobi sweeps, proper rotations only; align 1 (translation, and molecules of
+ *            fewer than 3 atoms) the centred sum; align 0 the plain sum.  In this order: no current minimum yet - START: recorded
+ *            (unless a kept history holds it), accepted, no parameter changes; the current minimum again (rmsd < rmsd_tol and
+ *            |dE| < energy_tol) - SAME, kT *= beta1; a ring entry - KNOWN, kT *= beta2, its visits + 1; otherwise NEW, kT *= beta3,
+ *            written to ring slot n_recorded mod capacity (the oldest entry is overwritten; n_recorded counts the START too) and
+ *            to `best` when it is the lowest ever, then ACCEPTED when E < E_cur + ediff (ediff *= alpha1; it becomes the current
+ *            minimum) or REJECTED (ediff *= alpha2).  Every outcome but START counts one hop.  The per-atom kernel copies pos into
+ *            the current minimum or puts the current minimum back into pos, then draws v = (sqrt(kT) sig_i) xi with xi from
+ *            normals3 on Philox4x32-10, key = seed, counter = (hop count lo, hi, the caller's atom index, 2).  LAUNCH follows.
+ *   LAUNCH   sums about the centroid of the current minimum: sum m, m d, m v, m d x v and the six second moments - and f.f, only so
+ *            that forces that are not finite are found before the launch's opening half-step consumes them.  v_com, and with
+ *            align 2 omega = I^-1 L about the centre of mass by an fp64 LDL^T solve (a pivot below 1e-10 of the trace: omega = 0 and
+ *            outcome SINGULAR); v <- v - (u + omega x d), u = v_com - omega x d_cm, then the opening half of an MD step.  E_0 = E.
+ *   MD       NVE: the closing and the opening half of tmdnet_md_advance's fused step.  E_k is appended; a minimum of the energy
+ *            along the escape is counted at k >= 2 when E_{k-1} < E_{k-2} and E_{k-1} <= E_k.  With mdmin minima counted, or at
+ *            k = md_steps, the escape ends in this step: v = 0, FIRE starts afresh (dt0, alpha0) and moves at once from
+ *            (v.f = 0, f.f, v.v = 0, max |f|^2); QUENCH follows.
+ * Fixed atoms (fixed[i] != 0; hk = sig = 0) never move, have zero velocity and enter no sum but those of COMPARE.
+ * Rounding: what moves an atom is fp32, one rounding per operation in the order written; the sums of LAUNCH and COMPARE are fp64
+ * products of widened fp32 values; everything per walker is fp64 and rounded to fp32 once where atoms consume it.  Sums are reduced
+ * in a fixed order without floating-point atomics: repeats are bit-identical.
+ * Status: 1 an evaluation overflowed the neighbour list (x and v of the last move are put back), 2 an energy or a sum of a walker
+ * was not finite (nothing of that step is written).  Either freezes everything until tmdnet_hop_reset. */
+#define TMDNET_HOP_QUENCH 0
+#define TMDNET_HOP_COMPARE 1
+#define TMDNET_HOP_LAUNCH 2
+#define TMDNET_HOP_MD 3
+#define TMDNET_HOP_ALIGN_NONE 0
+#define TMDNET_HOP_ALIGN_TRANSLATION 1
+#define TMDNET_HOP_ALIGN_ROTATION 2
+/* Parameters and buffers of a hop step.  Everything behind a pointer is device memory and stays the caller's; N = n_atoms,
+ * B = n_mol, C = capacity. */
+typedef struct tmdnet_hop_args {
+  double dt_max, f_inc, f_dec, alpha0, f_alpha, max_step, fmax, dt0; /* FIRE, as tmdnet_min_advance / tmdnet_min_reset */
+  double beta1, beta2, beta3, alpha1, alpha2;                        /* the feedback on kT and ediff */
+  double rmsd_tol, energy_tol;                                       /* > 0 */
+  uint64_t seed;
+  float dt;                                                          /* the MD time step */
+  int32_t n_min;                                                     /* FIRE */
+  int32_t mdmin, md_steps, opt_steps;                                /* >= 1 */
+  int32_t capacity;                                                  /* 1..64 ring entries per walker */
+  int32_t align;                                                     /* TMDNET_HOP_ALIGN_* */
+  float* pos;              /* [N, 3] read and rewritten */
+  float* vel;              /* [N, 3] read and rewritten: the MD velocity or FIRE's */
+  const float* forces;     /* [N, 3] of this step's evaluation */
+  const float* energy;     /* [B] */
+  const float* hk;         /* [N] dt force_scale / (2 m); 0 for a fixed atom */
+  const float* mass;       /* [N] */
+  const float* sig;        /* [N] sqrt(force_scale / m); 0 for a fixed atom */
+  const uint8_t* fixed;    /* [N] or NULL */
+  const int64_t* batch;    /* [N]; may be NULL for one molecule */
+  float* forces_keep;      /* [N, 3] or NULL: receives F of every accepted step */
+  float* cur_pos;          /* [N, 3] the minimum every walker hops from */
+  float* best_pos;         /* [N, 3] the lowest minimum ever recorded */
+  float* ring_pos;         /* [C, N, 3] */
+  double* ring_energy;     /* [B, C] */
+  int64_t* ring_found;     /* [B, C] the step an entry was recorded at */
+  int64_t* ring_visits;    /* [B, C] */
+  double* kT;              /* [B] the walkers' public state, rewritten by every step */
+  double* ediff;           /* [B] */
+  double* cur_energy;      /* [B] */
+  double* best_energy;     /* [B] */
+  int32_t* phase;          /* [B] the phase of the NEXT step */
+  int64_t* counters;       /* [B, 7] n_hops, n_same, n_known, n_new, n_accepted, n_unconverged, n_recorded */
+  float* epot_row;         /* log rows of this step, each [B] unless noted, each may be NULL */
+  float* fmax_row;         /* QUENCH and MD steps; 0 otherwise */
+  float* ekin_row;         /* MD steps: sum 0.5 m v^2 of the closed velocities, in the unit of m v^2; 0 otherwise */
+  int32_t* phase_row;      /* the phase the step ran in */
+  int32_t* outcome_row;    /* 0 none, 1 START, 2 SAME, 3 KNOWN, 4 ACCEPTED, 5 REJECTED, 6 UNCONVERGED, 7 SINGULAR */
+  double* sums_row;        /* [B, 16]: the phase's sums (QUENCH v.f, f.f, v.v, max |f|^2; MD ekin, f.f, 0, max |f|^2; LAUNCH its first 16;
+                              COMPARE rmsd^2 to the current minimum or -1, the smallest rmsd^2 to a ring entry looked at or -1, n) */
+  float* coef_row;         /* [B, 10]: c_v, c_f, d of FIRE, u and omega of a launch, sqrt(kT) of a draw */
+} tmdnet_hop_args;
+/* Bytes of the state `hop_ws`: the header, per walker its state, its decision and 18 (capacity + 1) sums (times the slices of a
+ * molecule of more than 1 024 atoms), per atom the saved x and v.  n_atoms >= 1, n_mol >= 1, capacity 1..64. */
+int tmdnet_hop_workspace_bytes(int64_t n_atoms, int64_t n_mol, int32_t capacity, size_t* bytes);
+/* Step counter = step0, status cleared, every walker in QUENCH of the geometry at args->pos with kT0[b], ediff0[b] (device, [B] fp64),
+ * FIRE at its start values and no current minimum; args->vel must be zero.  keep_history == 0: counters zero and the ring empty;
+ * otherwise ring, best and counters stay.  Rewrites the public state (kT, ediff, cur_energy, best_energy, phase, counters); of args it
+ * reads only the parameters, pos and vel: every other pointer may be NULL here. */
+int tmdnet_hop_reset(void* stream, void* hop_ws, int64_t n_atoms, int64_t n_mol, const tmdnet_hop_args* args, uint64_t step0,
+                     const double* kT0, const double* ediff0, int32_t keep_history);
+/* Enqueues the launches of one step after its evaluation: the reduction on a grid (walker, slice of <= 1 024 atoms), its finish
+ * pass when a molecule has more than one slice, the controller as one block, one thread per atom.  Nothing allocates or
+ * synchronises; `args` is read during the call.
+ *   m, graph_ws   the handle and graph workspace of the evaluation (the overflow counter and the molecules' atom ranges), or both
+ *                 NULL: then no overflow counter is looked at and a walker's atoms are those with batch[i] = b, so any forces and
+ *                 energies can be fed.
+ * TMDNET_ERR_INVALID before any launch for a NULL buffer other than fixed / batch (one molecule) / forces_keep / the log rows, a
+ * parameter outside its range, or a shape tmdnet_hop_workspace_bytes refuses. */
+int tmdnet_hop_advance(tmdnet_model* m, void* stream, void* graph_ws, void* hop_ws, int64_t n_atoms, int64_t n_mol,
+                       const tmdnet_hop_args* args);
+/* host[0] = the step counter, host[1] = the status.  TMDNET_ERR_OVERFLOW for status 1, TMDNET_ERR_STATE for 2.  Synchronises. */
+int tmdnet_hop_status(void* stream, void* hop_ws, uint64_t host[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,18 @@ class CommitteeGate(C.Structure):
                [(n, C.c_void_p) for n in ("md_ws", "flagged_at", "flagged_dev", "flagged_atom", "flagged_pos")]
 
 
+class HopArgs(C.Structure):
+    """tmdnet_hop_args (include/tmdnet_amd.h): the parameters and the device buffers of a minima-hopping step."""
+    _fields_ = [(n, C.c_double) for n in ("dt_max", "f_inc", "f_dec", "alpha0", "f_alpha", "max_step", "fmax", "dt0", "beta1", "beta2",
+                                          "beta3", "alpha1", "alpha2", "rmsd_tol", "energy_tol")] + \
+               [("seed", C.c_uint64), ("dt", C.c_float)] + \
+               [(n, C.c_int32) for n in ("n_min", "mdmin", "md_steps", "opt_steps", "capacity", "align")] + \
+               [(n, C.c_void_p) for n in ("pos", "vel", "forces", "energy", "hk", "mass", "sig", "fixed", "batch", "forces_keep",
+                                          "cur_pos", "best_pos", "ring_pos", "ring_energy", "ring_found", "ring_visits", "kT", "ediff",
+                                          "cur_energy", "best_energy", "phase", "counters", "epot_row", "fmax_row", "ekin_row",
+                                          "phase_row", "outcome_row", "sums_row", "coef_row")]
+
+
 class ObserveSpec(C.Structure):
     """tmdnet_md_observe_spec (include/tmdnet_amd.h): what the MD loop's observer records and how large its arrays are."""
     _fields_ = [("every", C.c_int32), ("frame_capacity", C.c_int32), ("frame_velocities", C.c_int32), ("n_pair_types", C.c_int32),
@@ -291,6 +303,10 @@ def lib():
     L.tmdnet_scan_advance.argtypes = [vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, f64, i32, f64, i32, f64,
                                       f64, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tmdnet_scan_status.argtypes = [vp, vp, C.POINTER(u64)]
+    L.tmdnet_hop_workspace_bytes.argtypes = [i64, i64, i32, C.POINTER(sz)]
+    L.tmdnet_hop_reset.argtypes = [vp, vp, i64, i64, C.POINTER(HopArgs), u64, vp, vp, i32]
+    L.tmdnet_hop_advance.argtypes = [vp, vp, vp, vp, i64, i64, C.POINTER(HopArgs)]
+    L.tmdnet_hop_status.argtypes = [vp, vp, C.POINTER(u64)]
     L.tmdnet_vib_workspace_bytes.argtypes = [i64, i64, C.POINTER(sz)]
     L.tmdnet_vib_seed.argtypes = [vp, i32, i64, i64, i64, i64, vp, vp, vp, vp, f32, vp]
     L.tmdnet_vib_gather.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -2117,6 +2117,54 @@ class TorchMD_Net(nn.Module):
         return DeviceScan(self, z, pos, kinds, atoms, distinct, targets, box, q, steps_per_replay, fmax, drive, tol, max_iter, fire, fixed,
                           warmup)
 
+    def capture_minima_hopping(self, z: Tensor, pos: Tensor, masses: Tensor, dt: float, batch: Optional[Tensor] = None,
+                               box: Optional[Tensor] = None, q: Optional[Tensor] = None, num_systems: Optional[int] = None,
+                               steps_per_replay: int = 10, force_scale: float = 9.648533e-3, kT0: float = 0.05, ediff0: float = 0.05,
+                               beta1: float = 1.1, beta2: float = 1.1, beta3: float = 1 / 1.1, alpha1: float = 0.98,
+                               alpha2: float = 1 / 0.98, mdmin: int = 2, md_steps: int = 400, opt_steps: int = 2000, fmax: float = 0.05,
+                               rmsd_tol: float = 0.1, energy_tol: float = 1e-3, capacity: int = 32, align: Optional[str] = None,
+                               seed: int = 0, fire: Optional[dict] = None, fixed: Optional[Tensor] = None, warmup: int = 3,
+                               atom_weights=None, halo_exchange=None):
+        """Capture ``steps_per_replay`` steps of a minima-hopping conformer search into ONE HIP graph (needs ``static_shapes=True``):
+        Goedecker, J. Chem. Phys. 120, 9911 (2004), parameters named as in ASE's ``MinimaHopping``.  The B molecules of the batch
+        are B independent walkers (the batch may be ragged; copies of one molecule give a parallel search of it).  Each walker
+        leaves its minimum by an NVE run with velocities drawn at ``kT`` - momentum and, with ``align="rotation"``, angular momentum
+        removed on the device - until the energy along the run has passed ``mdmin`` minima or ``md_steps`` steps, quenches with FIRE
+        to ``fmax`` (at most ``opt_steps`` steps), and compares the minimum it finds with the one it left and with a ring of
+        ``capacity`` (1..64) recorded minima: the same geometry (rmsd < ``rmsd_tol`` and |dE| < ``energy_tol``) as the one it left
+        scales kT by ``beta1``, a known one by ``beta2``, a new one by ``beta3``; a new minimum is accepted when it lies less than
+        ``ediff`` above the current one (``ediff *= alpha1``) and rejected otherwise (``ediff *= alpha2``).  ``align`` chooses the
+        rmsd: ``"rotation"`` (Horn's quaternion method; the default without a box and without fixed atoms), ``"translation"`` (the
+        default with a box) or ``"none"`` (the default with fixed atoms).  Every step is one evaluation shared by walkers in
+        different phases plus three launches (``tmdnet_hop_advance``) - no host work between steps.  Units, ``force_scale``,
+        ``masses`` and ``dt`` are ``capture_md``'s; ``fixed`` [N] marks atoms of infinite mass and zero velocity; ``fire`` is
+        ``capture_minimize``'s; ``kT0`` and ``ediff0`` in the unit of the energy.  Works for every architecture ``capture_md``
+        serves.  ``atom_weights`` / ``halo_exchange`` are accepted only to be refused.  Returns a ``torchmdnet_amd.hop.DeviceHop``:
+        ``hop(n)``, ``hop.run(hops, max_steps)``, ``hop.check()``, ``hop.reset(pos=, kT=, ediff=, history=)``, ``hop.pos / vel /
+        forces``, ``hop.phase / kT / ediff``, ``hop.minimum_pos / minimum_energy / best_pos / best_energy``, ``hop.n_hops / n_same /
+        n_known / n_new / n_accepted / n_unconverged``, the logs ``hop.epot / fmax / ekin / phase_log / outcome`` [K,B] and
+        ``hop.minima(b)``."""
+        from torchmdnet_amd.hop import DeviceHop, parse_hop
+
+        N = int(z.shape[0])
+        if masses.numel() != N:
+            raise ValueError(f"masses must have one entry per atom ({N}), got {masses.numel()}")
+        if fixed is not None and fixed.numel() != N:
+            raise ValueError(f"fixed must have one entry per atom ({N}), got {fixed.numel()}")
+        if not (float(force_scale) > 0):
+            raise ValueError(f"force_scale must be positive, got {force_scale}")
+        m = masses.detach().to(torch.float64)
+        if not bool(((m > 0) & ~torch.isnan(m)).all()):
+            raise ValueError("masses must be positive (infinite: a fixed atom)")
+        has_fixed = (fixed is not None and bool((fixed != 0).any())) or bool(torch.isinf(m).any())
+        has_box = box is not None or bool(self.representation_model.distance.use_periodic)
+        params = parse_hop(dt, kT0, ediff0, fire, align, has_box, has_fixed, beta1=beta1, beta2=beta2, beta3=beta3, alpha1=alpha1,
+                           alpha2=alpha2, mdmin=mdmin, md_steps=md_steps, opt_steps=opt_steps, fmax=fmax, rmsd_tol=rmsd_tol,
+                           energy_tol=energy_tol, capacity=capacity, seed=seed)
+        z, batch, box, q, n_mol, _ = self._capture_inputs("capture_minima_hopping", "minima hopping needs", z, pos, batch, box, q,
+                                                          num_systems, steps_per_replay, atom_weights, halo_exchange)
+        return DeviceHop(self, z, pos, masses, batch, box, q, n_mol, steps_per_replay, force_scale, params, fixed, warmup)
+
     def hessian(self, z: Tensor, pos: Tensor, batch: Optional[Tensor] = None, box: Optional[Tensor] = None, q: Optional[Tensor] = None,
                 method: str = "analytic", delta: float = 0.01, fixed: Optional[Tensor] = None, replicas: Optional[int] = None,
                 max_workspace_bytes: int = 8 << 30, atom_weights=None):
