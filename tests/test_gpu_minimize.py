@@ -306,6 +306,78 @@ def test_nan_force_latches_status_2(hip_lib):
     assert raw2.status() == (0, 1, 0) and _bits(raw2.pos, x_t)
 
 
+def test_more_molecules_than_controller_threads(hip_lib):
+    """257 molecules of 2 atoms: the one-block controller (256 threads) takes a second trip over its units, in both passes.  Every
+    step against the host mirror (tests/min_host.hip), for every molecule: the sums equal - a slice of two atoms is
+    (0 + t_0) + (0 + t_1), one rounding, whatever the reduction's order -, dt / alpha / converged_at and fmax equal to the mirror's
+    controller, which carries its own state from step to step; the coefficients within 1 ulp (fp32 roundings of fp64 results into
+    which the device compiler may contract a product, as in _check_control); x and v bit-identical to the mirror's update.  Then
+    the same shape with a force that is not finite in molecule 256 only - the last unit of the second trip: status 2, and no row,
+    state or counter is written."""
+    from tests import min_host_mirror as MH
+
+    B, n = 257, 2
+    rng = np.random.default_rng(257)
+    batch_np = np.repeat(np.arange(B), n)
+    k = (0.5 + 4.0 * rng.random(B)).astype(np.float32)[batch_np][:, None]
+    x0 = rng.standard_normal((B * n, 3)).astype(np.float32)
+    x = (x0 + 0.3 * rng.standard_normal((B * n, 3))).astype(np.float32)
+    for m in (5, 200):  # one molecule of each trip starts at its minimum: converged as it stands
+        x[batch_np == m] = x0[batch_np == m]
+    fixed_np = np.zeros(B * n, np.uint8)
+    fixed_np[[3, 2 * 256 + 1]] = 1  # an atom of molecule 1 and one of molecule 256
+    batch, fixed = torch.from_numpy(batch_np).cuda(), torch.from_numpy(fixed_np).cuda()
+    k_t, x0_t, x_t = (torch.from_numpy(a).cuda() for a in (k, x0, x))
+    force = lambda pos: -(k_t * (pos - x0_t))
+
+    def controlled(raw, state, xm, vm, f, step):
+        """the control of `step` on the mirror; the device's logs against it -> the mirror's new state"""
+        t = MH.terms(vm, f.cpu().numpy(), fixed_np).astype(np.float64).reshape(B, n, 3)
+        sums = np.concatenate([(0.0 + t[:, 0]) + (0.0 + t[:, 1]), np.maximum(t[:, :, 1].max(1), 0.0)[:, None]], 1)
+        state, coef, ret = MH.control(state, sums, P, step)
+        assert (ret != 2).all()
+        fmax, dsums, dcoef, dt, alpha, conv = (a.cpu().numpy() for a in raw.logs())
+        assert np.array_equal(dsums, sums), step
+        assert np.array_equal(dt, state[0]) and np.array_equal(alpha, state[1]) and np.array_equal(conv, state[3]), step
+        assert np.array_equal(fmax, np.sqrt(sums[:, 3]).astype(np.float32)), step
+        assert O.ulp_distance(dcoef, coef).max() <= 1, step
+        return state
+
+    raw = _Raw(hip_lib, x_t, batch, B, P, fixed)
+    state = (np.full(B, P["dt"]), np.full(B, P["alpha"]), np.zeros(B, np.int32), np.full(B, -1, np.int64))
+    xm, vm = x.copy(), np.zeros_like(x)
+    f = force(raw.pos)
+    raw.advance(CLOSE, f)
+    state = controlled(raw, state, xm, vm, f, 0)
+    assert raw.status() == (0, 0, 0) and state[3][5] == 0 and state[3][200] == 0 and (state[3] >= 0).sum() == 2
+    steps = 12
+    for step in range(1, steps + 1):
+        xm, vm = MH.update(batch_np, state[3], fixed_np, raw.coef.cpu().numpy(), xm, vm, raw.forces.cpu().numpy())
+        raw.advance(OPEN, raw.forces)
+        assert np.array_equal(raw.pos.cpu().numpy().view(np.int32), xm.view(np.int32)), step
+        assert np.array_equal(raw.vel.cpu().numpy().view(np.int32), vm.view(np.int32)), step
+        f = force(raw.pos)
+        raw.advance(CLOSE, f)
+        state = controlled(raw, state, xm, vm, f, step)
+        assert _bits(raw.forces, f)
+    assert raw.status() == (0, steps, 0)
+    assert len(set(raw.dt.tolist())) > 1 and (raw.conv[[0, 255, 256]] < 0).all()  # molecules of both trips still move
+    # a NaN in molecule 256 only
+    raw.advance(OPEN, raw.forces)
+    keep = [t.clone() for t in [raw.pos, raw.vel, raw.forces] + raw.logs()]
+    good = force(raw.pos)
+    bad = good.clone()
+    bad[2 * 256, 2] = float("nan")
+    raw.advance(CLOSE, bad)
+    assert raw.status() == (5, steps, 2)
+    raw.advance(OPEN, raw.forces)
+    raw.advance(MIDDLE, good)
+    raw.advance(CLOSE, good)
+    assert raw.status() == (5, steps, 2)
+    for t, kept in zip([raw.pos, raw.vel, raw.forces] + raw.logs(), keep):
+        assert _bits(t, kept) if t.is_floating_point() else torch.equal(t, kept)
+
+
 # ------------------------------------------------------------------------------------------------ through the model
 _models = {}
 

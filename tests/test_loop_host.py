@@ -1,5 +1,8 @@
 """The host parts of the captured loops' shared device layer (csrc/tn_loop.h), compiled host-only (tests/loop_host_mirror.py), against
-a Python spec: the slice count and the slice ranges of the per-molecule reductions, the workspace carver and the step counter."""
+a Python spec: the slice count and the slice ranges of the per-molecule reductions and their sums in slice order, the workspace carver,
+the step counter, the header's reset and status mapping, and the FIRE unit state with its log rows."""
+import os
+
 import numpy as np
 import pytest
 
@@ -119,3 +122,107 @@ def test_step_counter_round_trip():
     for step in (0, 1, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 5, 2 ** 63 + 11, 2 ** 64 - 1):
         back, lo, hi = H.step_roundtrip(step)
         assert back == step and lo == step % 2 ** 32 and hi == step >> 32
+
+
+# ---- slice_sums -----------------------------------------------------------------------------------------------------------------------
+def spec_slice_sums(slices, K, maxmask):
+    """from 0.0, the slices in order: the sum, or the maximum where the mask bit is set - one rounding per step, as the header"""
+    out = [np.float64(0.0)] * K
+    for row in slices:
+        for k in range(K):
+            v = np.float64(row[k])
+            out[k] = (v if v > out[k] else out[k]) if (maxmask >> k) & 1 else out[k] + v
+    return np.array(out)
+
+
+# (call shape, K, the entries that take the maximum, stride): FIRE's four, the IRC's six, the dimer's ten in rows three wider
+_SHAPES = [("fire", 4, 1 << 3, 4), ("irc", 6, 1 << 2, 6), ("dimer", 10, 1 << 3, 13)]
+
+
+@pytest.mark.parametrize("S", [1, 2, 3, 256])
+@pytest.mark.parametrize("shape,K,mask,stride", _SHAPES)
+def test_slice_sums_in_slice_order(shape, K, mask, stride, S):
+    rng = np.random.default_rng(S)
+    order = np.array([1e16, 1.0, -1e16, 1.0])  # ((1e16 + 1) - 1e16) + 1 = 1, any other order gives 0 or 2
+    slices = np.full((S, stride), 1e300)  # (the columns behind K are never read: a sum that took them would overflow)
+    for k in range(K):
+        col = order[(np.arange(S) + k) % 4] if k % 2 == 0 else rng.standard_normal(S) * 10.0 ** rng.integers(-8, 8, S)
+        slices[:, k] = np.abs(col) if (mask >> k) & 1 else col
+    got = H.slice_sums(shape, slices, stride)
+    want = spec_slice_sums(slices, K, mask)
+    assert got.shape == (K,) and np.array_equal(got, want), (got, want)
+    if S == 256:  # the order matters for these values: 64 times (((x + 1e16) + 1) - 1e16) + 1 leaves 1, the reverse order 0
+        assert want[0] == 1.0 and spec_slice_sums(slices[::-1], K, mask)[0] == 0.0
+    for k in range(K):  # a maximum starts from 0.0 as well
+        if (mask >> k) & 1:
+            assert got[k] == max(0.0, slices[:, k].max())
+    neg = slices.copy()
+    neg[:, :K] = -np.abs(neg[:, :K])
+    assert all(H.slice_sums(shape, neg, stride)[k] == 0.0 for k in range(K) if (mask >> k) & 1)
+
+
+# ---- the header: reset and status mapping ----------------------------------------------------------------------------------------------
+OK, ERR_STATE, ERR_OVERFLOW = 0, 5, 3
+
+
+def test_status_codes_are_the_public_ones():
+    import re
+
+    text = open(os.path.join(H.ROOT, "include", "tmdnet_amd.h")).read()
+    for name, value in (("TMDNET_OK", OK), ("TMDNET_ERR_STATE", ERR_STATE), ("TMDNET_ERR_OVERFLOW", ERR_OVERFLOW)):
+        assert int(re.search(rf"{name}\s*=?\s*(-?\d+)", text).group(1)) == value
+
+
+@pytest.mark.parametrize("step", [0, 41, 2 ** 32 + 5, 2 ** 63 + 11])
+@pytest.mark.parametrize("cause_word", [-1, 4, 8])
+@pytest.mark.parametrize("status", [0, 1, 2, 7])
+def test_status_mapping(status, cause_word, step):
+    head = np.arange(100, 164, dtype=np.uint32)  # every word distinct: a wrong index shows
+    head[0], head[1], head[2] = step % 2 ** 32, step >> 32, status
+    want_rc = OK if status == 0 else ERR_OVERFLOW if status == 1 else ERR_STATE
+    cause = int(head[cause_word]) if status == 2 and cause_word >= 0 else 0
+    sentinel = 2 ** 64 - 1
+    assert H.status_result(head, cause_word, 3) == (want_rc, [step, status, cause])
+    assert H.status_result(head, cause_word, 2) == (want_rc, [step, status, sentinel])  # a two-word entry writes two words
+
+
+@pytest.mark.parametrize("cause_word", [-1, 4, 5, 8])
+def test_head_reset(cause_word):
+    before = np.arange(100, 164, dtype=np.uint32)
+    for step0 in (0, 2 ** 32 + 5):
+        after = H.head_reset(before, step0, cause_word)
+        want = before.copy()
+        want[0], want[1], want[2], want[3] = step0 % 2 ** 32, step0 >> 32, 0, 1
+        if cause_word >= 0:
+            want[cause_word] = 0
+        assert np.array_equal(after, want)  # and no other word
+        assert H.status_result(after, cause_word, 3) == (OK, [step0, 0, 0])
+
+
+# ---- the FIRE unit state ----------------------------------------------------------------------------------------------------------------
+def test_fire_load_fresh_and_not():
+    A = H.FireArrays(5)
+    for unit in range(5):
+        assert H.fire_load(A, unit, False) == (A.dt[unit], A.alpha[unit], int(A.n_pos[unit]), int(A.conv[unit]))
+        assert H.fire_load(A, unit, True) == (0.125, 0.75, 0, -1)  # the start values of the header, whatever the arrays hold
+
+
+@pytest.mark.parametrize("rows", [True, False])
+@pytest.mark.parametrize("energy", [None, -3.25])
+def test_fire_store_and_rows(rows, energy):
+    A = H.FireArrays(5, rows)
+    before, rows_before = A.state(), [None if r is None else r.copy() for r in A.rows]
+    unit, coef3, sums4 = 3, np.array([0.5, 0.25, 2.0], np.float32), np.array([1.5, 9.0, -2.0, 6.25])
+    H.fire_store(A, unit, 0.3, 0.07, 4, 12, coef3, energy, sums4, 2.25)  # (fmax2 need not be sums4[3]: the cell passes another)
+    others = np.arange(5) != unit
+    for a, b in zip(A.state(), before):
+        assert np.array_equal(a[others], b[others])  # only this unit
+    assert (A.dt[unit], A.alpha[unit], A.n_pos[unit], A.conv[unit]) == (0.3, 0.07, 4, 12) and np.array_equal(A.coef[unit], coef3)
+    if not rows:
+        return  # every row NULL: nothing but the state was written (and nothing was dereferenced)
+    for r, b in zip(A.rows, rows_before):
+        assert np.array_equal(r[others], b[others])
+    epot, fmax, sums, coef, dt, alpha, conv = (r[unit] for r in A.rows)
+    assert epot == (np.float32(energy) if energy is not None else -5)  # no energy: the row is left alone
+    assert fmax == np.float32(1.5) and np.array_equal(sums, sums4) and np.array_equal(coef, coef3)
+    assert (dt, alpha, conv) == (0.3, 0.07, 12)

@@ -43,6 +43,19 @@ def cases():
         for m, g in ((3, 1), (7, 3), (16, 300)):
             if n * m * g <= (2 ** 31 - 1) // 4:
                 out.append(("neb", (n, m, g)))
+    # the optimisers added since: one unit (a dimer, a path, a scan point, a walker) is the molecule; rows of 3 floats stay below 2^31
+    for n, b in _nb():
+        if b >= 1 and n * b <= (2 ** 31 - 1) // 16:
+            out.append(("dimer", (n, b)))
+            for capacity in (1, 4096):  # irc: its frames stay below 2^36 rows
+                if n * b * capacity <= 2 ** 36:
+                    out.append(("irc", (n, b, capacity)))
+            if n >= 1:
+                out.append(("scan", (n, b)))
+        if b >= 1 and 1 <= n <= (2 ** 31 - 1) // 4:
+            for capacity in (1, 64):  # hop: the rows of its ring stay below 2^31 floats
+                if n * capacity <= (2 ** 31 - 1) // 4:
+                    out.append(("hop", (n, b, capacity)))
     return out
 
 
@@ -59,6 +72,10 @@ _SIZE_ENTRIES = {
     "min_cell": "tmdnet_min_workspace_bytes_cell",
     "lbfgs": "tmdnet_lbfgs_workspace_bytes",
     "neb": "tmdnet_neb_workspace_bytes",
+    "dimer": "tmdnet_dimer_workspace_bytes",
+    "irc": "tmdnet_irc_workspace_bytes",
+    "scan": "tmdnet_scan_workspace_bytes",
+    "hop": "tmdnet_hop_workspace_bytes",
 }
 
 

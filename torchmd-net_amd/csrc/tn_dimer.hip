@@ -136,12 +136,12 @@ __device__ __forceinline__ void dimer_load(const DimerIn& in, const DimerGeom& g
   }
 }
 
-__device__ __forceinline__ bool dimer_live(const DimerState& st, int d) { return st.head[3] != 0 || st.conv[d] < 0; }
+__device__ __forceinline__ bool dimer_live(const DimerState& st, int d) { return st.head[kHeadFresh] != 0 || st.conv[d] < 0; }
 
 // grid (G, S): slice s of dimer d -> sum_slices[d, s, 0..N_SUMS)
 __global__ __launch_bounds__(kThreads) void k_dimer_sums(DimerState st, DimerGeom g, DimerIn in) {
   __shared__ double sh[N_SUMS][kThreads / 64];
-  if (st.head[2]) return;                 // frozen
+  if (st.head[kHeadStatus]) return;                 // frozen
   if (in.counts && in.counts[2]) return;  // overflowed: stale forces, the controller latches it
   const int d = blockIdx.x, s = blockIdx.y;
   if (!dimer_live(st, d)) return;  // a dimer that has converged looks at nothing
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void k_dimer_sums(DimerState st, DimerGeo
 __global__ __launch_bounds__(kThreads) void k_dimer_project(DimerState st, DimerGeom g, DimerIn in) {
   __shared__ double sh[kPartSlice][kThreads / 64];
   __shared__ double shn[1][kThreads / 64];
-  if (st.head[2]) return;
+  if (st.head[kHeadStatus]) return;
   if (in.counts && in.counts[2]) return;
   const int d = blockIdx.x, s = blockIdx.y;
   if (!dimer_live(st, d)) return;
@@ -259,13 +259,7 @@ struct DimerCtlArgs {
   tn_min::FireParams p;
   const int* counts;  // the graph's counters, or NULL
   const float* energy;
-  float* epot_row;      // [G]
-  float* fmax_row;      // [G]
-  double* sums_row;     // [G, 4]
-  float* coef_row;      // [G, 3]
-  double* dt_row;       // [G]
-  double* alpha_row;    // [G]
-  int64_t* conv_row;    // [G]
+  FireRows rows;        // [G, ...]
   double* curv_row;     // [G]
   double* rot_row;      // [G, 2]
   double* resid_row;    // [G]
@@ -276,124 +270,69 @@ struct DimerCtlArgs {
 };
 
 // the sums of dimer d in slice order (FIRE's four, then the partner's), and its state (after a reset: the start values of the header)
-__device__ __forceinline__ void dimer_ctl_load(const DimerCtlArgs& a, int d, bool fresh, double sums[4], double P[N_PART],
-                                               tn_min::FireState* s) {
-  sums[0] = sums[1] = sums[2] = sums[3] = 0.0;
-#pragma unroll
-  for (int k = 0; k < N_PART; ++k) P[k] = 0.0;
-  const double* sl = a.st.part_slices + (int64_t)d * a.g.S * kPartSlice;
-  for (int k = 0; k < a.g.S; ++k) {
-    sums[0] += sl[k * kPartSlice + 0];
-    sums[1] += sl[k * kPartSlice + 1];
-    sums[2] += sl[k * kPartSlice + 2];
-    sums[3] = sl[k * kPartSlice + 3] > sums[3] ? sl[k * kPartSlice + 3] : sums[3];
-#pragma unroll
-    for (int j = 0; j < N_PART; ++j) P[j] += sl[k * kPartSlice + 4 + j];
-  }
-  if (fresh) {
-    s->dt = a.st.start[0];
-    s->alpha = a.st.start[1];
-    s->n_pos = 0;
-    s->converged_at = -1;
-  } else {
-    s->dt = a.st.dt[d];
-    s->alpha = a.st.alpha[d];
-    s->n_pos = a.st.n_pos[d];
-    s->converged_at = a.st.conv[d];
-  }
+__device__ __forceinline__ void dimer_ctl_load(const DimerCtlArgs& a, int d, bool fresh, double sums[kPartSlice], tn_min::FireState* s) {
+  slice_sums<kPartSlice, 8u>(a.st.part_slices + (int64_t)d * a.g.S * kPartSlice, a.g.S, kPartSlice, sums);
+  fire_load(fire_units(a.st), d, fresh, s);
 }
 
-// ONE block striding the dimers, after k_dimer_project.  Pass 1: is any dimer that still moves unusable?  Pass 2, only when none
-// is: every dimer's state, coefficients and log rows; then thread 0 advances the step counter.
+// ONE block striding the dimers, after k_dimer_project: optimiser_control (tn_loop.h) with FIRE's two passes on F_eff and the
+// projection's causes
 __global__ __launch_bounds__(kThreads) void k_dimer_control(DimerCtlArgs a) {
-  __shared__ int bad;
-  if (a.st.head[2]) return;  // frozen
-  if (a.counts && a.counts[2]) {
-    if (threadIdx.x == 0) a.st.head[2] = 1u;
-    return;
-  }
-  const bool fresh = a.st.head[3] != 0;
-  const int translate = a.st.head[kDimerTranslateWord] != 0;
-  const uint64_t step = loop_step(a.st.head) + (fresh ? 0 : 1);
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();  // (every thread has read the header by now: thread 0 rewrites it at the end)
-  int cause = 0;
-  double sums[4], P[N_PART];
-  float coef[3];
-  tn_min::FireState s;
-  for (int d = threadIdx.x; d < a.g.G; d += kThreads) {
-    dimer_ctl_load(a, d, fresh, sums, P, &s);
-    if (s.converged_at >= 0) continue;  // a dimer that has converged looks at nothing
-    int c = a.st.why[d];
-    const int has_free = a.st.msums[(int64_t)d * N_SUMS + S_FREE] > 0.0;
-    if (!c && dimer_fire(&s, a.p, sums, a.st.rec[(int64_t)d * kRec + 6], translate, has_free, (int64_t)step, coef) == tn_min::FIRE_UNUSABLE)
-      c = DIMER_BAD_SUMS;
-    cause = c > cause ? c : cause;
-  }
-  if (cause) atomicMax(&bad, cause);  // (an integer in LDS)
-  __syncthreads();
-  if (bad) {
-    if (threadIdx.x == 0) {
-      a.st.head[kDimerCauseWord] = (uint32_t)bad;
-      a.st.head[2] = 2u;
-    }
-    return;
-  }
-  for (int d = threadIdx.x; d < a.g.G; d += kThreads) {
-    dimer_ctl_load(a, d, fresh, sums, P, &s);
-    double* rec = a.st.rec + (int64_t)d * kRec;
-    float* mc = a.st.mcoef + (int64_t)d * N_COEF;
-    if (s.converged_at < 0) {  // (a dimer that had converged keeps the records of the step it converged at)
-      const int has_free = a.st.msums[(int64_t)d * N_SUMS + S_FREE] > 0.0;
-      partner_coef(P, has_free, mc, &rec[8]);
+  const int translate = a.st.head[kDimerTranslateWord] != 0;  // (no controller writes this word)
+  optimiser_control(
+      a.st.head, a.counts, kDimerCauseWord, true, a.g.G,
+      [&](int d, bool fresh, uint64_t step) {
+        double sums[kPartSlice];
+        float coef[3];
+        tn_min::FireState s;
+        dimer_ctl_load(a, d, fresh, sums, &s);
+        if (s.converged_at >= 0) return 0;  // a dimer that has converged looks at nothing
+        int c = a.st.why[d];
+        const int has_free = a.st.msums[(int64_t)d * N_SUMS + S_FREE] > 0.0;
+        if (!c && dimer_fire(&s, a.p, sums, a.st.rec[(int64_t)d * kRec + 6], translate, has_free, (int64_t)step, coef) == tn_min::FIRE_UNUSABLE)
+          c = DIMER_BAD_SUMS;
+        return c;
+      },
+      [&](int d, bool fresh, uint64_t step) {
+        double sums[kPartSlice];
+        const double* P = sums + 4;
+        float coef[3];
+        tn_min::FireState s;
+        dimer_ctl_load(a, d, fresh, sums, &s);
+        double* rec = a.st.rec + (int64_t)d * kRec;
+        float* mc = a.st.mcoef + (int64_t)d * N_COEF;
+        if (s.converged_at < 0) {  // (a dimer that had converged keeps the records of the step it converged at)
+          const int has_free = a.st.msums[(int64_t)d * N_SUMS + S_FREE] > 0.0;
+          partner_coef(P, has_free, mc, &rec[8]);
 #pragma unroll
-      for (int k = 0; k < N_PART; ++k) a.st.psums[(int64_t)d * N_PART + k] = P[k];
-      dimer_fire(&s, a.p, sums, rec[6], translate, has_free, (int64_t)step, coef);
-    } else {
-      coef[0] = coef[1] = coef[2] = 0.f;
-    }
-    a.st.dt[d] = s.dt;
-    a.st.alpha[d] = s.alpha;
-    a.st.n_pos[d] = s.n_pos;
-    a.st.conv[d] = s.converged_at;
+          for (int k = 0; k < N_PART; ++k) a.st.psums[(int64_t)d * N_PART + k] = P[k];
+          dimer_fire(&s, a.p, sums, rec[6], translate, has_free, (int64_t)step, coef);
+        } else {
+          coef[0] = coef[1] = coef[2] = 0.f;
+        }
+        fire_store(fire_units(a.st), d, s, coef);
+        a.rows.write(d, a.energy + (int64_t)d * 3, sums, sums[3], coef, s);
+        if (a.curv_row) a.curv_row[d] = rec[6];
+        if (a.rot_row) {
+          a.rot_row[(int64_t)d * 2 + 0] = rec[3];
+          a.rot_row[(int64_t)d * 2 + 1] = rec[4];
+        }
+        if (a.resid_row) a.resid_row[d] = rec[8];
+        if (a.quad_row)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) a.st.coef[d * 3 + k] = coef[k];
-    if (a.epot_row) a.epot_row[d] = a.energy[(int64_t)d * 3];
-    if (a.fmax_row) a.fmax_row[d] = (float)sqrt(sums[3]);
-    if (a.sums_row)
+          for (int k = 0; k < 3; ++k) a.quad_row[(int64_t)d * 3 + k] = rec[k];
+        if (a.msums_row) {
+          double* row = a.msums_row + (int64_t)d * (N_SUMS + 1 + N_PART);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) a.sums_row[(int64_t)d * 4 + k] = sums[k];
-    if (a.coef_row)
+          for (int k = 0; k < N_SUMS; ++k) row[k] = a.st.msums[(int64_t)d * N_SUMS + k];
+          row[N_SUMS] = rec[5];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) a.coef_row[(int64_t)d * 3 + k] = coef[k];
-    if (a.dt_row) a.dt_row[d] = s.dt;
-    if (a.alpha_row) a.alpha_row[d] = s.alpha;
-    if (a.conv_row) a.conv_row[d] = s.converged_at;
-    if (a.curv_row) a.curv_row[d] = rec[6];
-    if (a.rot_row) {
-      a.rot_row[(int64_t)d * 2 + 0] = rec[3];
-      a.rot_row[(int64_t)d * 2 + 1] = rec[4];
-    }
-    if (a.resid_row) a.resid_row[d] = rec[8];
-    if (a.quad_row)
+          for (int k = 0; k < N_PART; ++k) row[N_SUMS + 1 + k] = a.st.psums[(int64_t)d * N_PART + k];
+        }
+        if (a.mcoef_row)
 #pragma unroll
-      for (int k = 0; k < 3; ++k) a.quad_row[(int64_t)d * 3 + k] = rec[k];
-    if (a.msums_row) {
-      double* row = a.msums_row + (int64_t)d * (N_SUMS + 1 + N_PART);
-#pragma unroll
-      for (int k = 0; k < N_SUMS; ++k) row[k] = a.st.msums[(int64_t)d * N_SUMS + k];
-      row[N_SUMS] = rec[5];
-#pragma unroll
-      for (int k = 0; k < N_PART; ++k) row[N_SUMS + 1 + k] = a.st.psums[(int64_t)d * N_PART + k];
-    }
-    if (a.mcoef_row)
-#pragma unroll
-      for (int k = 0; k < N_COEF; ++k) a.mcoef_row[(int64_t)d * N_COEF + k] = mc[k];
-  }
-  if (threadIdx.x == 0) {
-    loop_set_step(a.st.head, step);
-    a.st.head[3] = 0u;
-  }
+          for (int k = 0; k < N_COEF; ++k) a.mcoef_row[(int64_t)d * N_COEF + k] = mc[k];
+      });
 }
 
 struct DimerAtomArgs {
@@ -421,7 +360,7 @@ __global__ __launch_bounds__(kThreads) void k_dimer_atoms(DimerAtomArgs a) {
   if (r >= a.N) return;
   const int d = (int)(r / a.g.n), atom = (int)(r - (int64_t)d * a.g.n);
   const int64_t r0 = ((int64_t)d * 3) * a.g.n + atom, r1 = r0 + a.g.n, r2 = r1 + a.g.n;
-  const uint32_t status = a.st.head[2], fresh = a.st.head[3];
+  const uint32_t status = a.st.head[kHeadStatus], fresh = a.st.head[kHeadFresh];
   float x[3], v[3], f[3], N[3], M[3], xi[3];
   if (status) {
     if (ACCEPT && status == 1u && !fresh && a.counts && a.counts[2]) {
@@ -503,11 +442,8 @@ __global__ __launch_bounds__(kThreads) void k_dimer_atoms(DimerAtomArgs a) {
 
 __global__ void k_dimer_reset(DimerState st, uint64_t step0, double dt0, double alpha0, uint32_t translate) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    loop_set_step(st.head, step0);
-    st.head[2] = 0u;
-    st.head[3] = 1u;
+    loop_head_reset(st.head, step0, kDimerCauseWord);
     st.head[kDimerTranslateWord] = translate;
-    st.head[kDimerCauseWord] = 0u;
     st.start[0] = dt0;
     st.start[1] = alpha0;
   }
@@ -588,13 +524,7 @@ int tmdnet_dimer_advance(tmdnet_model* m, void* stream, void* graph_ws, void* di
     c.p.n_min = n_min;
     c.counts = counts;
     c.energy = energy;
-    c.epot_row = epot_log_row;
-    c.fmax_row = fmax_log_row;
-    c.sums_row = sums_log_row;
-    c.coef_row = coef_log_row;
-    c.dt_row = dt_log_row;
-    c.alpha_row = alpha_log_row;
-    c.conv_row = converged_log_row;
+    c.rows = {epot_log_row, fmax_log_row, sums_log_row, coef_log_row, dt_log_row, alpha_log_row, converged_log_row};
     c.curv_row = curvature_log_row;
     c.rot_row = rotation_log_row;
     c.resid_row = residual_log_row;
@@ -631,14 +561,7 @@ int tmdnet_dimer_advance(tmdnet_model* m, void* stream, void* graph_ws, void* di
 
 int tmdnet_dimer_status(void* stream, void* dimer_ws, uint64_t host[3]) {
   if (!dimer_ws || !host) return TMDNET_ERR_INVALID;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t head[kDimerHeadWords] = {0, 0, 0, 0, 0, 0};
-  if (hipMemcpyAsync(head, carve_dimer(dimer_ws, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = loop_step(head);
-  host[1] = head[2];
-  host[2] = head[2] == 2 ? head[kDimerCauseWord] : 0;
-  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
+  return loop_read_status(stream, carve_dimer(dimer_ws, 0, 0).head, kDimerHeadWords, kDimerCauseWord, host, 3);
 }
 
 }  // extern "C"

@@ -88,7 +88,7 @@ __device__ __forceinline__ Ring hop_ring(const HopArgs& h, int m) {
 // the other through the same 18, so the kernel's register need does not grow with the capacity.
 __global__ __launch_bounds__(kThreads) void k_hop_reduce(HopArgs h) {
   __shared__ double sh[kPair][kThreads / 64];
-  if (h.st.head[2]) return;               // frozen
+  if (h.st.head[kHeadStatus]) return;               // frozen
   if (h.counts && h.counts[2]) return;    // overflowed: stale forces, the controller latches it
   const int m = blockIdx.x, s = blockIdx.y, t = threadIdx.x;
   const Walker& w = h.st.walker[m];
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void k_hop_reduce(HopArgs h) {
 
 // grid (B), S > 1 only: tot[m, j] = the slices' entries j in slice order; entry 3 of QUENCH and MD takes the maximum
 __global__ __launch_bounds__(kThreads) void k_hop_finish(HopArgs h) {
-  if (h.st.head[2]) return;
+  if (h.st.head[kHeadStatus]) return;
   if (h.counts && h.counts[2]) return;
   const int m = blockIdx.x;
   const Walker& w = h.st.walker[m];
@@ -193,63 +193,50 @@ __global__ __launch_bounds__(kThreads) void k_hop_finish(HopArgs h) {
   }
 }
 
-// ONE block striding the walkers, after the reduction.  Pass 1: is any walker's step unusable?  Pass 2, only when none is: every
-// walker's state, decision, public state and log rows; then thread 0 advances the step counter.
+// ONE block striding the walkers, after the reduction: optimiser_control (tn_loop.h) without a fresh word - the counter always
+// advances - and without causes.  Pass 1: is any walker's step unusable?  Pass 2: every walker's state, decision, public state and
+// log rows.
 __global__ __launch_bounds__(kThreads) void k_hop_control(HopArgs h) {
-  __shared__ int bad;
-  if (h.st.head[2]) return;  // frozen
-  if (h.counts && h.counts[2]) {
-    if (threadIdx.x == 0) h.st.head[2] = 1u;
-    return;
-  }
-  const uint64_t step = loop_step(h.st.head) + 1;
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();  // (every thread has read the header by now: thread 0 rewrites it at the end)
-  int flag = 0;
-  for (int m = threadIdx.x; m < h.B; m += kThreads)
-    flag |= !walker_usable(h.st.walker[m], hop_ring(h, m), h.p, h.st.tot + (int64_t)m * h.W, (double)h.a.energy[m]);
-  if (flag) bad = 1;  // (every writer stores the same value)
-  __syncthreads();
-  if (bad) {
-    if (threadIdx.x == 0) h.st.head[2] = 2u;
-    return;
-  }
-  for (int m = threadIdx.x; m < h.B; m += kThreads) {
-    Walker w = h.st.walker[m];
-    Decision d;
-    double log[kSumsLog];
-    const double* tot = h.st.tot + (int64_t)m * h.W;
-    const double E = (double)h.a.energy[m];
-    walker_control(&w, hop_ring(h, m), h.p, tot, E, (int64_t)step, &d, log);
-    h.st.walker[m] = w;
-    h.st.dec[m] = d;
-    h.a.kT[m] = w.kT;
-    h.a.ediff[m] = w.ediff;
-    h.a.cur_energy[m] = w.e_cur;
-    h.a.best_energy[m] = w.e_best;
-    h.a.phase[m] = w.phase;
+  optimiser_control(
+      h.st.head, h.counts, -1, false, h.B,
+      [&](int m, bool, uint64_t) {
+        return (int)!walker_usable(h.st.walker[m], hop_ring(h, m), h.p, h.st.tot + (int64_t)m * h.W, (double)h.a.energy[m]);
+      },
+      [&](int m, bool, uint64_t step) {
+        Walker w = h.st.walker[m];
+        Decision d;
+        double log[kSumsLog];
+        const double* tot = h.st.tot + (int64_t)m * h.W;
+        const double E = (double)h.a.energy[m];
+        walker_control(&w, hop_ring(h, m), h.p, tot, E, (int64_t)step, &d, log);
+        h.st.walker[m] = w;
+        h.st.dec[m] = d;
+        h.a.kT[m] = w.kT;
+        h.a.ediff[m] = w.ediff;
+        h.a.cur_energy[m] = w.e_cur;
+        h.a.best_energy[m] = w.e_best;
+        h.a.phase[m] = w.phase;
 #pragma unroll
-    for (int k = 0; k < kCounters; ++k) h.a.counters[(int64_t)m * kCounters + k] = w.n[k];
-    if (h.a.epot_row) h.a.epot_row[m] = h.a.energy[m];
-    if (h.a.fmax_row) h.a.fmax_row[m] = d.phase == PH_QUENCH || d.phase == PH_MD ? (float)sqrt(tot[3]) : 0.f;
-    if (h.a.ekin_row) h.a.ekin_row[m] = d.phase == PH_MD ? (float)tot[0] : 0.f;
-    if (h.a.phase_row) h.a.phase_row[m] = d.phase;
-    if (h.a.outcome_row) h.a.outcome_row[m] = d.outcome;
-    if (h.a.sums_row)
+        for (int k = 0; k < kCounters; ++k) h.a.counters[(int64_t)m * kCounters + k] = w.n[k];
+        if (h.a.epot_row) h.a.epot_row[m] = h.a.energy[m];
+        if (h.a.fmax_row) h.a.fmax_row[m] = d.phase == PH_QUENCH || d.phase == PH_MD ? (float)sqrt(tot[3]) : 0.f;
+        if (h.a.ekin_row) h.a.ekin_row[m] = d.phase == PH_MD ? (float)tot[0] : 0.f;
+        if (h.a.phase_row) h.a.phase_row[m] = d.phase;
+        if (h.a.outcome_row) h.a.outcome_row[m] = d.outcome;
+        if (h.a.sums_row)
 #pragma unroll
-      for (int k = 0; k < kSumsLog; ++k) h.a.sums_row[(int64_t)m * kSumsLog + k] = log[k];
-    if (h.a.coef_row) {
-      float* c = h.a.coef_row + (int64_t)m * kCoefLog;
+          for (int k = 0; k < kSumsLog; ++k) h.a.sums_row[(int64_t)m * kSumsLog + k] = log[k];
+        if (h.a.coef_row) {
+          float* c = h.a.coef_row + (int64_t)m * kCoefLog;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        c[k] = d.coef[k];
-        c[3 + k] = d.u[k];
-        c[6 + k] = d.w[k];
-      }
-      c[9] = d.vscale;
-    }
-  }
-  if (threadIdx.x == 0) loop_set_step(h.st.head, step);
+          for (int k = 0; k < 3; ++k) {
+            c[k] = d.coef[k];
+            c[3 + k] = d.u[k];
+            c[6 + k] = d.w[k];
+          }
+          c[9] = d.vscale;
+        }
+      });
 }
 
 // One thread per atom, the caller's atom order, after k_hop_control: keep the forces of the evaluation, save x and v, then
@@ -258,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void k_hop_control(HopArgs h) {
 __global__ __launch_bounds__(kThreads) void k_hop_move(HopArgs h) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= h.N) return;
-  const uint32_t status = h.st.head[2];
+  const uint32_t status = h.st.head[kHeadStatus];
   if (status) {
     if (status == 1u && h.counts && h.counts[2]) {
 #pragma unroll
@@ -316,7 +303,7 @@ __global__ __launch_bounds__(kThreads) void k_hop_reset(HopResetArgs r) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i == 0) {
     loop_set_step(r.st.head, r.step0);
-    r.st.head[2] = 0u;
+    r.st.head[kHeadStatus] = 0u;
   }
   if (i < r.B) {
     Walker w = r.st.walker[i];
@@ -428,13 +415,7 @@ int tmdnet_hop_advance(tmdnet_model* m, void* stream, void* graph_ws, void* hop_
 
 int tmdnet_hop_status(void* stream, void* hop_ws, uint64_t host[2]) {
   if (!hop_ws || !host) return TMDNET_ERR_INVALID;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t head[3] = {0, 0, 0};
-  if (hipMemcpyAsync(head, carve_hop(hop_ws, 0, 0, 1).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = loop_step(head);
-  host[1] = head[2];
-  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
+  return loop_read_status(stream, carve_hop(hop_ws, 0, 0, 1).head, 3, -1, host, 2);
 }
 
 }  // extern "C"

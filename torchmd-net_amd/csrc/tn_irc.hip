@@ -115,16 +115,16 @@ struct IrcIn {  // what the sums read
 };
 
 // a path is looked at while it moves (after a reset every path does)
-__device__ __forceinline__ bool irc_live(const IrcState& st, int p) { return st.head[3] != 0 || st.conv[p] < 0; }
+__device__ __forceinline__ bool irc_live(const IrcState& st, int p) { return st.head[kHeadFresh] != 0 || st.conv[p] < 0; }
 
 // grid (P, S): slice s of path p -> slices[p, s, 0..N_SUMS), all six entries from one pass over the atoms
 __global__ __launch_bounds__(kThreads) void k_irc_sums(IrcState st, IrcGeom g, IrcIn in) {
   __shared__ double sh[N_SUMS][kThreads / 64];
-  if (st.head[2]) return;                 // frozen
+  if (st.head[kHeadStatus]) return;                 // frozen
   if (in.counts && in.counts[2]) return;  // overflowed: stale forces, the controller latches it
   const int p = blockIdx.x, s = blockIdx.y;
   if (!irc_live(st, p)) return;  // a path that has finished looks at nothing
-  const bool fresh = st.head[3] != 0;
+  const bool fresh = st.head[kHeadFresh] != 0;
   const float dt = fresh ? 0.f : (float)st.dt[p];
   const int has2 = !fresh && st.n_acc[p] >= 1;
   const float T = has2 ? md_add(st.dt_used[p], dt) : 0.f;
@@ -181,18 +181,7 @@ struct IrcCtlArgs {
 
 // the sums of path p in slice order, and its state (after a reset: the start values)
 __device__ __forceinline__ void irc_ctl_load(const IrcCtlArgs& a, int p, bool fresh, double sums[N_SUMS], IrcPath* s) {
-#pragma unroll
-  for (int k = 0; k < N_SUMS; ++k) sums[k] = 0.0;
-  const double* sl = a.st.slices + (int64_t)p * a.g.S * N_SUMS;
-  for (int k = 0; k < a.g.S; ++k)
-#pragma unroll
-    for (int j = 0; j < N_SUMS; ++j) {
-      const double v = sl[k * N_SUMS + j];
-      if (j == S_FMAX2)
-        sums[j] = v > sums[j] ? v : sums[j];
-      else
-        sums[j] += v;
-    }
+  slice_sums<N_SUMS, kMaxMask>(a.st.slices + (int64_t)p * a.g.S * N_SUMS, a.g.S, N_SUMS, sums);
   if (fresh) {
     s->dt = a.st.start[0];
     s->arc = 0.0;
@@ -210,78 +199,61 @@ __device__ __forceinline__ void irc_ctl_load(const IrcCtlArgs& a, int p, bool fr
   }
 }
 
-// ONE block striding the paths, after k_irc_sums.  Pass 1: is any path that still moves unusable?  Pass 2, only when none is:
-// every path's state, coefficients, frame slot and log rows; then thread 0 advances the step counter.
+// ONE block striding the paths, after k_irc_sums: optimiser_control (tn_loop.h).  Pass 1: is any path that still moves unusable?
+// Pass 2: every path's state, coefficients, frame slot and log rows.
 __global__ __launch_bounds__(kThreads) void k_irc_control(IrcCtlArgs a) {
-  __shared__ int bad;
-  if (a.st.head[2]) return;  // frozen
-  if (a.counts && a.counts[2]) {
-    if (threadIdx.x == 0) a.st.head[2] = 1u;
-    return;
-  }
-  const bool fresh = a.st.head[3] != 0;
-  const uint64_t step = loop_step(a.st.head) + (fresh ? 0 : 1);
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();  // (every thread has read the header by now: thread 0 rewrites it at the end)
-  int worst = 0, slot, cause;
-  double sums[N_SUMS];
-  float out[2];
-  IrcPath s;
-  for (int p = threadIdx.x; p < a.g.P; p += kThreads) {
-    irc_ctl_load(a, p, fresh, sums, &s);
-    if (irc_control(&s, a.p, sums, a.energy[p], fresh, (int64_t)step, out, &slot, &cause) == IRC_UNUSABLE) worst = cause > worst ? cause : worst;
-  }
-  if (worst) atomicMax(&bad, worst);  // (an integer in LDS)
-  __syncthreads();
-  if (bad) {
-    if (threadIdx.x == 0) {
-      a.st.head[kIrcCauseWord] = (uint32_t)bad;
-      a.st.head[2] = 2u;
-    }
-    return;
-  }
-  for (int p = threadIdx.x; p < a.g.P; p += kThreads) {
-    irc_ctl_load(a, p, fresh, sums, &s);
-    double* rec = a.st.rec + (int64_t)p * N_SUMS;
-    if (irc_control(&s, a.p, sums, a.energy[p], fresh, (int64_t)step, out, &slot, &cause) != IRC_FROZEN) {
-      a.st.damp[p] = out[0];
-      a.st.dt_used[p] = out[1];
+  optimiser_control(
+      a.st.head, a.counts, kIrcCauseWord, true, a.g.P,
+      [&](int p, bool fresh, uint64_t step) {
+        int slot, cause;
+        double sums[N_SUMS];
+        float out[2];
+        IrcPath s;
+        irc_ctl_load(a, p, fresh, sums, &s);
+        return irc_control(&s, a.p, sums, a.energy[p], fresh, (int64_t)step, out, &slot, &cause) == IRC_UNUSABLE ? cause : 0;
+      },
+      [&](int p, bool fresh, uint64_t step) {
+        int slot, cause;
+        double sums[N_SUMS];
+        float out[2];
+        IrcPath s;
+        irc_ctl_load(a, p, fresh, sums, &s);
+        double* rec = a.st.rec + (int64_t)p * N_SUMS;
+        if (irc_control(&s, a.p, sums, a.energy[p], fresh, (int64_t)step, out, &slot, &cause) != IRC_FROZEN) {
+          a.st.damp[p] = out[0];
+          a.st.dt_used[p] = out[1];
 #pragma unroll
-      for (int k = 0; k < N_SUMS; ++k) rec[k] = sums[k];
-      if (slot >= 0) {
-        a.st.frame_s[(int64_t)p * a.g.C + slot] = s.arc;
-        a.st.frame_e[(int64_t)p * a.g.C + slot] = a.energy[p];
-      }
-    }  // (a path that had finished keeps the records of the step it finished at)
-    a.st.slot[p] = slot;
-    a.st.dt[p] = s.dt;
-    a.st.arc[p] = s.arc;
-    a.st.conv[p] = s.converged_at;
-    a.st.reason[p] = s.reason;
-    a.st.n_acc[p] = s.n_acc;
-    a.st.n_rec[p] = s.n_rec;
-    if (a.epot_row) a.epot_row[p] = a.energy[p];
-    if (a.fmax_row) a.fmax_row[p] = (float)sqrt(rec[S_FMAX2]);
-    if (a.sums_row)
+          for (int k = 0; k < N_SUMS; ++k) rec[k] = sums[k];
+          if (slot >= 0) {
+            a.st.frame_s[(int64_t)p * a.g.C + slot] = s.arc;
+            a.st.frame_e[(int64_t)p * a.g.C + slot] = a.energy[p];
+          }
+        }  // (a path that had finished keeps the records of the step it finished at)
+        a.st.slot[p] = slot;
+        a.st.dt[p] = s.dt;
+        a.st.arc[p] = s.arc;
+        a.st.conv[p] = s.converged_at;
+        a.st.reason[p] = s.reason;
+        a.st.n_acc[p] = s.n_acc;
+        a.st.n_rec[p] = s.n_rec;
+        if (a.epot_row) a.epot_row[p] = a.energy[p];
+        if (a.fmax_row) a.fmax_row[p] = (float)sqrt(rec[S_FMAX2]);
+        if (a.sums_row)
 #pragma unroll
-      for (int k = 0; k < N_SUMS; ++k) a.sums_row[(int64_t)p * N_SUMS + k] = rec[k];
-    if (a.coef_row) {
-      a.coef_row[(int64_t)p * 2 + 0] = a.st.damp[p];
-      a.coef_row[(int64_t)p * 2 + 1] = a.st.dt_used[p];
-    }
-    if (a.dt_row) a.dt_row[p] = s.dt;
-    if (a.arc_row) a.arc_row[p] = s.arc;
-    if (a.power_row) a.power_row[p] = rec[S_P];
-    if (a.conv_out) a.conv_out[p] = s.converged_at;
-    if (a.reason_out) a.reason_out[p] = s.reason;
-    if (a.dt_out) a.dt_out[p] = s.dt;
-    if (a.arc_out) a.arc_out[p] = s.arc;
-    if (a.n_rec_out) a.n_rec_out[p] = s.n_rec;
-  }
-  if (threadIdx.x == 0) {
-    loop_set_step(a.st.head, step);
-    a.st.head[3] = 0u;
-  }
+          for (int k = 0; k < N_SUMS; ++k) a.sums_row[(int64_t)p * N_SUMS + k] = rec[k];
+        if (a.coef_row) {
+          a.coef_row[(int64_t)p * 2 + 0] = a.st.damp[p];
+          a.coef_row[(int64_t)p * 2 + 1] = a.st.dt_used[p];
+        }
+        if (a.dt_row) a.dt_row[p] = s.dt;
+        if (a.arc_row) a.arc_row[p] = s.arc;
+        if (a.power_row) a.power_row[p] = rec[S_P];
+        if (a.conv_out) a.conv_out[p] = s.converged_at;
+        if (a.reason_out) a.reason_out[p] = s.reason;
+        if (a.dt_out) a.dt_out[p] = s.dt;
+        if (a.arc_out) a.arc_out[p] = s.arc;
+        if (a.n_rec_out) a.n_rec_out[p] = s.n_rec;
+      });
 }
 
 struct IrcAtomArgs {
@@ -306,7 +278,7 @@ __global__ __launch_bounds__(kThreads) void k_irc_atoms(IrcAtomArgs a) {
   if (i >= a.N) return;
   const int p = (int)(i / a.g.n), atom = (int)(i - (int64_t)p * a.g.n);
   const int64_t r = i * 3;
-  const uint32_t status = a.st.head[2], fresh = a.st.head[3];
+  const uint32_t status = a.st.head[kHeadStatus], fresh = a.st.head[kHeadFresh];
   if (status) {
     if (ACCEPT && !fresh && a.st.conv[p] < 0) {  // the step was opened and then refused: back to where it began
 #pragma unroll
@@ -368,10 +340,7 @@ __global__ __launch_bounds__(kThreads) void k_irc_atoms(IrcAtomArgs a) {
 
 __global__ void k_irc_reset(IrcState st, uint64_t step0, double dt0) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    loop_set_step(st.head, step0);
-    st.head[2] = 0u;
-    st.head[3] = 1u;
-    st.head[kIrcCauseWord] = 0u;
+    loop_head_reset(st.head, step0, kIrcCauseWord);
     st.start[0] = dt0;
   }
 }
@@ -485,14 +454,7 @@ int tmdnet_irc_advance(tmdnet_model* m, void* stream, void* graph_ws, void* irc_
 
 int tmdnet_irc_status(void* stream, void* irc_ws, uint64_t host[3]) {
   if (!irc_ws || !host) return TMDNET_ERR_INVALID;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t head[kIrcHeadWords] = {0, 0, 0, 0, 0};
-  if (hipMemcpyAsync(head, carve_irc(irc_ws, 0, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = loop_step(head);
-  host[1] = head[2];
-  host[2] = head[2] == 2 ? head[kIrcCauseWord] : 0;
-  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
+  return loop_read_status(stream, carve_irc(irc_ws, 0, 0, 0).head, kIrcHeadWords, kIrcCauseWord, host, 3);
 }
 
 }  // extern "C"

@@ -39,6 +39,8 @@ namespace {
 
 constexpr int kLbDotsThreads = 1024;  // sixteen waves share the h + 1 tasks of a slice
 constexpr int kLbCtlWaves = 4;  // molecules per block of the controller
+constexpr int kLbCopyWord = 4;  // header words 4, 5, 7: the copy of words 0, 1, 3 that the controller's blocks read
+constexpr int kLbCauseWord = 8; // the cause of status 2 (1: a sum)
 
 // doubles of LDS per wave of the controller: delta [2 M1 + 1], av [M1] and the ring order as M1 int32 (<= 57 504 B per block at memory 512)
 __host__ __device__ inline size_t lb_ctl_doubles(int M1) { return (size_t)(3 * M1 + 1) + (size_t)(M1 + 1) / 2; }
@@ -107,16 +109,16 @@ __global__ __launch_bounds__(kLbDotsThreads) void k_lbfgs_dots(LbState st, const
                                                            const int* __restrict__ mend, int N, int B, int S, int M1,
                                                            const int64_t* __restrict__ batch, const float* __restrict__ pos,
                                                            const float* __restrict__ forces, const uint8_t* __restrict__ fixed) {
-  if (st.head[2]) return;  // frozen
+  if (st.head[kHeadStatus]) return;  // frozen
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
     // what the controller's blocks read of the header: block 0 of them rewrites the header itself while others may still start
-    st.head[4] = st.head[0];
-    st.head[5] = st.head[1];
-    st.head[7] = st.head[3];
+    st.head[kLbCopyWord + kHeadStepLo] = st.head[kHeadStepLo];
+    st.head[kLbCopyWord + kHeadStepHi] = st.head[kHeadStepHi];
+    st.head[kLbCopyWord + kHeadFresh] = st.head[kHeadFresh];
   }
   if (counts && counts[2]) return;  // overflowed: stale forces, the controller latches it
   const int m = blockIdx.x, s = blockIdx.y;
-  const bool fresh = st.head[3] != 0;
+  const bool fresh = st.head[kHeadFresh] != 0;
   const bool moved = !fresh && st.conv[m] < 0;  // a move preceded this evaluation: there is a candidate
   const int h = moved ? st.h[m] : 0;
   const int32_t* order = st.order + (int64_t)m * M1;
@@ -231,13 +233,13 @@ __device__ __forceinline__ tn_lbfgs::MolState lb_mol(const LbState& st, int m, i
 __global__ __launch_bounds__(64 * kLbCtlWaves) void k_lbfgs_control(LbCtlArgs a) {
   extern __shared__ double lds[];
   const LbState& st = a.st;
-  if (st.head[2]) return;  // frozen (or latched by block 0 a moment ago: the same outcome)
+  if (st.head[kHeadStatus]) return;  // frozen (or latched by block 0 a moment ago: the same outcome)
   if (a.counts && a.counts[2]) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) st.head[2] = 1u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) st.head[kHeadStatus] = 1u;
     return;
   }
-  const bool fresh = st.head[7] != 0;
-  const uint64_t step = loop_step(st.head + 4) + (fresh ? 0 : 1);
+  const bool fresh = st.head[kLbCopyWord + kHeadFresh] != 0;
+  const uint64_t step = loop_step(st.head + kLbCopyWord) + (fresh ? 0 : 1);
   const int M1 = a.p.memory + 1, NP = 6 * M1 + 4;
   int flag = 0;
   for (int m = threadIdx.x; m < a.B; m += blockDim.x) {
@@ -255,8 +257,8 @@ __global__ __launch_bounds__(64 * kLbCtlWaves) void k_lbfgs_control(LbCtlArgs a)
   }
   if (__syncthreads_or(flag)) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-      st.head[8] = 1u;
-      st.head[2] = 2u;
+      st.head[kLbCauseWord] = 1u;
+      st.head[kHeadStatus] = 2u;
     }
     return;
   }
@@ -313,7 +315,7 @@ __global__ __launch_bounds__(64 * kLbCtlWaves) void k_lbfgs_control(LbCtlArgs a)
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     loop_set_step(st.head, step);
-    st.head[3] = 0u;
+    st.head[kHeadFresh] = 0u;
   }
 }
 
@@ -323,7 +325,7 @@ __global__ __launch_bounds__(kThreads) void k_lbfgs_direction(LbState st, const 
                                                                 const int64_t* __restrict__ batch, const float* __restrict__ forces,
                                                                 const uint8_t* __restrict__ fixed, float* __restrict__ direction) {
   __shared__ double sh[1][kThreads / 64];
-  if (st.head[2]) return;  // frozen (an overflow: the controller has just latched it)
+  if (st.head[kHeadStatus]) return;  // frozen (an overflow: the controller has just latched it)
   const int m = blockIdx.x, s = blockIdx.y;
   if (st.conv[m] >= 0) return;  // converged: it never moves again
   const int h = st.h[m];
@@ -373,7 +375,7 @@ __device__ __forceinline__ float lb_scale(const LbAtomArgs& a, int64_t m) {
 template <bool ACCEPT, bool MOVE>
 __global__ __launch_bounds__(kThreads) void k_lbfgs_move(LbAtomArgs a) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
-  const uint32_t status = a.st.head[2], fresh = a.st.head[3];
+  const uint32_t status = a.st.head[kHeadStatus], fresh = a.st.head[kHeadFresh];
   if (status) {
     // the evaluation before this launch overflowed (the controller has just latched it): back to the last completed step.  A
     // later launch that finds the flag still set writes the same values again; nothing was ever saved before the first control.
@@ -412,10 +414,7 @@ __global__ __launch_bounds__(kThreads) void k_lbfgs_move(LbAtomArgs a) {
 
 __global__ void k_lbfgs_reset(LbState st, uint64_t step0) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    loop_set_step(st.head, step0);
-    st.head[2] = 0u;
-    st.head[3] = 1u;
-    st.head[8] = 0u;
+    loop_head_reset(st.head, step0, kLbCauseWord);
   }
 }
 
@@ -525,14 +524,7 @@ int tmdnet_lbfgs_advance(tmdnet_model* m, void* stream, void* graph_ws, void* lb
 
 int tmdnet_lbfgs_status(void* stream, void* lbfgs_ws, uint64_t host[3]) {
   if (!lbfgs_ws || !host) return TMDNET_ERR_INVALID;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t head[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipMemcpyAsync(head, carve_lb(lbfgs_ws, 0, 0, 1).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = loop_step(head);
-  host[1] = head[2];
-  host[2] = head[2] == 2 ? head[8] : 0;
-  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
+  return loop_read_status(stream, carve_lb(lbfgs_ws, 0, 0, 1).head, kLbCauseWord + 1, kLbCauseWord, host, 3);
 }
 
 }  // extern "C"

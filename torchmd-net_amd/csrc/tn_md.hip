@@ -59,7 +59,7 @@ template <bool CLOSE, bool OPEN>
 __global__ __launch_bounds__(kThreads) void k_md_atoms(MdArgs a) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= a.N) return;
-  if (a.st.head[2]) return;  // frozen since an earlier overflow
+  if (a.st.head[kHeadStatus]) return;  // frozen since an earlier overflow
   float x[3], v[3], f[3];
   if (CLOSE && a.counts && a.counts[2]) {  // this evaluation overflowed: back to the last completed step
 #pragma unroll
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(kThreads) void k_md_atoms(MdArgs a) {
 __global__ void k_md_reset(MdState st, uint64_t step0) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     loop_set_step(st.head, step0);
-    st.head[2] = 0u;
+    st.head[kHeadStatus] = 0u;
   }
 }
 
@@ -160,7 +160,7 @@ template <bool OPEN>
 __global__ __launch_bounds__(kThreads) void k_md_scale(ScaleArgs a) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= a.N) return;
-  if (a.st.head[2]) return;  // overflow (1) or an unusable move (2): k_md_baro wrote no factors
+  if (a.st.head[kHeadStatus]) return;  // overflow (1) or an unusable move (2): k_md_baro wrote no factors
   const int64_t m = a.batch ? a.batch[i] : 0;
   if (m < 0 || m >= a.B) return;
   const float mu = a.factors[m], nu = a.factors[a.B + m];
@@ -313,13 +313,7 @@ int tmdnet_md_barostat(tmdnet_model* m, void* stream, void* graph_ws, void* md_w
 
 int tmdnet_md_status(void* stream, void* md_ws, uint64_t host[2]) {
   if (!md_ws || !host) return TMDNET_ERR_INVALID;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t head[3] = {0, 0, 0};
-  if (hipMemcpyAsync(head, carve_md(md_ws, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = loop_step(head);
-  host[1] = head[2];
-  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
+  return loop_read_status(stream, carve_md(md_ws, 0, 0).head, 3, -1, host, 2);
 }
 
 }  // extern "C"

@@ -114,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void k_min_reduce(MinState st, const floa
                                                          const int64_t* __restrict__ batch, const float* __restrict__ vel,
                                                          const float* __restrict__ forces, const uint8_t* __restrict__ fixed) {
   __shared__ double sh[4][kThreads / 64];
-  if (st.head[2]) return;           // frozen
+  if (st.head[kHeadStatus]) return;           // frozen
   if (counts && counts[2]) return;  // overflowed: stale forces, the controller latches it
   const int m = blockIdx.x, s = blockIdx.y;
   const SliceRange r = mol_slice_range(counts, mstart, mend, N, S, batch, m, s);
@@ -152,92 +152,38 @@ struct MinCtlArgs {
   tn_min::FireParams p;
   const int* counts;  // the graph's counters, or NULL
   const float* energy;
-  float* epot_row;
-  float* fmax_row;
-  double* sums_row;  // [B, 4]
-  float* coef_row;   // [B, 3]
-  double* dt_row;
-  double* alpha_row;
-  int64_t* conv_row;
+  FireRows rows;
   MinState st;
 };
 
 // the sums of molecule m (slices in slice order) and its state (after a reset: the start values of the header)
 __device__ __forceinline__ void min_load(const MinCtlArgs& a, int m, bool fresh, double sums[4], tn_min::FireState* s) {
-  const double* sl = a.st.slices + (int64_t)m * a.S * 4;
-  sums[0] = sums[1] = sums[2] = sums[3] = 0.0;
-  for (int k = 0; k < a.S; ++k) {
-    sums[0] += sl[k * 4 + 0];
-    sums[1] += sl[k * 4 + 1];
-    sums[2] += sl[k * 4 + 2];
-    sums[3] = sl[k * 4 + 3] > sums[3] ? sl[k * 4 + 3] : sums[3];
-  }
-  if (fresh) {
-    s->dt = a.st.start[0];
-    s->alpha = a.st.start[1];
-    s->n_pos = 0;
-    s->converged_at = -1;
-  } else {
-    s->dt = a.st.dt[m];
-    s->alpha = a.st.alpha[m];
-    s->n_pos = a.st.n_pos[m];
-    s->converged_at = a.st.conv[m];
-  }
+  slice_sums<4, 8u>(a.st.slices + (int64_t)m * a.S * 4, a.S, 4, sums);
+  fire_load(fire_units(a.st), m, fresh, s);
 }
 
-// ONE block striding the molecules, after k_min_reduce.  Pass 1: is any molecule's move unusable?  Pass 2, only when none is:
-// every molecule's state, coefficients and log rows; then thread 0 advances the step counter (the first control after a reset
-// belongs to the start geometry and counts no step).  The move is a function of what pass 1 read, so pass 2 evaluates it again.
+// ONE block striding the molecules, after k_min_reduce: optimiser_control (tn_loop.h) with FIRE's two passes
 __global__ __launch_bounds__(kThreads) void k_min_control(MinCtlArgs a) {
-  __shared__ int bad;
-  if (a.st.head[2]) return;  // frozen
-  if (a.counts && a.counts[2]) {
-    if (threadIdx.x == 0) a.st.head[2] = 1u;
-    return;
-  }
-  const bool fresh = a.st.head[3] != 0;
-  const uint64_t step = loop_step(a.st.head) + (fresh ? 0 : 1);
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();  // (every thread has read the header by now: thread 0 rewrites it at the end)
-  int flag = 0;
-  double sums[4];
-  float coef[3];
-  tn_min::FireState s;
-  for (int m = threadIdx.x; m < a.B; m += kThreads) {
-    min_load(a, m, fresh, sums, &s);
-    flag |= tn_min::fire_control(&s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef) == tn_min::FIRE_UNUSABLE;
-  }
-  if (flag) bad = 1;  // (every writer stores the same value)
-  __syncthreads();
-  if (bad) {
-    if (threadIdx.x == 0) a.st.head[2] = 2u;
-    return;
-  }
-  for (int m = threadIdx.x; m < a.B; m += kThreads) {
-    min_load(a, m, fresh, sums, &s);
-    tn_min::fire_control(&s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef);
-    a.st.dt[m] = s.dt;
-    a.st.alpha[m] = s.alpha;
-    a.st.n_pos[m] = s.n_pos;
-    a.st.conv[m] = s.converged_at;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a.st.coef[m * 3 + k] = coef[k];
-    if (a.energy && a.epot_row) a.epot_row[m] = a.energy[m];
-    if (a.fmax_row) a.fmax_row[m] = (float)sqrt(sums[3]);
-    if (a.sums_row)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) a.sums_row[(int64_t)m * 4 + k] = sums[k];
-    if (a.coef_row)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) a.coef_row[(int64_t)m * 3 + k] = coef[k];
-    if (a.dt_row) a.dt_row[m] = s.dt;
-    if (a.alpha_row) a.alpha_row[m] = s.alpha;
-    if (a.conv_row) a.conv_row[m] = s.converged_at;
-  }
-  if (threadIdx.x == 0) {
-    loop_set_step(a.st.head, step);
-    a.st.head[3] = 0u;
-  }
+  const auto control = [&](int m, bool fresh, uint64_t step, double sums[4], float coef[3], tn_min::FireState* s) {
+    min_load(a, m, fresh, sums, s);
+    return tn_min::fire_control(s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef);
+  };
+  optimiser_control(
+      a.st.head, a.counts, -1, true, a.B,
+      [&](int m, bool fresh, uint64_t step) {
+        double sums[4];
+        float coef[3];
+        tn_min::FireState s;
+        return (int)(control(m, fresh, step, sums, coef, &s) == tn_min::FIRE_UNUSABLE);
+      },
+      [&](int m, bool fresh, uint64_t step) {
+        double sums[4];
+        float coef[3];
+        tn_min::FireState s;
+        control(m, fresh, step, sums, coef, &s);
+        fire_store(fire_units(a.st), m, s, coef);
+        a.rows.write(m, a.energy ? a.energy + m : nullptr, sums, sums[3], coef, s);
+      });
 }
 
 struct MinAtomArgs {
@@ -258,7 +204,7 @@ template <bool ACCEPT, bool MOVE>
 __global__ __launch_bounds__(kThreads) void k_min_atoms(MinAtomArgs a) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= a.N) return;
-  const uint32_t status = a.st.head[2], fresh = a.st.head[3];
+  const uint32_t status = a.st.head[kHeadStatus], fresh = a.st.head[kHeadFresh];
   if (status) {
     // the evaluation before this launch overflowed (the controller has just latched it): back to the last completed step.  A
     // later launch that finds the flag still set writes the same values again; nothing was ever saved before the first control.
@@ -304,9 +250,7 @@ __global__ __launch_bounds__(kThreads) void k_min_atoms(MinAtomArgs a) {
 
 __global__ void k_min_reset(MinState st, uint64_t step0, double dt0, double alpha0) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    loop_set_step(st.head, step0);
-    st.head[2] = 0u;
-    st.head[3] = 1u;
+    loop_head_reset(st.head, step0, -1);
     st.start[0] = dt0;
     st.start[1] = alpha0;
   }
@@ -319,8 +263,8 @@ __global__ void k_min_reset(MinState st, uint64_t step0, double dt0, double alph
 // current positions were formed with, and `d32_prev`, which the positions before the last move were formed with.  A move (the
 // end of the controller in MIDDLE, k_min_cell_commit in OPEN) saves the current values, makes the prepared ones current and moves
 // d32 to d32_prev; the per-atom kernel then forms the generalised force with d32_prev and the new position with d32.
-// (MinCell and its layout: with MinState, above.)  head[8] (header byte 32): which sum or input was unusable when status 2 was
-// latched (tn_min::CELL_BAD_*)
+// (MinCell and its layout: with MinState, above.)
+constexpr int kMinCellCauseWord = 8;  // header byte 32: which sum or input was unusable when status 2 was latched (tn_min::CELL_BAD_*)
 
 struct MinCellCtlArgs {
   MinCtlArgs base;
@@ -377,14 +321,12 @@ __device__ __forceinline__ void min_cell_eval(const MinCellCtlArgs& a, int m, bo
                                 o->stress, o->Dn, o->VDn, o->boxn, o->d32n, &o->why);
 }
 
-// k_min_control with the cell rows: ONE block striding the molecules.  On an overflow it also puts D, V_D, the box and d32 back.
+// k_min_control with the cell rows: ONE block striding the molecules.  On an overflow it also puts D, V_D, the box and d32 back,
+// before the skeleton latches it.
 __global__ __launch_bounds__(kThreads) void k_min_control_cell(MinCellCtlArgs a) {
-  __shared__ int bad;
   const MinState& st = a.base.st;
-  if (st.head[2]) return;  // frozen
-  const bool fresh = st.head[3] != 0;
-  if (a.base.counts && a.base.counts[2]) {
-    if (!fresh)  // nothing was saved before the first control
+  if (!st.head[kHeadStatus] && a.base.counts && a.base.counts[2]) {
+    if (!st.head[kHeadFresh])  // nothing was saved before the first control
       for (int m = threadIdx.x; m < a.base.B; m += kThreads)
         for (int k = 0; k < 9; ++k) {
           const int j = m * 9 + k;
@@ -394,66 +336,38 @@ __global__ __launch_bounds__(kThreads) void k_min_control_cell(MinCellCtlArgs a)
           a.cs.d32[j] = a.cs.d32_prev[j];
         }
     __syncthreads();  // (every thread has read the status word)
-    if (threadIdx.x == 0) st.head[2] = 1u;
-    return;
   }
-  const uint64_t step = loop_step(st.head) + (fresh ? 0 : 1);
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  MinCellOut o;
-  int why = 0;
-  for (int m = threadIdx.x; m < a.base.B; m += kThreads) {
-    min_cell_eval(a, m, fresh, (int64_t)step, &o);
-    if (o.ret == tn_min::FIRE_UNUSABLE && o.why > why) why = o.why;
-  }
-  if (why) atomicMax(&bad, why);  // (an integer in LDS)
-  __syncthreads();
-  if (bad) {
-    if (threadIdx.x == 0) {
-      st.head[8] = (uint32_t)bad;
-      st.head[2] = 2u;
-    }
-    return;
-  }
-  for (int m = threadIdx.x; m < a.base.B; m += kThreads) {
-    min_cell_eval(a, m, fresh, (int64_t)step, &o);
-    st.dt[m] = o.s.dt;
-    st.alpha[m] = o.s.alpha;
-    st.n_pos[m] = o.s.n_pos;
-    st.conv[m] = o.s.converged_at;
-    for (int k = 0; k < 3; ++k) st.coef[m * 3 + k] = o.coef[k];
-    for (int k = 0; k < 9; ++k) {
-      const int j = m * 9 + k;
-      a.cs.D_next[j] = o.Dn[k];
-      a.cs.VD_next[j] = o.VDn[k];
-      a.cs.box_next[j] = o.boxn[k];
-      a.cs.d32_next[j] = o.d32n[k];
-      if (a.stress_row) a.stress_row[j] = o.stress[k];
-      if (a.cell_force_row) a.cell_force_row[j] = o.Gc[k];
-    }
-    if (a.volume_row) a.volume_row[m] = o.V;
-    if (a.base.energy && a.base.epot_row) a.base.epot_row[m] = a.base.energy[m];
-    if (a.base.fmax_row) a.base.fmax_row[m] = (float)sqrt(o.sums[3]);
-    if (a.base.sums_row)
-      for (int k = 0; k < 4; ++k) a.base.sums_row[(int64_t)m * 4 + k] = o.atoms[k];
-    if (a.base.coef_row)
-      for (int k = 0; k < 3; ++k) a.base.coef_row[(int64_t)m * 3 + k] = o.coef[k];
-    if (a.base.dt_row) a.base.dt_row[m] = o.s.dt;
-    if (a.base.alpha_row) a.base.alpha_row[m] = o.s.alpha;
-    if (a.base.conv_row) a.base.conv_row[m] = o.s.converged_at;
-    if (a.move) min_cell_commit(a.cs, a.box, a.deform, a.cell_vel, m);
-  }
-  if (threadIdx.x == 0) {
-    loop_set_step(st.head, step);
-    st.head[3] = 0u;
-  }
+  optimiser_control(
+      st.head, a.base.counts, kMinCellCauseWord, true, a.base.B,
+      [&](int m, bool fresh, uint64_t step) {
+        MinCellOut o;
+        min_cell_eval(a, m, fresh, (int64_t)step, &o);
+        return o.ret == tn_min::FIRE_UNUSABLE ? o.why : 0;
+      },
+      [&](int m, bool fresh, uint64_t step) {
+        MinCellOut o;
+        min_cell_eval(a, m, fresh, (int64_t)step, &o);
+        fire_store(fire_units(st), m, o.s, o.coef);
+        for (int k = 0; k < 9; ++k) {
+          const int j = m * 9 + k;
+          a.cs.D_next[j] = o.Dn[k];
+          a.cs.VD_next[j] = o.VDn[k];
+          a.cs.box_next[j] = o.boxn[k];
+          a.cs.d32_next[j] = o.d32n[k];
+          if (a.stress_row) a.stress_row[j] = o.stress[k];
+          if (a.cell_force_row) a.cell_force_row[j] = o.Gc[k];
+        }
+        if (a.volume_row) a.volume_row[m] = o.V;
+        a.base.rows.write(m, a.base.energy ? a.base.energy + m : nullptr, o.atoms, o.sums[3], o.coef, o.s);
+        if (a.move) min_cell_commit(a.cs, a.box, a.deform, a.cell_vel, m);
+      });
 }
 
 // OPEN: the cell's part of the move from what the last control prepared, before the per-atom kernel
 __global__ __launch_bounds__(kThreads) void k_min_cell_commit(MinState st, MinCell cs, int B, float* box, double* deform,
                                                                   double* cell_vel) {
   const int m = blockIdx.x * kThreads + threadIdx.x;
-  if (m >= B || st.head[2] || st.head[3]) return;  // frozen, or straight after a reset: nothing is prepared yet
+  if (m >= B || st.head[kHeadStatus] || st.head[kHeadFresh]) return;  // frozen, or straight after a reset: nothing is prepared yet
   min_cell_commit(cs, box, deform, cell_vel, m);
 }
 
@@ -470,7 +384,7 @@ __global__ __launch_bounds__(kThreads) void k_min_atoms_cell(MinCellAtomArgs c) 
   const MinAtomArgs& a = c.base;
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= a.N) return;
-  const uint32_t status = a.st.head[2], fresh = a.st.head[3];
+  const uint32_t status = a.st.head[kHeadStatus], fresh = a.st.head[kHeadFresh];
   const int64_t m = a.batch ? a.batch[i] : 0;
   const bool mol_ok = m >= 0 && m < a.B;
   if (status) {
@@ -543,10 +457,7 @@ __global__ __launch_bounds__(kThreads) void k_min_reset_cell(MinState st, MinCel
                                                                  const float* pos, float* xt) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i == 0) {
-    loop_set_step(st.head, step0);
-    st.head[2] = 0u;
-    st.head[3] = 1u;
-    st.head[8] = 0u;
+    loop_head_reset(st.head, step0, kMinCellCauseWord);
     st.start[0] = dt0;
     st.start[1] = alpha0;
   }
@@ -617,13 +528,7 @@ int tmdnet_min_advance(tmdnet_model* m, void* stream, void* graph_ws, void* min_
     c.p.n_min = n_min;
     c.counts = counts;
     c.energy = energy;
-    c.epot_row = epot_log_row;
-    c.fmax_row = fmax_log_row;
-    c.sums_row = sums_log_row;
-    c.coef_row = coef_log_row;
-    c.dt_row = dt_log_row;
-    c.alpha_row = alpha_log_row;
-    c.conv_row = converged_log_row;
+    c.rows = {epot_log_row, fmax_log_row, sums_log_row, coef_log_row, dt_log_row, alpha_log_row, converged_log_row};
     c.st = st;
     hipLaunchKernelGGL(k_min_control, dim3(1), block, 0, s, c);
   }
@@ -652,13 +557,7 @@ int tmdnet_min_advance(tmdnet_model* m, void* stream, void* graph_ws, void* min_
 
 int tmdnet_min_status(void* stream, void* min_ws, uint64_t host[2]) {
   if (!min_ws || !host) return TMDNET_ERR_INVALID;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t head[3] = {0, 0, 0};
-  if (hipMemcpyAsync(head, carve_min(min_ws, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = loop_step(head);
-  host[1] = head[2];
-  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
+  return loop_read_status(stream, carve_min(min_ws, 0, 0).head, 3, -1, host, 2);
 }
 
 int tmdnet_min_workspace_bytes_cell(int64_t n_atoms, int64_t n_mol, size_t* bytes) {
@@ -719,13 +618,7 @@ int tmdnet_min_advance_cell(tmdnet_model* m, void* stream, void* graph_ws, void*
     c.base.p.n_min = n_min;
     c.base.counts = counts;
     c.base.energy = energy;
-    c.base.epot_row = epot_log_row;
-    c.base.fmax_row = fmax_log_row;
-    c.base.sums_row = sums_log_row;
-    c.base.coef_row = coef_log_row;
-    c.base.dt_row = dt_log_row;
-    c.base.alpha_row = alpha_log_row;
-    c.base.conv_row = converged_log_row;
+    c.base.rows = {epot_log_row, fmax_log_row, sums_log_row, coef_log_row, dt_log_row, alpha_log_row, converged_log_row};
     c.base.st = st;
     c.cs = cs;
     for (int k = 0; k < 9; ++k) c.cp.mask[k] = mask[k] != 0.0 ? 1.0 : 0.0;
@@ -772,14 +665,7 @@ int tmdnet_min_advance_cell(tmdnet_model* m, void* stream, void* graph_ws, void*
 
 int tmdnet_min_status_cell(void* stream, void* min_ws, uint64_t host[3]) {
   if (!min_ws || !host) return TMDNET_ERR_INVALID;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t head[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipMemcpyAsync(head, carve_min(min_ws, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = loop_step(head);
-  host[1] = head[2];
-  host[2] = head[2] == 2 ? head[8] : 0;
-  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
+  return loop_read_status(stream, carve_min(min_ws, 0, 0).head, kMinCellCauseWord + 1, kMinCellCauseWord, host, 3);
 }
 
 }  // extern "C"

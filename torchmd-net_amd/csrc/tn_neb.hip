@@ -115,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void k_neb_path(NebState st, NebGeom g, c
                                                           const float* __restrict__ pos, const float* __restrict__ forces,
                                                           const uint8_t* __restrict__ fixed) {
   __shared__ double sh[6][kThreads / 64];
-  if (st.head[2]) return;           // frozen
+  if (st.head[kHeadStatus]) return;           // frozen
   if (counts && counts[2]) return;  // overflowed: stale forces, the controller latches it
   const int img = blockIdx.x, s = blockIdx.y, i = img % g.M;
   if (i == 0 || i == g.M - 1) return;  // an endpoint has no tangent
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void k_neb_project(NebState st, NebGeom g
                                                              const float* __restrict__ forces, const float* __restrict__ energy,
                                                              const uint8_t* __restrict__ fixed, double spring_k) {
   __shared__ double sh[4][kThreads / 64];
-  if (st.head[2]) return;
+  if (st.head[kHeadStatus]) return;
   if (counts && counts[2]) return;
   const int img = blockIdx.x, s = blockIdx.y, i = img % g.M;
   const int a0 = (int)((int64_t)g.n * s / g.S), a1 = (int)((int64_t)g.n * (s + 1) / g.S);
@@ -207,12 +207,7 @@ struct NebCtlArgs {
   const int* counts;  // the graph's counters, or NULL
   const float* energy;
   float* epot_row;      // [G, M]
-  float* fmax_row;      // [G]
-  double* sums_row;     // [G, 4]
-  float* coef_row;      // [G, 3]
-  double* dt_row;       // [G]
-  double* alpha_row;    // [G]
-  int64_t* conv_row;    // [G]
+  FireRows rows;        // [G, ...]; its epot is NULL: the band's energy row is epot_row
   double* path_row;     // [G, M, 5]
   double* weights_row;  // [G, M, 2]
   float* tcoef_row;     // [G, M, 2]
@@ -227,109 +222,58 @@ __device__ __forceinline__ int neb_load(const NebCtlArgs& a, int b, bool fresh, 
   int why = 0;
   for (int i = 1; i < a.g.M - 1; ++i) {
     const int img = b * a.g.M + i;
-    const double* sl = a.st.fire_slices + (int64_t)img * a.g.S * 4;
-    double t[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int k = 0; k < a.g.S; ++k) {
-      t[0] += sl[k * 4 + 0];
-      t[1] += sl[k * 4 + 1];
-      t[2] += sl[k * 4 + 2];
-      t[3] = sl[k * 4 + 3] > t[3] ? sl[k * 4 + 3] : t[3];
-    }
+    double t[4];
+    slice_sums<4, 8u>(a.st.fire_slices + (int64_t)img * a.g.S * 4, a.g.S, 4, t);
     sums[0] += t[0];
     sums[1] += t[1];
     sums[2] += t[2];
     sums[3] = t[3] > sums[3] ? t[3] : sums[3];
     why = a.st.img_why[img] > why ? a.st.img_why[img] : why;
   }
-  if (fresh) {
-    s->dt = a.st.start[0];
-    s->alpha = a.st.start[1];
-    s->n_pos = 0;
-    s->converged_at = -1;
-  } else {
-    s->dt = a.st.dt[b];
-    s->alpha = a.st.alpha[b];
-    s->n_pos = a.st.n_pos[b];
-    s->converged_at = a.st.conv[b];
-  }
+  fire_load(fire_units(a.st), b, fresh, s);
   return why;
 }
 
-// ONE block striding the bands, after k_neb_project: k_min_control with the tangents' causes.  Pass 1: is any band that still moves
-// unusable?  Pass 2, only when none is: every band's state, coefficients and log rows; then thread 0 advances the step counter.
+// ONE block striding the bands, after k_neb_project: optimiser_control (tn_loop.h) with FIRE's two passes and the tangents' causes
 __global__ __launch_bounds__(kThreads) void k_neb_control(NebCtlArgs a) {
-  __shared__ int bad;
-  if (a.st.head[2]) return;  // frozen
-  if (a.counts && a.counts[2]) {
-    if (threadIdx.x == 0) a.st.head[2] = 1u;
-    return;
-  }
-  const bool fresh = a.st.head[3] != 0;
-  const uint64_t step = loop_step(a.st.head) + (fresh ? 0 : 1);
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();  // (every thread has read the header by now: thread 0 rewrites it at the end)
-  int cause = 0;
-  double sums[4];
-  float coef[3];
-  tn_min::FireState s;
-  for (int b = threadIdx.x; b < a.g.G; b += kThreads) {
-    const int why = neb_load(a, b, fresh, sums, &s);
-    if (s.converged_at >= 0) continue;  // a band that has converged looks at nothing
-    int c = why;
-    if (!c && tn_min::fire_control(&s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef) == tn_min::FIRE_UNUSABLE)
-      c = tn_neb::NEB_BAD_SUMS;
-    cause = c > cause ? c : cause;
-  }
-  if (cause) atomicMax(&bad, cause);  // (an integer in LDS)
-  __syncthreads();
-  if (bad) {
-    if (threadIdx.x == 0) {
-      a.st.head[kNebCauseWord] = (uint32_t)bad;
-      a.st.head[2] = 2u;
-    }
-    return;
-  }
-  const int M = a.g.M;
-  for (int b = threadIdx.x; b < a.g.G; b += kThreads) {
-    neb_load(a, b, fresh, sums, &s);
-    tn_min::fire_control(&s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef);
-    a.st.dt[b] = s.dt;
-    a.st.alpha[b] = s.alpha;
-    a.st.n_pos[b] = s.n_pos;
-    a.st.conv[b] = s.converged_at;
+  optimiser_control(
+      a.st.head, a.counts, kNebCauseWord, true, a.g.G,
+      [&](int b, bool fresh, uint64_t step) {
+        double sums[4];
+        float coef[3];
+        tn_min::FireState s;
+        int c = neb_load(a, b, fresh, sums, &s);
+        if (s.converged_at >= 0) return 0;  // a band that has converged looks at nothing
+        if (!c && tn_min::fire_control(&s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef) == tn_min::FIRE_UNUSABLE)
+          c = tn_neb::NEB_BAD_SUMS;
+        return c;
+      },
+      [&](int b, bool fresh, uint64_t step) {
+        const int M = a.g.M;
+        double sums[4];
+        float coef[3];
+        tn_min::FireState s;
+        neb_load(a, b, fresh, sums, &s);
+        tn_min::fire_control(&s, a.p, sums[0], sums[1], sums[2], sums[3], (int64_t)step, coef);
+        fire_store(fire_units(a.st), b, s, coef);
+        if (a.epot_row)
+          for (int i = 0; i < M; ++i) a.epot_row[b * M + i] = a.energy[b * M + i];
+        a.rows.write(b, nullptr, sums, sums[3], coef, s);
+        if (a.climber_row) a.climber_row[b] = tn_neb::climber(a.energy + (int64_t)b * M, M);
+        for (int i = 0; i < M; ++i) {  // an endpoint's rows are zero
+          const int64_t img = (int64_t)b * M + i;
+          const bool inner = i > 0 && i < M - 1;
+          if (a.path_row)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) a.st.coef[b * 3 + k] = coef[k];
-    if (a.epot_row)
-      for (int i = 0; i < M; ++i) a.epot_row[b * M + i] = a.energy[b * M + i];
-    if (a.fmax_row) a.fmax_row[b] = (float)sqrt(sums[3]);
-    if (a.sums_row)
+            for (int k = 0; k < 5; ++k) a.path_row[img * 5 + k] = inner ? a.st.img_sums[img * 5 + k] : 0.0;
+          if (a.weights_row)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) a.sums_row[(int64_t)b * 4 + k] = sums[k];
-    if (a.coef_row)
+            for (int k = 0; k < 2; ++k) a.weights_row[img * 2 + k] = inner ? a.st.img_w[img * 2 + k] : 0.0;
+          if (a.tcoef_row)
 #pragma unroll
-      for (int k = 0; k < 3; ++k) a.coef_row[(int64_t)b * 3 + k] = coef[k];
-    if (a.dt_row) a.dt_row[b] = s.dt;
-    if (a.alpha_row) a.alpha_row[b] = s.alpha;
-    if (a.conv_row) a.conv_row[b] = s.converged_at;
-    if (a.climber_row) a.climber_row[b] = tn_neb::climber(a.energy + (int64_t)b * M, M);
-    for (int i = 0; i < M; ++i) {  // an endpoint's rows are zero
-      const int64_t img = (int64_t)b * M + i;
-      const bool inner = i > 0 && i < M - 1;
-      if (a.path_row)
-#pragma unroll
-        for (int k = 0; k < 5; ++k) a.path_row[img * 5 + k] = inner ? a.st.img_sums[img * 5 + k] : 0.0;
-      if (a.weights_row)
-#pragma unroll
-        for (int k = 0; k < 2; ++k) a.weights_row[img * 2 + k] = inner ? a.st.img_w[img * 2 + k] : 0.0;
-      if (a.tcoef_row)
-#pragma unroll
-        for (int k = 0; k < 2; ++k) a.tcoef_row[img * 2 + k] = inner ? a.st.img_s[img * 2 + k] : 0.f;
-    }
-  }
-  if (threadIdx.x == 0) {
-    loop_set_step(a.st.head, step);
-    a.st.head[3] = 0u;
-  }
+            for (int k = 0; k < 2; ++k) a.tcoef_row[img * 2 + k] = inner ? a.st.img_s[img * 2 + k] : 0.f;
+        }
+      });
 }
 
 struct NebAtomArgs {
@@ -350,7 +294,7 @@ template <bool ACCEPT, bool MOVE>
 __global__ __launch_bounds__(kThreads) void k_neb_atoms(NebAtomArgs a) {
   const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (r >= a.N) return;
-  const uint32_t status = a.st.head[2], fresh = a.st.head[3];
+  const uint32_t status = a.st.head[kHeadStatus], fresh = a.st.head[kHeadFresh];
   if (status) {
     if (ACCEPT && status == 1u && !fresh && a.counts && a.counts[2]) {
 #pragma unroll
@@ -394,11 +338,8 @@ __global__ __launch_bounds__(kThreads) void k_neb_atoms(NebAtomArgs a) {
 
 __global__ void k_neb_reset(NebState st, uint64_t step0, double dt0, double alpha0, uint32_t climb) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    loop_set_step(st.head, step0);
-    st.head[2] = 0u;
-    st.head[3] = 1u;
+    loop_head_reset(st.head, step0, kNebCauseWord);
     st.head[kNebClimbWord] = climb;
-    st.head[kNebCauseWord] = 0u;
     st.start[0] = dt0;
     st.start[1] = alpha0;
   }
@@ -472,12 +413,7 @@ int tmdnet_neb_advance(tmdnet_model* m, void* stream, void* graph_ws, void* neb_
     c.counts = counts;
     c.energy = energy;
     c.epot_row = epot_log_row;
-    c.fmax_row = fmax_log_row;
-    c.sums_row = sums_log_row;
-    c.coef_row = coef_log_row;
-    c.dt_row = dt_log_row;
-    c.alpha_row = alpha_log_row;
-    c.conv_row = converged_log_row;
+    c.rows = {nullptr, fmax_log_row, sums_log_row, coef_log_row, dt_log_row, alpha_log_row, converged_log_row};
     c.path_row = path_sums_log_row;
     c.weights_row = weights_log_row;
     c.tcoef_row = tangent_coef_log_row;
@@ -509,14 +445,7 @@ int tmdnet_neb_advance(tmdnet_model* m, void* stream, void* graph_ws, void* neb_
 
 int tmdnet_neb_status(void* stream, void* neb_ws, uint64_t host[3]) {
   if (!neb_ws || !host) return TMDNET_ERR_INVALID;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t head[kNebHeadWords] = {0, 0, 0, 0, 0, 0};
-  if (hipMemcpyAsync(head, carve_neb(neb_ws, 0, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = loop_step(head);
-  host[1] = head[2];
-  host[2] = head[2] == 2 ? head[kNebCauseWord] : 0;
-  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
+  return loop_read_status(stream, carve_neb(neb_ws, 0, 0, 0).head, kNebHeadWords, kNebCauseWord, host, 3);
 }
 
 }  // extern "C"

@@ -100,7 +100,7 @@ struct ScanGeom {
   int n, G, S;
 };
 
-__device__ __forceinline__ bool scan_live(const ScanState& st, int g) { return st.head[3] != 0 || st.conv[g] < 0; }
+__device__ __forceinline__ bool scan_live(const ScanState& st, int g) { return st.head[kHeadFresh] != 0 || st.conv[g] < 0; }
 
 // the distinct CV atom that `atom` is, or -1
 __device__ __forceinline__ int scan_find(const Tables& T, int atom) {
@@ -128,11 +128,11 @@ __global__ __launch_bounds__(kThreads) void k_scan_project(ScanProjectArgs a) {
   __shared__ float sh_mult[2 * kMaxCv], sh_corr[kMaxAtoms * 6];
   __shared__ double sh_dv[2 * kMaxCv];
   __shared__ int sh_why;
-  if (a.st.head[2]) return;               // frozen
+  if (a.st.head[kHeadStatus]) return;               // frozen
   if (a.counts && a.counts[2]) return;    // overflowed: stale forces, the controller latches it
   const int g = blockIdx.x, s = blockIdx.y, t = threadIdx.x;
   if (!scan_live(a.st, g)) return;  // a point that has converged looks at nothing
-  const bool fresh = a.st.head[3] != 0;
+  const bool fresh = a.st.head[kHeadFresh] != 0;
   const int64_t row0 = (int64_t)g * a.g.n;
   if (t < a.T.A) {
     const int64_t r = row0 + a.T.atom_rel[t];
@@ -203,13 +203,7 @@ struct ScanCtlArgs {
   const int* counts;
   const float* energy;    // [G]
   const double* t_fin;    // [G, D]
-  float* epot_row;        // [G]
-  float* fmax_row;        // [G]
-  double* sums_row;       // [G, 4]
-  float* coef_row;        // [G, 3]
-  double* dt_row;         // [G]
-  double* alpha_row;      // [G]
-  int64_t* conv_row;      // [G]
+  FireRows rows;          // [G, ...]
   double* cv_row;         // [G, D]
   double* target_row;     // [G, D]
   float* mult_row;        // [G, 2, D] lambda, mu
@@ -217,101 +211,54 @@ struct ScanCtlArgs {
   ScanState st;
 };
 
+// the sums of point g in slice order, its state (after a reset: the start values of the header), and whether it stands at its
+// final targets
 __device__ __forceinline__ void scan_ctl_load(const ScanCtlArgs& a, int g, bool fresh, double sums[4], tn_min::FireState* s, int* here) {
-  sums[0] = sums[1] = sums[2] = sums[3] = 0.0;
-  const double* sl = a.st.slices + (int64_t)g * a.g.S * 4;
-  for (int k = 0; k < a.g.S; ++k) {
-    sums[0] += sl[k * 4 + 0];
-    sums[1] += sl[k * 4 + 1];
-    sums[2] += sl[k * 4 + 2];
-    sums[3] = sl[k * 4 + 3] > sums[3] ? sl[k * 4 + 3] : sums[3];
-  }
-  if (fresh) {
-    s->dt = a.st.start[0];
-    s->alpha = a.st.start[1];
-    s->n_pos = 0;
-    s->converged_at = -1;
-  } else {
-    s->dt = a.st.dt[g];
-    s->alpha = a.st.alpha[g];
-    s->n_pos = a.st.n_pos[g];
-    s->converged_at = a.st.conv[g];
-  }
+  slice_sums<4, 8u>(a.st.slices + (int64_t)g * a.g.S * 4, a.g.S, 4, sums);
+  fire_load(fire_units(a.st), g, fresh, s);
   *here = arrived(a.D, a.st.t_cur + g * kMaxCv, a.t_fin + (int64_t)g * a.D);
 }
 
-// ONE block striding the points, after k_scan_project.  Pass 1: is any point that still moves unusable?  Pass 2, only when none is:
-// every point's state, coefficients and log rows; then thread 0 advances the step counter.
+// ONE block striding the points, after k_scan_project: optimiser_control (tn_loop.h) with FIRE's two passes and the causes of the
+// projection and of the last constraint step
 __global__ __launch_bounds__(kThreads) void k_scan_control(ScanCtlArgs a) {
-  __shared__ int bad;
-  if (a.st.head[2]) return;  // frozen
-  if (a.counts && a.counts[2]) {
-    if (threadIdx.x == 0) a.st.head[2] = 1u;
-    return;
-  }
-  const bool fresh = a.st.head[3] != 0;
-  const uint64_t step = loop_step(a.st.head) + (fresh ? 0 : 1);
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();  // (every thread has read the header by now: thread 0 rewrites it at the end)
-  int cause = 0, here;
-  double sums[4];
-  float coef[3];
-  tn_min::FireState s;
-  for (int g = threadIdx.x; g < a.g.G; g += kThreads) {
-    scan_ctl_load(a, g, fresh, sums, &s, &here);
-    if (s.converged_at >= 0) continue;  // a point that has converged looks at nothing
-    int c = fresh ? 0 : a.st.why2[g];
-    if (!c) c = a.st.why[g];
-    if (!c && scan_fire(&s, a.p, sums, here, (int64_t)step, coef) == tn_min::FIRE_UNUSABLE) c = SCAN_BAD_SUMS;
-    if (!c && !isfinite(a.energy[g])) c = SCAN_BAD_SUMS;
-    cause = c > cause ? c : cause;
-  }
-  if (cause) atomicMax(&bad, cause);  // (an integer in LDS)
-  __syncthreads();
-  if (bad) {
-    if (threadIdx.x == 0) {
-      a.st.head[kScanCauseWord] = (uint32_t)bad;
-      a.st.head[2] = 2u;
-    }
-    return;
-  }
-  for (int g = threadIdx.x; g < a.g.G; g += kThreads) {
-    scan_ctl_load(a, g, fresh, sums, &s, &here);
-    // (a point that had converged: its slice sums, CVs, multipliers and corrections are those of the step it converged at, since
-    // the projection no longer looks at it, and every row below repeats them)
-    scan_fire(&s, a.p, sums, here, (int64_t)step, coef);
-    a.st.dt[g] = s.dt;
-    a.st.alpha[g] = s.alpha;
-    a.st.n_pos[g] = s.n_pos;
-    a.st.conv[g] = s.converged_at;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a.st.coef[g * 3 + k] = coef[k];
-    if (a.dt_row) a.dt_row[g] = s.dt;
-    if (a.alpha_row) a.alpha_row[g] = s.alpha;
-    if (a.conv_row) a.conv_row[g] = s.converged_at;
-    if (a.coef_row)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) a.coef_row[(int64_t)g * 3 + k] = coef[k];
-    if (a.epot_row) a.epot_row[g] = a.energy[g];
-    if (a.fmax_row) a.fmax_row[g] = (float)sqrt(sums[3]);
-    if (a.sums_row)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) a.sums_row[(int64_t)g * 4 + k] = sums[k];
-    for (int c = 0; c < a.D; ++c) {
-      if (a.cv_row) a.cv_row[(int64_t)g * a.D + c] = a.st.cv[g * kMaxCv + c];
-      if (a.target_row) a.target_row[(int64_t)g * a.D + c] = a.st.t_cur[g * kMaxCv + c];
-      if (a.mult_row) {
-        a.mult_row[((int64_t)g * 2 + 0) * a.D + c] = a.st.mult[g * 2 * kMaxCv + c];
-        a.mult_row[((int64_t)g * 2 + 1) * a.D + c] = a.st.mult[g * 2 * kMaxCv + kMaxCv + c];
-      }
-    }
-    if (a.corr_row)
-      for (int k = 0; k < a.A * 6; ++k) a.corr_row[(int64_t)g * a.A * 6 + k] = a.st.corr[(int64_t)g * kMaxAtoms * 6 + k];
-  }
-  if (threadIdx.x == 0) {
-    loop_set_step(a.st.head, step);
-    a.st.head[3] = 0u;
-  }
+  optimiser_control(
+      a.st.head, a.counts, kScanCauseWord, true, a.g.G,
+      [&](int g, bool fresh, uint64_t step) {
+        int here;
+        double sums[4];
+        float coef[3];
+        tn_min::FireState s;
+        scan_ctl_load(a, g, fresh, sums, &s, &here);
+        if (s.converged_at >= 0) return 0;  // a point that has converged looks at nothing
+        int c = fresh ? 0 : a.st.why2[g];
+        if (!c) c = a.st.why[g];
+        if (!c && scan_fire(&s, a.p, sums, here, (int64_t)step, coef) == tn_min::FIRE_UNUSABLE) c = SCAN_BAD_SUMS;
+        if (!c && !isfinite(a.energy[g])) c = SCAN_BAD_SUMS;
+        return c;
+      },
+      [&](int g, bool fresh, uint64_t step) {
+        int here;
+        double sums[4];
+        float coef[3];
+        tn_min::FireState s;
+        scan_ctl_load(a, g, fresh, sums, &s, &here);
+        // (a point that had converged: its slice sums, CVs, multipliers and corrections are those of the step it converged at, since
+        // the projection no longer looks at it, and every row below repeats them)
+        scan_fire(&s, a.p, sums, here, (int64_t)step, coef);
+        fire_store(fire_units(a.st), g, s, coef);
+        a.rows.write(g, a.energy + g, sums, sums[3], coef, s);
+        for (int c = 0; c < a.D; ++c) {
+          if (a.cv_row) a.cv_row[(int64_t)g * a.D + c] = a.st.cv[g * kMaxCv + c];
+          if (a.target_row) a.target_row[(int64_t)g * a.D + c] = a.st.t_cur[g * kMaxCv + c];
+          if (a.mult_row) {
+            a.mult_row[((int64_t)g * 2 + 0) * a.D + c] = a.st.mult[g * 2 * kMaxCv + c];
+            a.mult_row[((int64_t)g * 2 + 1) * a.D + c] = a.st.mult[g * 2 * kMaxCv + kMaxCv + c];
+          }
+        }
+        if (a.corr_row)
+          for (int k = 0; k < a.A * 6; ++k) a.corr_row[(int64_t)g * a.A * 6 + k] = a.st.corr[(int64_t)g * kMaxAtoms * 6 + k];
+      });
 }
 
 struct ScanAtomArgs {
@@ -336,7 +283,7 @@ __global__ __launch_bounds__(kThreads) void k_scan_atoms(ScanAtomArgs a) {
   const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (r >= a.N) return;
   const int g = (int)(r / a.g.n), atom = (int)(r - (int64_t)g * a.g.n);
-  const uint32_t status = a.st.head[2], fresh = a.st.head[3];
+  const uint32_t status = a.st.head[kHeadStatus], fresh = a.st.head[kHeadFresh];
   if (status) {
     const bool overflowed = status == 1u && a.counts && a.counts[2];
     const bool off_surface = status == 2u && a.st.head[kScanCauseWord] == (uint32_t)SCAN_BAD_STEP;
@@ -415,7 +362,7 @@ __global__ __launch_bounds__(64) void k_scan_constrain(ScanConsArgs a) {
   __shared__ double sh_t[kMaxCv];
   __shared__ int sh_why, sh_iters;
   const int g = blockIdx.x, t = threadIdx.x;
-  if (a.st.head[2] || a.st.head[3]) return;  // frozen, or straight after a reset
+  if (a.st.head[kHeadStatus] || a.st.head[kHeadFresh]) return;  // frozen, or straight after a reset
   if (a.st.conv[g] >= 0) return;             // a point that has converged keeps its bits
   const int64_t row0 = (int64_t)g * a.g.n;
   if (t < a.T.A) {
@@ -455,10 +402,7 @@ __global__ __launch_bounds__(64) void k_scan_constrain(ScanConsArgs a) {
 __global__ __launch_bounds__(kThreads) void k_scan_reset(ScanState st, int G, uint64_t step0, double dt0, double alpha0) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i == 0) {
-    loop_set_step(st.head, step0);
-    st.head[2] = 0u;
-    st.head[3] = 1u;
-    st.head[kScanCauseWord] = 0u;
+    loop_head_reset(st.head, step0, kScanCauseWord);
     st.start[0] = dt0;
     st.start[1] = alpha0;
   }
@@ -550,13 +494,7 @@ int tmdnet_scan_advance(tmdnet_model* m, void* stream, void* graph_ws, void* sca
     c.counts = counts;
     c.energy = energy;
     c.t_fin = targets;
-    c.epot_row = epot_log_row;
-    c.fmax_row = fmax_log_row;
-    c.sums_row = sums_log_row;
-    c.coef_row = coef_log_row;
-    c.dt_row = dt_log_row;
-    c.alpha_row = alpha_log_row;
-    c.conv_row = converged_log_row;
+    c.rows = {epot_log_row, fmax_log_row, sums_log_row, coef_log_row, dt_log_row, alpha_log_row, converged_log_row};
     c.cv_row = cv_log_row;
     c.target_row = target_log_row;
     c.mult_row = multiplier_log_row;
@@ -603,14 +541,7 @@ int tmdnet_scan_advance(tmdnet_model* m, void* stream, void* graph_ws, void* sca
 
 int tmdnet_scan_status(void* stream, void* scan_ws, uint64_t host[3]) {
   if (!scan_ws || !host) return TMDNET_ERR_INVALID;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  uint32_t head[kScanHeadWords] = {0, 0, 0, 0, 0};
-  if (hipMemcpyAsync(head, carve_scan(scan_ws, 0, 0).head, sizeof(head), hipMemcpyDeviceToHost, s) != hipSuccess) return TMDNET_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess) return TMDNET_ERR_HIP;
-  host[0] = loop_step(head);
-  host[1] = head[2];
-  host[2] = head[2] == 2 ? head[kScanCauseWord] : 0;
-  return head[2] == 1 ? TMDNET_ERR_OVERFLOW : head[2] ? TMDNET_ERR_STATE : TMDNET_OK;
+  return loop_read_status(stream, carve_scan(scan_ws, 0, 0).head, kScanHeadWords, kScanCauseWord, host, 3);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@ import ctypes as C
 
 import torch
 
+from torchmdnet_amd import _C
 from torchmdnet_amd.models.utils import _ptr, _stream_ptr
 
 
@@ -108,6 +109,19 @@ class CapturedLoop:
         return RuntimeError("Found num_pairs > max_num_pairs, please increase max_num_pairs "
                             f"(max_num_neighbors={self._model.representation_model.max_num_neighbors}; {self._noun} is frozen at "
                             f"step {step})")
+
+    def _verdict(self, entry, rc, step, status, cause=0, label=None, causes=None):
+        """What ``check()`` makes of the answer of the status entry named ``entry``: the step counter, or the reference's overflow
+        error, or - status 2 of a loop that gives its ``label`` - the error naming the cause (``causes``: cause -> text), or the
+        entry's failure.  A loop whose messages have another shape raises them itself and passes no label."""
+        if rc == _C.ERR_OVERFLOW:
+            raise self._overflow(step)
+        if status == 2 and label is not None:
+            why = (causes or {}).get(cause, "a sum is not finite")
+            raise RuntimeError(f"{label}: after step {step} {why}; the state is frozen at that step")
+        if rc != _C.OK:
+            raise RuntimeError(f"{entry} failed (code {rc})")
+        return step
 
     def _reset(self, copy_in, start, step=0):
         """The skeleton of every ``reset``: ``copy_in()`` validates and then writes the static buffers, the evaluation there raises

@@ -161,14 +161,7 @@ class DeviceDimer(ConvergingLoop):
         unusable - forces or an energy that are not finite, or a mode without length: ``pos`` / ``mode`` / ``forces``, the logs and
         the counter are then those of the last valid step, and replays change nothing until ``reset``.  Returns the step counter."""
         rc, (step, status, cause) = self._status(_C.lib().tmdnet_dimer_status, 3)
-        if rc == _C.ERR_OVERFLOW:
-            raise self._overflow(step)
-        if status == 2:
-            why = _CAUSES.get(cause, "a sum is not finite")
-            raise RuntimeError(f"dimer search: after step {step} {why}; the state is frozen at that step")
-        if rc != _C.OK:
-            raise RuntimeError(f"tmdnet_dimer_status failed (code {rc})")
-        return step
+        return self._verdict("tmdnet_dimer_status", rc, step, status, cause, "dimer search", _CAUSES)
 
     def reset(self, pos: Optional[Tensor] = None, mode: Optional[Tensor] = None, translate: Optional[bool] = None):
         """New midpoints (None: as they are), a new axis (None: the axis and the partner as they are; given, it is orthonormalised on

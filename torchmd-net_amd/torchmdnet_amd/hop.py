@@ -255,14 +255,9 @@ class DeviceHop(CapturedLoop):
         energy or a sum of a walker was not finite: ``pos`` / ``vel``, the walkers' state, the logs and the counter are then those
         of the last valid step, and replays change nothing until ``reset``.  Returns the step counter."""
         rc, (step, status) = self._status(_C.lib().tmdnet_hop_status, 2)
-        if rc == _C.ERR_OVERFLOW:
-            raise self._overflow(step)
-        if status == 2:
-            raise RuntimeError(f"minima hopping: after step {step} an energy or a sum over the forces, velocities or positions of a "
-                               "walker is not finite (a NaN or an infinite energy or force); the state is frozen at that step")
-        if rc != _C.OK:
-            raise RuntimeError(f"tmdnet_hop_status failed (code {rc})")
-        return step
+        why = ("an energy or a sum over the forces, velocities or positions of a walker is not finite (a NaN or an infinite energy or "
+               "force)")
+        return self._verdict("tmdnet_hop_status", rc, step, status, 0, "minima hopping", {0: why})
 
     def reset(self, pos: Optional[Tensor] = None, kT=None, ediff=None, history: str = "clear"):
         """New start geometries (copied into the static buffer; None: the positions as they are), velocity zero, every walker back

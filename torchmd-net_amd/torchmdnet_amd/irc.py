@@ -180,14 +180,7 @@ class DeviceIRC(ConvergingLoop):
         unusable - forces or an energy that are not finite, or a velocity without length: ``pos`` / ``vel`` / ``forces``, the logs and
         the counter are then those of the last valid step, and replays change nothing until ``reset``.  Returns the step counter."""
         rc, (step, status, cause) = self._status(_C.lib().tmdnet_irc_status, 3)
-        if rc == _C.ERR_OVERFLOW:
-            raise self._overflow(step)
-        if status == 2:
-            why = _CAUSES.get(cause, "a sum is not finite")
-            raise RuntimeError(f"IRC: after step {step} {why}; the state is frozen at that step")
-        if rc != _C.OK:
-            raise RuntimeError(f"tmdnet_irc_status failed (code {rc})")
-        return step
+        return self._verdict("tmdnet_irc_status", rc, step, status, cause, "IRC", _CAUSES)
 
     @property
     def truncated(self) -> bool:

@@ -136,14 +136,10 @@ class DeviceLBFGS(ConvergingLoop):
         finite: ``pos`` / ``forces``, the history, the logs and the counter are then those of the last valid step, and replays change
         nothing until ``reset``.  Returns the step counter."""
         rc, (step, status, cause) = self._status(_C.lib().tmdnet_lbfgs_status, 3)
-        if rc == _C.ERR_OVERFLOW:
-            raise self._overflow(step)
         if status == 2:
             raise RuntimeError(f"minimiser: the forces after step {step} are not finite (a NaN or an infinite force sum); the "
                                "state is frozen at that step")
-        if rc != _C.OK:
-            raise RuntimeError(f"tmdnet_lbfgs_status failed (code {rc})")
-        return step
+        return self._verdict("tmdnet_lbfgs_status", rc, step, status)
 
     def reset(self, pos: Optional[Tensor] = None):
         """New positions (copied into the static buffer), forces evaluated there, the history of every molecule emptied, status

@@ -465,8 +465,6 @@ class DeviceMD(CapturedLoop):
         RuntimeError naming the thermostat (``DeviceGlobalMD``) when a move of the global thermostat was unusable (a kinetic energy
         that is not finite): the state is frozen at the closed step, before that move.  Returns the step counter."""
         rc, (step, status) = self._status(_C.lib().tmdnet_md_status, 2)
-        if rc == _C.ERR_OVERFLOW:
-            raise self._overflow(step)
         if status == 2:
             raise RuntimeError(f"barostat: the move after step {step} was not finite (zero volume, or a NaN in the virial or "
                                "the kinetic energy); the MD state is frozen before that move")
@@ -486,9 +484,7 @@ class DeviceMD(CapturedLoop):
             raise RuntimeError(f"thermostat: the {kind} move after step {step} was unusable (a kinetic energy, a scale factor or a "
                                "chain value that is not finite, or a scale factor that is not positive); the MD state is frozen "
                                "before that move")
-        if rc != _C.OK:
-            raise RuntimeError(f"tmdnet_md_status failed (code {rc})")
-        return step
+        return self._verdict("tmdnet_md_status", rc, step, status)
 
     def reset(self, pos: Optional[Tensor] = None, vel: Optional[Tensor] = None, step: int = 0, box: Optional[Tensor] = None,
               observables: str = "clear"):

@@ -230,8 +230,6 @@ class DeviceMinimizer(ConvergingLoop):
         ``box`` / ``deform`` are those of the last valid step as well.  Returns the step counter."""
         L = _C.lib()
         rc, (step, status, cause) = self._status(L.tmdnet_min_status if self.cell is None else L.tmdnet_min_status_cell, 3)
-        if rc == _C.ERR_OVERFLOW:
-            raise self._overflow(step)
         if status == 2 and cause == 2:
             raise RuntimeError(f"minimiser: the virial after step {step} is not finite; the state, the box included, is frozen "
                                "at that step")
@@ -241,9 +239,7 @@ class DeviceMinimizer(ConvergingLoop):
         if status == 2:
             raise RuntimeError(f"minimiser: the forces after step {step} are not finite (a NaN or an infinite force sum); the "
                                "state is frozen at that step")
-        if rc != _C.OK:
-            raise RuntimeError(f"tmdnet_min_status failed (code {rc})")
-        return step
+        return self._verdict("tmdnet_min_status", rc, step, status)
 
     def reset(self, pos: Optional[Tensor] = None, box: Optional[Tensor] = None):
         """New positions (copied into the static buffer), forces evaluated there, velocity zero, every molecule's controller back to

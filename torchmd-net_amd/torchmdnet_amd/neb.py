@@ -153,14 +153,7 @@ class DeviceNEB(ConvergingLoop):
         unusable - band forces or an energy that are not finite, or coincident images: ``images`` / ``forces``, the logs and the
         counter are then those of the last valid step, and replays change nothing until ``reset``.  Returns the step counter."""
         rc, (step, status, cause) = self._status(_C.lib().tmdnet_neb_status, 3)
-        if rc == _C.ERR_OVERFLOW:
-            raise self._overflow(step)
-        if status == 2:
-            why = _CAUSES.get(cause, "a sum is not finite")
-            raise RuntimeError(f"nudged elastic band: after step {step} {why}; the state is frozen at that step")
-        if rc != _C.OK:
-            raise RuntimeError(f"tmdnet_neb_status failed (code {rc})")
-        return step
+        return self._verdict("tmdnet_neb_status", rc, step, status, cause, "nudged elastic band", _CAUSES)
 
     def reset(self, images: Optional[Tensor] = None, climb: Optional[bool] = None):
         """New images (copied into the static buffer; None: the path as it is), ``climb`` switched (None: as it is), forces evaluated

@@ -192,14 +192,7 @@ class DeviceScan(ConvergingLoop):
         constraint step that did not converge: ``pos`` / ``forces``, the logs and the counter are then those of the last valid step,
         and replays change nothing until ``reset``.  Returns the step counter."""
         rc, (step, status, cause) = self._status(_C.lib().tmdnet_scan_status, 3)
-        if rc == _C.ERR_OVERFLOW:
-            raise self._overflow(step)
-        if status == 2:
-            why = _CAUSES.get(cause, "a sum is not finite")
-            raise RuntimeError(f"scan: after step {step} {why}; the state is frozen at that step")
-        if rc != _C.OK:
-            raise RuntimeError(f"tmdnet_scan_status failed (code {rc})")
-        return step
+        return self._verdict("tmdnet_scan_status", rc, step, status, cause, "scan", _CAUSES)
 
     def reset(self, pos: Optional[Tensor] = None, targets: Optional[Tensor] = None):
         """New start geometries ([n,3], shared, or [G,n,3]; None: the positions as they are) and new final targets ([G,D]; None: as
